@@ -15,9 +15,9 @@ lone tick of this size is a 13 us launch on a mostly idle device.
 So `--batch` ticks (default 128) go through ONE launch sequence (rm_batch_run_sources_device), and
 `--inflight` contexts (default 3), each with its own stream, take the batches in turn.  The
 strictly sequential rate (one tick at a time, what a closed-loop simulation sees) is measured in
-the same run and printed as "sequential_ticks".
+the same run with `--full` and printed as "sequential_ticks".
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload c2|c3|udgm|m1|...]
+    python bench.py [--gpus N --steps K --warmup W] [--workload c2|c3|udgm|m1|...] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 N > 1: receivers are partitioned over the ranks (regions of the plane); per batch each rank packs the source indices of
@@ -32,15 +32,17 @@ collective.  Rank 0 prints ONE JSON line.
 
 Map of this file.  What the driver runs is `python bench.py` with no flags (and `--gpus N --steps K --warmup W`): main() ->
 measure(): workload c3 = BASELINE configs[2], 128 ticks per launch, three contexts; its timed region is the K steps between
-fence() and fence() (barrier + synchronize on both sides, MAX over ranks), and `value`, `ms_per_step`, `roofline` come from it
-alone.  Everything else on the line is an extra key measured AFTER the timed region, each by its own function, and none of it
-enters `value`:
+fence() and fence() (barrier + synchronize on both sides, MAX over ranks), and `value`, `ms_per_step` come from it alone.  A plain
+run does nothing else: set-up, warm-up, the K steps, `--dump-outputs DIR` (dump_outputs(): the heard links of the last step's
+ticks as .npy files), the result line.  `--full` adds the kernel probes inside the timed region and the extra keys, each measured
+AFTER the timed region by its own function, none of them entering `value`:
     roofline_object()     the `roofline` object of a run (kernel intervals from the library's probes, 8(d) bytes, cross-check)
     cpu_baseline()        `cpu_baseline`: the oracle (oracle/rm_oracle.c) on a bounded sample, rank 0, one GPU only
     sequential (inline)   `sequential_ticks`: the same ticks one at a time on one context
     host_transfer_legs()  `with_host_transfer`: the PCIe-inclusive closed loops (never `value`)
     scale_probe()         `at_1M_nodes`: a short run at a million nodes
     dense_probe()         `dense_layout`: the reference's default Null medium and a unit disc over the whole field
+    (several GPUs)        `weak_scaling`: the same run once more with the node count grown as sqrt(GPUs)
 Modes behind flags (none of them the driver's path): --workload (the other BASELINE configs), --as-rank R:W (one rank's share on
 one GPU), --dense-only, --force-sharded / --collective / --partition (the multi-GPU driver on one GPU, rehearsals), --nodes,
 --link-capacity, --batch, --inflight.  spawn_ranks() starts the ranks of `--gpus N` when no launcher did; dry_run() is the
@@ -62,6 +64,7 @@ import numpy as np  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 S_NODE, S_TX, S_REC = 37, 56, 25   # algorithmic bytes: SURVEY.md section 8(d)
+DUMP_BUDGET, DUMP_SEED = 48 << 20, 20240601   # --dump-outputs: bytes written at most (all ranks), seed of the tick sample
 
 WORKLOADS = {
     # name: (config index, N, tx fraction, model name, description)
@@ -138,7 +141,14 @@ def parse():
     ap.add_argument("--force-sharded", action="store_true",
                     help="use the pipelined multi-GPU tick driver even on one GPU (testing)")
     ap.add_argument("--profile-every", type=int, default=16,
-                    help="HIP-event sample of the dominant kernel every n-th tick of the timed region")
+                    help="--full: HIP-event sample of the dominant kernel every n-th tick of the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: kernel probes in the timed region, `roofline`, and the extra keys measured "
+                         "after it (sequential_ticks, with_host_transfer, at_1M_nodes, dense_layout, cpu_baseline, weak_scaling); "
+                         "the --no-* options above leave out single ones")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the heard links of the last step's ticks to DIR/<name>.npy (float32 / float64; "
+                         "a fixed, seeded sample of the ticks where all of them would exceed %d MB)" % (DUMP_BUDGET >> 20))
     return ap.parse_args()
 
 
@@ -1093,12 +1103,13 @@ def timed_region(run, issue):
     issue(0, run.warm_ticks)
     issue(run.warm_ticks, run.ticks, plan_only=True)     # the timed steps' calls, arguments converted
     fence(run)
-    # kernel probes on a few launch sequences of every context: the roofline line takes its kernel times from sequences that run
-    # alone after the region; these samples only feed the cross-check, so that the probes cost the headline next to nothing
+    # --full: kernel probes on a few launch sequences of every context: the roofline line takes its kernel times from sequences
+    # that run alone after the region; these samples only feed the cross-check, so that the probes cost the headline next to nothing
+    probes = run.args.full
     every = run.args.profile_every if run.batch == 1 else 4
     if run.steps <= 8 * run.inflight:
         every = 1 if run.steps <= 2 * run.inflight else 2
-    for e in run.engines:
+    for e in run.engines if probes else ():
         e.profile_enable(every)
     t_start = time.perf_counter()
     run.links_done = 0
@@ -1106,7 +1117,7 @@ def timed_region(run, issue):
     fence(run)
     elapsed = time.perf_counter() - t_start
     n_samples, kernels = 0, {}
-    for e in run.engines:
+    for e in run.engines if probes else ():
         ns, _ = e.profile_read()
         for name, (launches, ms, stage) in e.profile_kernels().items():
             k = kernels.setdefault(name, {"launches": 0, "ms": 0.0, "stage": stage})
@@ -1187,6 +1198,56 @@ def sequential_leg(run, links_per_tick, timed_ticks, heard):
     return sequential
 
 
+def last_step_views(run):
+    """the heard links of every tick of the last timed step, as a caller of that step reads them: the host view of the result
+    slots of the context that ran it (one packing launch, one wait)"""
+    if run.batch > 1:
+        eng, nb = run.last_run[0], run.last_run[1] + 1
+    elif run.sharded is not None:                  # mode_torch_ticks: the context of the tick staged (and swept) last
+        eng, nb = run.engines[run.sharded.staged[2] % run.inflight], 1
+    else:                                          # mode_lone_ticks: tick k on context k % inflight
+        eng, nb = run.engines[(run.ticks - 1) % run.inflight], 1
+    views, _ = eng.batch_result_view(nb)
+    return views
+
+
+def dump_outputs(run, out_dir):
+    """--dump-outputs DIR: what the last timed step computed, as .npy files.  `heard_per_tick` (every tick of the step), then the
+    links of whole ticks taken in a seeded order while they fit DUMP_BUDGET (`sampled_ticks`, ascending; a seeded sample of the
+    first one's links, `sampled_links`, if that tick alone does not fit), packet-major / receiver ascending as the engine orders
+    them: `pkt` (the frame's index in its tick), `dst`, `verdict` as float32 (exact: all below 2^24), `rssi` (and `sinr` where the
+    medium has that column) as float64.  Several ranks: each writes its own share, `<name>_rank<r>.npy`."""
+    views = last_step_views(run)
+    counts = np.array([v.count for v in views], dtype=np.int64)
+    cols = ["pkt", "dst", "verdict", "rssi"] + (["sinr"] if run.sinr_column else [])
+    per_link = 3 * 4 + (len(cols) - 3) * 8
+    budget = DUMP_BUDGET // max(1, run.env.world) - 8 * 2 * len(views)
+    rng = np.random.default_rng(DUMP_SEED)
+    order = rng.permutation(len(views))
+    picked, used = [], 0
+    for b in order:
+        if used + counts[b] * per_link > budget:
+            break
+        picked.append(int(b))
+        used += counts[b] * per_link
+    links = None
+    if not picked:
+        picked = [int(order[0])]
+        links = np.sort(rng.choice(counts[picked[0]], budget // (per_link + 8), replace=False))   # (+ its index)
+    picked.sort()
+    out = {"heard_per_tick": counts.astype(np.float64), "sampled_ticks": np.array(picked, dtype=np.float64)}
+    for c in cols:
+        parts = [np.asarray(getattr(views[b], c)) for b in picked]
+        a = np.concatenate(parts) if parts else np.zeros(0)
+        out[c] = (a[links] if links is not None else a).astype(np.float64 if c in ("rssi", "sinr") else np.float32)
+    if links is not None:
+        out["sampled_links"] = links.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "_rank%d" % run.env.rank if run.env.world > 1 else ""
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+
+
 def measure(args, env):
     """ONE configuration through the whole bench -- what the driver runs; rank 0 gets the result line's dictionary"""
     args = copy.copy(args)
@@ -1199,8 +1260,10 @@ def measure(args, env):
     heard, dropped = run.last_run[0].batch_result_count(run.last_run[1]) if batch > 1 else eng.result_count()
     if dropped:
         raise SystemExit("heard links were dropped for capacity: the measurement is invalid")
-    alone = alone_pass(run)
-    tile_reuse = eng.batch_tile_reuse() if batch > 1 else 1
+    if args.dump_outputs:
+        dump_outputs(run, args.dump_outputs)
+    alone = alone_pass(run) if args.full else None
+    tile_reuse = eng.batch_tile_reuse() if (args.full and batch > 1) else 1
     if world > 1:   # the contract: MAX over ranks of the timed region
         rdev = env.dev if env.backend == "nccl" else torch.device("cpu")
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=rdev)
@@ -1226,7 +1289,7 @@ def measure(args, env):
                      "scan, %d added their frames to per-receiver lists, %d rebuilt those)"
                      % (value * elapsed / timed_ticks, ot, ob, eng.air_scan_ticks(), inc, reb))
     sequential = None
-    if (run.inflight > 1 or batch > 1) and run.sharded is None and world == 1:
+    if args.full and (run.inflight > 1 or batch > 1) and run.sharded is None and world == 1:
         sequential = sequential_leg(run, links_per_tick, timed_ticks, heard)
 
     result = None
@@ -1236,16 +1299,6 @@ def measure(args, env):
         except Exception:
             cand = 0
         step_s = elapsed / run.steps
-        pairs = interferers = 0
-        if run.stateful and batch > 1:
-            pairs, _, interferers = eng.air_batch_pairs()
-        roofline = roofline_object(kernels=kernels, n_samples=n_samples, n_loc=run.n_loc, t_per_tick=run.t_per_tick, heard=heard, cand=cand,
-                                   ticks_per_launch=batch, step_s=step_s, contexts=run.inflight, workload=args.workload,
-                                   pmc_ok=(world == 1 and not run.as_rank and args.nodes == 0), pairs_per_launch=pairs, alone=alone,
-                                   sinr_column=run.sinr_column, tile_reuse=tile_reuse)
-        if pairs:
-            roofline["surviving_pairs_per_launch"] = pairs
-            roofline["interfering_pairs_per_launch"] = interferers
         result = {
             "metric": baseline_metric(), "value": value, "unit": "links/s", "n_gpus": world, "steps": run.steps, "warmup": run.warmup,
             "ms_per_step": step_s * 1e3, "ms_per_tick": elapsed / timed_ticks * 1e3, "higher_is_better": True,
@@ -1258,8 +1311,19 @@ def measure(args, env):
                                     % (world, "regions of the k-d order" if run.spatial else "node index ranges",
                                        "ncclAllGather inside libradiomedium_hip.so: stage + collective + frame list + sweep in one call"
                                        if run.lib_dist else "torch.distributed around the engine calls")) if world > 1 else "none"},
-            "roofline": roofline,
         }
+    if env.rank == 0 and args.full:
+        pairs = interferers = 0
+        if run.stateful and batch > 1:
+            pairs, _, interferers = eng.air_batch_pairs()
+        roofline = roofline_object(kernels=kernels, n_samples=n_samples, n_loc=run.n_loc, t_per_tick=run.t_per_tick, heard=heard, cand=cand,
+                                   ticks_per_launch=batch, step_s=step_s, contexts=run.inflight, workload=args.workload,
+                                   pmc_ok=(world == 1 and not run.as_rank and args.nodes == 0), pairs_per_launch=pairs, alone=alone,
+                                   sinr_column=run.sinr_column, tile_reuse=tile_reuse)
+        if pairs:
+            roofline["surviving_pairs_per_launch"] = pairs
+            roofline["interfering_pairs_per_launch"] = interferers
+        result["roofline"] = roofline
         if roofline["overlap_check"]["ok"] is False and not roofline["overlap_check"]["under_profiler"]:
             result["roofline_check_failed"] = ("the kernel intervals sampled inside the timed region add up to more than the driver-timed "
                                                "step allows (overlap_check): roofline.achieved / frac come from the launch sequences that ran alone")
@@ -1335,6 +1399,8 @@ def main():
             dist.init_process_group(env.backend, rank=env.rank, world_size=env.world)
 
     if args.dense_only:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: the timed steps of the main run; --dense-only has none")
         d = dense_probe(rsa, W, torch, env.dev, env.device_ordinal)
         lead = d["null_medium"]
         out = {"metric": baseline_metric(), "value": lead["value"], "unit": "links/s", "n_gpus": 1, "steps": 24, "warmup": 3,
@@ -1345,7 +1411,7 @@ def main():
         return
 
     out = measure(args, env)
-    if env.world > 1 and args.scaling == "strong" and not args.no_weak_probe and not args.as_rank and args.nodes == 0:
+    if args.full and env.world > 1 and args.scaling == "strong" and not args.no_weak_probe and not args.as_rank and args.nodes == 0:
         # the same run once more with the node count grown as sqrt(GPUs) (constant link evaluations per GPU and tick):
         # printed as an extra key, the headline stays the BASELINE config
         a2 = copy.copy(args)
@@ -1353,6 +1419,7 @@ def main():
         a2.steps = 8 if args.steps <= 0 else min(args.steps, 8)
         a2.warmup = 2 if args.warmup < 0 else min(args.warmup, 2)
         a2.no_cpu_baseline = True
+        a2.dump_outputs = ""        # the outputs are the headline run's
         try:
             w = measure(a2, env)
             if out is not None and w is not None:

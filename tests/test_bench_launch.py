@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -96,3 +98,70 @@ def test_roofline_bound_is_the_larger_fraction():
                                                                             "step_us_probed": 420.0}, tile_reuse=4)
     assert rl["valu_issue"] is not None and rl["step"]["valu_frac"] > rl["step"]["hbm_frac"] and rl["bound"] == "valu"
     assert rl["traffic"] is not None and rl["traffic_over_required"] > 0
+
+
+# ---- --dump-outputs: what the last timed step computed, sampled within the budget (a stand-in context, no device)
+
+class _View:
+    def __init__(self, b, count):
+        self.count = count
+        self.pkt = np.arange(count, dtype=np.int32) // 5
+        self.dst = (np.arange(count, dtype=np.int32) * 7 + b) % 100_000
+        self.verdict = np.full(count, b % 3, dtype=np.uint8)
+        self.rssi = -90.0 + np.arange(count) / 3.0 + b
+        self.sinr = np.zeros(count)
+
+
+class _Eng:
+    def __init__(self, counts):
+        self.views = [_View(b, c) for b, c in enumerate(counts)]
+
+    def batch_result_view(self, n):
+        assert n == len(self.views)
+        return self.views, [0] * n
+
+
+def _dump(tmp_path, counts, budget=None, monkeypatch=None):
+    import types
+    B = _bench()
+    if budget is not None:
+        monkeypatch.setattr(B, "DUMP_BUDGET", budget)
+    eng = _Eng(counts)
+    run = types.SimpleNamespace(batch=len(counts), last_run=(eng, len(counts) - 1), sharded=None, sinr_column=False,
+                                env=types.SimpleNamespace(world=1, rank=0))
+    B.dump_outputs(run, str(tmp_path))
+    return eng, {f[:-4]: np.load(os.path.join(str(tmp_path), f)) for f in os.listdir(str(tmp_path))}
+
+
+def test_dump_outputs_writes_every_tick_of_the_last_step(tmp_path):
+    eng, out = _dump(tmp_path, [30, 0, 12, 45])
+    assert set(out) == {"heard_per_tick", "sampled_ticks", "pkt", "dst", "verdict", "rssi"}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert out["rssi"].dtype == np.float64 and out["dst"].dtype == np.float32
+    np.testing.assert_array_equal(out["heard_per_tick"], [30, 0, 12, 45])
+    np.testing.assert_array_equal(out["sampled_ticks"], [0, 1, 2, 3])
+    for c in ("pkt", "dst", "verdict", "rssi"):
+        np.testing.assert_array_equal(out[c], np.concatenate([getattr(v, c) for v in eng.views]))
+
+
+def test_dump_outputs_samples_whole_ticks_within_the_budget(tmp_path, monkeypatch):
+    counts = [1000 + 10 * b for b in range(64)]
+    budget = 20 * 1000 * 20
+    eng, out = _dump(tmp_path / "a", counts, budget, monkeypatch)
+    picked = out["sampled_ticks"].astype(int)
+    assert 0 < len(picked) < 64 and np.all(np.diff(picked) > 0)
+    assert sum(a.nbytes for a in out.values()) <= budget
+    np.testing.assert_array_equal(out["heard_per_tick"], counts)
+    np.testing.assert_array_equal(out["dst"], np.concatenate([eng.views[b].dst for b in picked]))
+    _, again = _dump(tmp_path / "b", counts, budget, monkeypatch)      # the same outputs: the same sample
+    for k in out:
+        np.testing.assert_array_equal(out[k], again[k])
+
+
+def test_dump_outputs_samples_the_links_of_a_tick_larger_than_the_budget(tmp_path, monkeypatch):
+    eng, out = _dump(tmp_path, [50_000, 60_000], 100_000, monkeypatch)
+    (b,) = out["sampled_ticks"].astype(int)
+    keep = out["sampled_links"].astype(int)
+    assert 0 < len(keep) < eng.views[b].count and np.all(np.diff(keep) > 0)
+    assert sum(a.nbytes for a in out.values()) <= 100_000
+    np.testing.assert_array_equal(out["rssi"], eng.views[b].rssi[keep])

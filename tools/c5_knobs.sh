@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 for kv in "$@"; do
   echo "== $kv"
   O=$R/gpurun_out/prof_knob; rm -rf $O; mkdir -p $O
-  env $kv rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python $R/bench.py --workload c5 --steps 40 --warmup 12 --no-host-transfer --no-cpu-baseline > $O/run.log 2>&1
+  env $kv rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python $R/bench.py --full --workload c5 --steps 40 --warmup 12 --no-host-transfer --no-cpu-baseline > $O/run.log 2>&1
   python - $O <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/**/*kernel_stats.csv", recursive=True)[0]

@@ -13,7 +13,7 @@ mkdir -p $O
 stamp() { for f in "$@"; do echo "# commit ${RM_COMMIT:-unrecorded}" >> $f; done; }
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 cd /tmp && export TMPDIR=/tmp
-LEAN="--no-cpu-baseline --no-scale-probe --no-host-transfer"
+LEAN="--full --no-cpu-baseline --no-scale-probe --no-host-transfer"
 
 # kernel stats of one bench command: stats <name> <bench args...>   -> ${ROUND}_<name>_kernel_stats.csv + ${ROUND}_<name>_bench.json
 stats() {
@@ -38,7 +38,7 @@ pmc() {
 }
 
 if has bench; then
-python3 $R/bench.py > $O/bench.json 2> $O/bench.err
+python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err
 cp $O/bench.json $O/${ROUND}_c3_bench_full.json
 echo "bench done"
 # the kernels' own intervals of the SAME command as the line's roofline (three contexts, 128 ticks per launch): what

@@ -3,7 +3,7 @@
 R=$PWD
 O=$R/gpurun_out/prof_evgaps; rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $O -- python $R/bench.py --no-cpu-baseline --no-scale-probe --steps 4 --warmup 1 > $O/run.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $O -- python $R/bench.py --full --no-cpu-baseline --no-scale-probe --steps 4 --warmup 1 > $O/run.log 2>&1
 python - $O <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]
