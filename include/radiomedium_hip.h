@@ -501,7 +501,8 @@ int rm_dist_tick_run_sources_device(rm_context *ctx, int64_t t_begin_us, int64_t
 
 /* ---- reception stage: what the reference does with the verdicts, on the device -------------------------
  * SURVEY.md section 8f-1 / 8f-3.  After rm_events_enable every evaluated tick (rm_transmit, rm_tick_flush*,
- * rm_tick_run*, not rm_batch_*) also hands its packets and heard links to the event stage, exactly as the
+ * rm_tick_run*; the ticks of a batch through rm_events_process_batch, below) also hands its packets and heard links to the
+ * event stage, exactly as the
  * reference's media call Simulator.generateTransmissionEvents / generateReceptionEvents (Simulator.java:321-350)
  * per packet and heard link: event times max(start, rm_set_time value) and + air time.  The constant-loss
  * medium queues nothing and delivers synchronously (UDGMConstantLossRadioMedium.java:30): its links come
@@ -540,6 +541,20 @@ int rm_events_enable(rm_context *ctx, uint32_t max_pending_packets, uint32_t max
 int rm_events_disable(rm_context *ctx);
 int64_t rm_events_next_packet(rm_context *ctx);
 int rm_events_process(rm_context *ctx, int64_t time_us, rm_delivery_view *out);
+/* The ticks of the last rm_batch_run_device / rm_batch_run_sources_device call handed to the reception stage, slot b as tick b:
+ * identical, bit for bit, to a lone tick's hand-over of slot b (its transmissions at the current time, as rm_set_time or the
+ * drain before left it) followed by rm_events_process(time_us[b], &out[b]), for b = 0 .. n_ticks-1.  Afterwards the current
+ * time is time_us[n_ticks-1], rm_events_next_packet has moved on by every record of the batch (padding included) and
+ * rm_node_info / rm_node_info_changed report the state after the last drain.  All drains are issued at once (no host round
+ * trip between ticks); the views point into one host-mapped block, valid until the next rm_events_process* call.
+ * RM_ERR_STATE, with nothing changed: events were not on when the batch ran, no batch, the batch was handed over already,
+ * or anything that rewrites the slots, the node table or the medium came in between (a lone tick, rm_transmit, another
+ * batch, rm_nodes_upload / rm_node_update / rm_nodes_move / rm_set_partition*, rm_set_model / rm_set_n2n_matrix,
+ * rm_events_process, rm_events_enable); draws pending; the gathered and rm_dist_* batches and spatially partitioned
+ * contexts, which drain one tick at a time.  RM_ERR_INVALID: n_ticks is not the batch's tick count.  RM_ERR_CAPACITY as
+ * rm_events_process reports it (a slot that overflowed the link capacity, the pending rings), for the first drain that
+ * lost something; every view is filled all the same. */
+int rm_events_process_batch(rm_context *ctx, int32_t n_ticks, const int64_t *time_us, rm_delivery_view *out);
 int rm_node_info(rm_context *ctx, const int32_t *nodes, int32_t n, double *rssi, int32_t *receiving, int32_t *channel);
 /* The same, incrementally (ABI version 4): only the nodes whose (rssi, receiving state, channel) differ from what THIS call
  * reported for them last -- the first call after rm_events_enable or a new node table reports every node.  A time-step

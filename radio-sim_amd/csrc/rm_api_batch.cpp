@@ -186,6 +186,7 @@ int rmh::launch_batch(rm_context *c, TickSlot *const *slots, const TickPlan *pla
     for (int b = 0; b < n; ++b) {
         slots[b]->have_result = true;
         slots[b]->compact_pending = false;
+        slots[b]->last_cfg = plans[b].cfg; // (the reception stage asks whether the slot's verdicts were drawn: rm_events_process_batch)
     }
     return RM_OK;
 }
@@ -364,21 +365,27 @@ int rm_batch_run_sources_device(rm_context *c, int32_t n_ticks, const int64_t *t
                                 const int64_t *air_us)
 {
     if (!dev_src) return fail(RM_ERR_INVALID, "bad arguments");
-    return batch_run(c, n_ticks, t_begin_us, t_end_us, dev_src, nullptr, n_src, start_us, air_us);
+    const int rc = batch_run(c, n_ticks, t_begin_us, t_end_us, dev_src, nullptr, n_src, start_us, air_us);
+    ev_batch_ran(c, rc, n_ticks, true);
+    return rc;
 }
 
 int rm_batch_run_device(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us, const int64_t *t_end_us,
                         const rm_tx_record *const *dev_new, const int32_t *n_new)
 {
     if (!dev_new) return fail(RM_ERR_INVALID, "bad arguments");
-    return batch_run(c, n_ticks, t_begin_us, t_end_us, nullptr, dev_new, n_new, nullptr, nullptr);
+    const int rc = batch_run(c, n_ticks, t_begin_us, t_end_us, nullptr, dev_new, n_new, nullptr, nullptr);
+    ev_batch_ran(c, rc, n_ticks, true);
+    return rc;
 }
 
 int rm_batch_run_gathered_device(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us, const int64_t *t_end_us,
                                  const rm_tx_record *dev_gathered, int32_t world, int32_t slots)
 {
     if (!dev_gathered) return fail(RM_ERR_INVALID, "bad arguments");
-    return batch_run(c, n_ticks, t_begin_us, t_end_us, nullptr, nullptr, nullptr, nullptr, nullptr, dev_gathered, world, slots);
+    const int rc = batch_run(c, n_ticks, t_begin_us, t_end_us, nullptr, nullptr, nullptr, nullptr, nullptr, dev_gathered, world, slots);
+    ev_batch_ran(c, rc, n_ticks, false);
+    return rc;
 }
 
 int rm_batch_tile_reuse(const rm_context *c) { return c ? c->last_tile_reuse : fail(RM_ERR_INVALID, "ctx is NULL"); }

@@ -199,7 +199,9 @@ int rm_batch_run_gathered_sources_device(rm_context *c, int32_t n_ticks, const i
     // the frames' time spans travel with the call -- the SINR medium's ticks may outlive each other)
     static thread_local std::vector<int64_t> air_v;
     air_v.assign(size_t(n_ticks), air_us);
-    return batch_run(c, n_ticks, t_begin_us, t_end_us, nullptr, nullptr, nullptr, start_us, air_v.data(), nullptr, world, slots, dev_src_all);
+    const int rc = batch_run(c, n_ticks, t_begin_us, t_end_us, nullptr, nullptr, nullptr, start_us, air_v.data(), nullptr, world, slots, dev_src_all);
+    ev_batch_ran(c, rc, n_ticks, false); // (rm_events_process_batch takes the gathered forms one tick at a time only)
+    return rc;
 }
 
 // The same with every rank's block as the library's own all-gather leaves it: n_ticks * slots source indices, then
@@ -216,8 +218,10 @@ int rm_batch_run_gathered_blocks_device(rm_context *c, int32_t n_ticks, const in
     static thread_local std::vector<int64_t> air_v;
     air_v.assign(size_t(n_ticks), air_us);
     const int mine = n_ticks * slots;
-    return batch_run(c, n_ticks, t_begin_us, t_end_us, nullptr, nullptr, nullptr, start_us, air_v.data(), nullptr, world, slots, dev_blocks,
-                     mine + rm::kGatherTrailer, mine);
+    const int rc = batch_run(c, n_ticks, t_begin_us, t_end_us, nullptr, nullptr, nullptr, start_us, air_v.data(), nullptr, world, slots,
+                             dev_blocks, mine + rm::kGatherTrailer, mine);
+    ev_batch_ran(c, rc, n_ticks, false);
+    return rc;
 }
 
 int rm_dist_batch_run_sources_device(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us, const int64_t *t_end_us,

@@ -383,6 +383,7 @@ int rm_set_model(rm_context *c, const rm_model_params *p)
     if (!c || !p) return fail(RM_ERR_INVALID, "NULL argument");
     RM_TRY(validate_model(p));
     RM_TRY(ev_flush_append(c)); // (the tick before was evaluated by the old medium: its append does not wait for the next drain)
+    ev_touch(c);
     const bool was_geo = is_geometric(c);
     c->params = *p;
     if (was_geo != is_geometric(c)) c->rx_dirty = true;
@@ -407,6 +408,7 @@ int rm_set_n2n_matrix(rm_context *c, int32_t m, const double *row_major)
 {
     if (!c || m < 0 || (m > 0 && !row_major)) return fail(RM_ERR_INVALID, "bad matrix");
     RM_HIP(hipSetDevice(c->device));
+    ev_touch(c);
     c->n2n_m = m;
     if (m == 0) {
         c->d_n2n.release();

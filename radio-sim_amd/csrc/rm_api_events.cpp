@@ -73,17 +73,11 @@ int ev_flush_append(rm_context *c)
     return RM_OK;
 }
 
-int ev_append(rm_context *c, TickSlot &ts, bool may_wait)
+// where an evaluated slot's heard links are, packet by packet, for the reception stage (records: materialize first)
+static rm::EvLinkSrc ev_link_src(rm_context *c, const TickSlot &ts, const uint32_t *&dropped)
 {
-    if (!c->ev.on || !ts.have_result || ts.last_n_new <= 0) {
-        return RM_OK;
-    }
-    RM_TRY(ev_flush_append(c));
-    RM_TRY(ev_ensure_nodes(c));
-    if (ts.dense_pending) RM_TRY(materialize(c, ts)); // (the reception stage reads records)
     const rm::TickDev &t = ts.last;
     rm::EvLinkSrc ls{};
-    const uint32_t *dropped = nullptr;
     if (ts.compact_pending) {
         ls.dst = t.a_dst;
         ls.rssi = t.a_rssi;
@@ -102,6 +96,20 @@ int ev_append(rm_context *c, TickSlot &ts, bool may_wait)
         dropped = t.out_count + 1;
     }
     ls.per_frame_verdict = (!ts.last_cfg.stochastic && !is_sinr(c)) ? 1 : 0;
+    return ls;
+}
+
+int ev_append(rm_context *c, TickSlot &ts, bool may_wait)
+{
+    if (!c->ev.on || !ts.have_result || ts.last_n_new <= 0) {
+        return RM_OK;
+    }
+    RM_TRY(ev_flush_append(c));
+    RM_TRY(ev_ensure_nodes(c));
+    if (ts.dense_pending) RM_TRY(materialize(c, ts)); // (the reception stage reads records)
+    const rm::TickDev &t = ts.last;
+    const uint32_t *dropped = nullptr;
+    const rm::EvLinkSrc ls = ev_link_src(c, ts, dropped);
     const int immediate = (c->params.kind == RM_MODEL_UDGM_CONST) ? 1 : 0;
     static const bool never_wait = [] { const char *e = std::getenv("RM_EV_FUSE"); return e && std::atoi(e) == 0; }();
     if (may_wait && !never_wait) { // (the closed loop: rm_events_process comes next, and takes the append into its first launch)
@@ -120,6 +128,14 @@ int ev_append(rm_context *c, TickSlot &ts, bool may_wait)
     c->ev.par ^= 1; // the launch wrote the other set of tails
     c->ev.next_packet += ts.last_n_new;
     return RM_OK;
+}
+
+void ev_batch_ran(rm_context *c, int rc, int n_ticks, bool eligible)
+{
+    rm_context::Events &v = c->ev;
+    v.batch_n = (rc == RM_OK && v.on) ? n_ticks : 0;
+    v.batch_ok = eligible;
+    v.batch_gen = v.gen;
 }
 
 } // namespace rmh
@@ -166,6 +182,15 @@ int rm_events_disable(rm_context *c)
         (void)hipStreamSynchronize(c->stream);
     }
     v.pending.on = false;
+    ev_touch(c);
+    v.batch_n = 0;
+    if (v.h_batch) (void)hipHostFree(v.h_batch);
+    if (v.h_bslots) (void)hipHostFree(v.h_bslots);
+    if (v.h_bsize) (void)hipHostFree(v.h_bsize);
+    v.h_batch = nullptr;
+    v.h_batch_bytes = 0;
+    v.h_bslots = nullptr;
+    v.h_bsize = nullptr;
     v.d_st.release(); v.d_pk.release(); v.d_ldst.release(); v.d_lrssi.release(); v.d_lverdict.release();
     v.d_gtime.release(); v.d_gmeta.release(); v.d_gref.release(); v.d_grank.release(); v.d_cnt.release(); v.d_off.release(); v.d_grun.release(); v.d_run_rec.release();
     v.d_recv_key.release(); v.d_send_key.release(); v.d_receiving.release(); v.d_sending.release(); v.d_latched.release();
@@ -234,6 +259,7 @@ int rm_events_process(rm_context *c, int64_t time_us, rm_delivery_view *out)
     if (c->draws_pending) return fail(RM_ERR_STATE, "the last tick waits for rm_tick_finish_draws");
     RM_HIP(hipSetDevice(c->device));
     RM_TRY(ev_ensure_nodes(c));
+    ev_touch(c); // (a batch evaluated before this drain can no longer be handed over: its tick 0 would come after it)
     const rm::EvOut o = ev_out(c);
     const uint32_t seq = ++c->ev.seq;
     // (the ring window the drain looks at: at most the packets numbered since the oldest pending one of the last drain)
@@ -276,6 +302,161 @@ int rm_events_process(rm_context *c, int64_t time_us, rm_delivery_view *out)
     if (o.hdr->err) return fail(RM_ERR_CAPACITY, "the reception stage ran out of room for pending packets / links (rm_events_enable)");
     if (o.hdr->total > o.hdr->count) return fail(RM_ERR_CAPACITY, "more deliveries than the delivery block holds");
     return RM_OK;
+}
+
+// The ticks of the last batch, drained one by one as if each had been a lone tick followed by rm_events_process(time_us[b]):
+// per tick one append + selection launch, the rank pass and the state update (rm_events.hip), all issued back to back -- the
+// drains place their deliveries and runs behind each other on the device (EvState::out_base / run_base) and the host waits
+// once, for the last tick's header.  Before the drains: one small readback that bounds the batch's deliveries and runs
+// (k_ev_batch_size), to size the host-mapped block.
+int rm_events_process_batch(rm_context *c, int32_t n_ticks, const int64_t *time_us, rm_delivery_view *out)
+{
+    if (!c || !time_us || !out || n_ticks < 1 || n_ticks > RM_MAX_BATCH) return fail(RM_ERR_INVALID, "bad arguments");
+    rm_context::Events &v = c->ev;
+    if (!v.on) return fail(RM_ERR_STATE, "rm_events_enable first");
+    if (v.batch_n == 0)
+        return fail(RM_ERR_STATE, "no batch to hand over: rm_events_enable, then rm_batch_run_device / rm_batch_run_sources_device (each "
+                                  "batch is handed over once)");
+    if (v.batch_gen != v.gen)
+        return fail(RM_ERR_STATE, "the batch's slots are gone: a tick, a transmission, another batch, a node-table or medium change or a "
+                                  "drain came in between");
+    if (!v.batch_ok || part_spatial(c))
+        return fail(RM_ERR_STATE, "gathered and rm_dist_* batches and spatially partitioned contexts are drained one tick at a time");
+    if (n_ticks != v.batch_n) return fail(RM_ERR_INVALID, "n_ticks is not the batch's tick count");
+    if (c->draws_pending) return fail(RM_ERR_STATE, "the last tick waits for rm_tick_finish_draws");
+    for (int b = 0; b < n_ticks; ++b) {
+        const TickSlot *ts = slot_of(c, b);
+        if (!ts || !ts->have_result) return fail(RM_ERR_STATE, "no evaluated tick in a slot of the batch");
+        if (ts->draws_pending) return fail(RM_ERR_STATE, "a slot's verdicts wait for rm_tick_finish_draws");
+    }
+    RM_HIP(hipSetDevice(c->device));
+    RM_TRY(ev_flush_append(c));
+    RM_TRY(ev_ensure_nodes(c));
+    if (!v.h_bslots) {
+        RM_HIP(hipHostMalloc(reinterpret_cast<void **>(&v.h_bslots), sizeof(rm::EvBatchSlot) * RM_MAX_BATCH, hipHostMallocMapped));
+        RM_HIP(hipHostMalloc(reinterpret_cast<void **>(&v.h_bsize), sizeof(uint32_t) * (RM_MAX_BATCH + 2), hipHostMallocMapped));
+    }
+    // the slots' link sources (dense slots get their records first, as ev_append does)
+    static thread_local std::vector<const uint32_t *> dropped_v;
+    dropped_v.assign(size_t(n_ticks), nullptr);
+    uint64_t new_packets = 0;
+    for (int b = 0; b < n_ticks; ++b) {
+        TickSlot &ts = *slot_of(c, b);
+        if (ts.dense_pending) RM_TRY(materialize(c, ts));
+        rm::EvBatchSlot &bs = v.h_bslots[b];
+        bs = rm::EvBatchSlot{};
+        bs.n_new = std::max(ts.last_n_new, 0);
+        if (bs.n_new > 0) {
+            if (c->n_rx <= 0 && !ts.compact_pending && ts.last.slot_off) // (a tick without receivers here: its packets exist all the same)
+                RM_HIP(hipMemsetAsync(ts.last.slot_off, 0, (size_t(std::max(ts.last.n_cnt, 0)) + 2) * sizeof(uint32_t), c->stream));
+            bs.ls = ev_link_src(c, ts, dropped_v[size_t(b)]);
+            if (bs.ls.n_scan > rm::kFusedScanMax) return fail(RM_ERR_STATE, "a tick of more frames than one drain's append takes");
+        }
+        new_packets += uint64_t(bs.n_new);
+    }
+    const rm::EvDev e0 = ev_dev(c);
+    RM_HIP(rm::launch_ev_batch_size(c->stream, e0, v.h_bslots, n_ticks, v.h_bsize));
+    RM_HIP(hipStreamSynchronize(c->stream));
+    uint64_t links = v.h_bsize[0], packets = uint64_t(v.h_bsize[1]) + new_packets;
+    for (int b = 0; b < n_ticks; ++b) links += v.h_bsize[2 + b];
+    // every pending or appended link is delivered at most once, every packet delivers in at most one run
+    const uint64_t cap64 = std::max<uint64_t>(links, 64), run_cap64 = std::max<uint64_t>(packets, 64);
+    if (cap64 > 0xFFFFFFFFull || run_cap64 > 0xFFFFFFFFull) return fail(RM_ERR_CAPACITY, "a batch of more deliveries than 2^32");
+    const uint32_t cap = uint32_t(cap64), run_cap = uint32_t(run_cap64);
+    const size_t hdr_bytes = pad64(sizeof(rm::EvHeader) * size_t(n_ticks));
+    const size_t need = hdr_bytes + pad64(size_t(run_cap) * 8) + 2 * pad64(size_t(run_cap) * 4) + pad64(size_t(cap) * 4) + pad64(size_t(cap) * 8);
+    if (v.h_batch_bytes < need) { // (nothing of the stream uses the block: the wait above)
+        if (v.h_batch) RM_HIP(hipHostFree(v.h_batch));
+        v.h_batch = nullptr;
+        v.h_batch_bytes = 0;
+        const size_t want = std::max(need + need / 2, size_t(1) << 20);
+        RM_HIP(hipHostMalloc(reinterpret_cast<void **>(&v.h_batch), want, hipHostMallocMapped));
+        v.h_batch_bytes = want;
+    }
+    rm::EvOut o{};
+    {
+        char *p = v.h_batch;
+        size_t off = hdr_bytes;
+        o.hdr = reinterpret_cast<rm::EvHeader *>(p);
+        o.run_packet = reinterpret_cast<int64_t *>(p + off); off += pad64(size_t(run_cap) * 8);
+        o.run_first = reinterpret_cast<uint32_t *>(p + off); off += pad64(size_t(run_cap) * 4);
+        o.run_count = reinterpret_cast<uint32_t *>(p + off); off += pad64(size_t(run_cap) * 4);
+        o.dst = reinterpret_cast<int32_t *>(p + off); off += pad64(size_t(cap) * 4);
+        o.rssi = reinterpret_cast<double *>(p + off);
+        o.cap = cap;
+        o.run_cap = run_cap;
+        std::memset(p, 0, hdr_bytes);
+    }
+    // the drains, back to back
+    v.batch_n = 0; // (handed over from here on)
+    const int immediate = (c->params.kind == RM_MODEL_UDGM_CONST) ? 1 : 0;
+    const uint32_t seq0 = v.seq;
+    const int64_t oldest = v.oldest_packet; // (the oldest packet the host saw: a bound on every drain's window, which only moves up)
+    for (int b = 0; b < n_ticks; ++b) {
+        TickSlot &ts = *slot_of(c, b);
+        const rm::EvBatchSlot &bs = v.h_bslots[b];
+        rm::EvOut ob = o;
+        ob.hdr = o.hdr + b;
+        const uint32_t seq = ++v.seq;
+        const int64_t now = c->current_time; // Simulator.java:323-326, with currentTime as the drain before left it
+        if (bs.n_new > 0) v.next_packet += bs.n_new;
+        const uint32_t window = uint32_t(std::min<int64_t>(std::max<int64_t>(v.next_packet - oldest, 1), 0x7FFFFFFF));
+        if (bs.n_new > 0) {
+            RM_HIP(rm::launch_ev_drain(c->stream, ev_dev(c), ob, time_us[b], seq, window, &bs.ls, ts.last.tx + ts.last.first_new, bs.n_new, now,
+                                       immediate, dropped_v[size_t(b)], true));
+            v.par ^= 1; // (the first launch appended: it wrote the other set of tails)
+        } else {
+            RM_HIP(rm::launch_ev_drain(c->stream, ev_dev(c), ob, time_us[b], seq, window, nullptr, nullptr, 0, 0, 0, nullptr, true));
+        }
+        c->current_time = time_us[b]; // Simulator.java:156
+    }
+    ev_touch(c);
+    // one wait, for the last drain's header; the others came before it (each header's four quarters are checked all the same)
+    auto arrived = [&](int b) {
+        const rm::EvHeader *h = o.hdr + b;
+        const uint32_t want = seq0 + uint32_t(b) + 1u;
+        return __atomic_load_n(&h->seq, __ATOMIC_ACQUIRE) == want && __atomic_load_n(&h->seq1, __ATOMIC_ACQUIRE) == want &&
+               __atomic_load_n(&h->seq2, __ATOMIC_ACQUIRE) == want && __atomic_load_n(&h->seq3, __ATOMIC_ACQUIRE) == want;
+    };
+    bool seen = false;
+    for (int spin = 0; spin < 400000 && !seen; ++spin) seen = arrived(n_ticks - 1);
+    if (!seen) RM_HIP(hipStreamSynchronize(c->stream));
+    bool all = true;
+    for (int b = 0; b < n_ticks && all; ++b) all = arrived(b);
+    if (!all) {
+        RM_HIP(hipStreamSynchronize(c->stream));
+        for (int b = 0; b < n_ticks; ++b)
+            if (!arrived(b)) return fail(RM_ERR_HIP, "a drain of the batch finished without its header");
+    }
+    int first_error = RM_OK;
+    uint32_t dbase = 0, rbase = 0;
+    for (int b = 0; b < n_ticks; ++b) {
+        const rm::EvHeader &h = o.hdr[b];
+        rm_delivery_view &r = out[b];
+        r.count = h.count;
+        r.pending_packets = h.pending_packets;
+        r.oldest_packet = h.oldest_packet;
+        r.packet = nullptr;
+        r.dst = o.dst + dbase;
+        r.rssi = o.rssi + dbase;
+        r.n_runs = h.runs;
+        r.run_packet = o.run_packet + rbase;
+        r.run_first = o.run_first + rbase;
+        r.run_count = o.run_count + rbase;
+        dbase += h.count; // (as the drain's finishing workgroup moved the device's bases on)
+        rbase += h.runs;
+        // (the first drain that lost something is the one reported; the views of all drains are filled all the same)
+        if (h.err & 8u) c->air.valid = false;
+        if (first_error != RM_OK) continue;
+        if (h.err & 8u)
+            first_error = fail(RM_ERR_CAPACITY, "a tick's heard links exceeded the link capacity (rm_set_link_capacity): its events are missing");
+        else if (h.err)
+            first_error = fail(RM_ERR_CAPACITY, "the reception stage ran out of room for pending packets / links (rm_events_enable)");
+        else if (h.total > h.count)
+            first_error = fail(RM_ERR_CAPACITY, "more deliveries than the delivery block holds");
+    }
+    v.oldest_packet = o.hdr[n_ticks - 1].oldest_packet;
+    return first_error;
 }
 
 int rm_node_info(rm_context *c, const int32_t *nodes, int32_t n, double *rssi, int32_t *receiving, int32_t *channel)

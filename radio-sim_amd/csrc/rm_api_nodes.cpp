@@ -391,6 +391,7 @@ int rm_nodes_upload(rm_context *c, int32_t n, const double *x, const double *y, 
     }
     RM_HIP(hipSetDevice(c->device));
     RM_TRY(ev_flush_append(c)); // (an append left for the next drain reads the tick's records and the radio-state arrays as they are now)
+    ev_touch(c);
     c->n = n;
     c->x.assign(x, x + n);
     c->y.assign(y, y + n);
@@ -462,6 +463,7 @@ int rm_node_update(rm_context *c, int32_t i, double x, double y, double z, doubl
     if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(z)) return fail(RM_ERR_INVALID, "position must be finite");
     RM_HIP(hipSetDevice(c->device));
     RM_TRY(ev_flush_append(c));
+    ev_touch(c);
     note_probabilities(c, c->rxprob[i], c->txprob[i], rxprob, txprob);
     c->table_xor ^= node_hash(c, i);
     c->x[i] = x; c->y[i] = y; c->z[i] = z; c->txpower[i] = txpower; c->channel[i] = channel;
@@ -481,6 +483,7 @@ int rm_nodes_move(rm_context *c, int32_t count, const int32_t *nodes, const doub
     }
     RM_HIP(hipSetDevice(c->device));
     RM_TRY(ev_flush_append(c));
+    ev_touch(c);
     for (int k = 0; k < count; ++k) {
         const int i = nodes[k];
         c->table_xor ^= node_hash(c, i);
@@ -508,6 +511,7 @@ int rm_set_partition(rm_context *c, int32_t first, int32_t count)
 {
     if (!c || first < 0 || count < 0 || first + count > c->n) return fail(RM_ERR_INVALID, "partition out of range");
     RM_TRY(ev_flush_append(c)); // (whose Transcievers live here is part of what an append writes)
+    ev_touch(c);
     if (c->air_culled && c->air_tail > c->air_head)
         return fail(RM_ERR_STATE, "frames on the air were kept for the present partition's region only: change the partition once they have left the air");
     c->rx_first = first;
@@ -523,6 +527,7 @@ int rm_set_partition_spatial(rm_context *c, int32_t part, int32_t n_parts)
     if (!c || n_parts < 1 || part < 0 || part >= n_parts) return fail(RM_ERR_INVALID, "partition out of range");
     RM_HIP(hipSetDevice(c->device));
     RM_TRY(ev_flush_append(c));
+    ev_touch(c);
     if (c->air_culled && c->air_tail > c->air_head && !(c->sp_parts == ((n_parts > 1) ? n_parts : 0) && c->sp_part == ((n_parts > 1) ? part : 0)))
         return fail(RM_ERR_STATE, "frames on the air were kept for the present partition's region only: change the partition once they have left the air");
     c->rx_first = 0;

@@ -109,6 +109,7 @@ int prepare_tick(rm_context *c, TickSlot &ts, TickPlan &plan, bool want_wg, cons
     const rm::PlanKnobs knobs = knobs_in ? *knobs_in : rm::read_plan_knobs();
     const int n_new = n_active - first_new;
     RM_TRY(ev_flush_append(c)); // (the tick before, if its append was left for a drain that did not come: its records are about to go)
+    ev_touch(c);
     ts.have_result = false;
     ts.compact_pending = false;
     ts.dense_pending = ts.dense_result = ts.dense_layout_pending = false;

@@ -374,6 +374,7 @@ int rm_transmit(rm_context *c, int32_t src, int64_t start_us, int64_t hex_length
     if (!c) return fail(RM_ERR_INVALID, "ctx is NULL");
     if (src < 0 || src >= c->n) return fail(RM_ERR_INVALID, "could not find source node");
     if (hex_length < 0) return fail(RM_ERR_INVALID, "negative packet length");
+    ev_touch(c);
     const bool draws_need_exchange = maybe_draws(c) && part_count(c) != c->n;
     if (is_sinr(c) || draws_need_exchange) {
         // the on-air list of earlier calls / the per-rank draw exchange: the general tick path

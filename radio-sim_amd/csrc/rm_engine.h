@@ -468,6 +468,7 @@ struct EvState {
     uint32_t done_apply;        // ... of k_ev_apply (the last one finishes the drain)
     uint32_t n_dgroups;         // fired end groups that deliver something: the runs of the drain's delivery list
     EvTails tails[2];
+    uint32_t out_base, run_base; // a batch of drains (rm_events_process_batch): where the running drain's deliveries / runs begin
     // (its own 128-byte line: k_ev_select's workgroups add to n_groups and take minima here at the same time)
     alignas(128) uint32_t first_live; // window index of the oldest packet with events still queued (0xFFFFFFFF: none)
     // k_ev_apply's "last workgroup" count in two levels: 512 workgroups that finish together on ONE word were six microseconds of
@@ -509,6 +510,13 @@ struct EvLinkSrc {
     const uint32_t *cnt;   // [n_new] or nullptr
     int n_scan;            // segments: entries of cnt to scan for the pool positions (n_cnt), 0 = off is the scan
     int per_frame_verdict; // every link of a frame carries the same verdict (no draws, no SINR: the frame's transmission failed or not)
+};
+
+// a slot of a batch handed to the reception stage (rm_events_process_batch): what k_ev_batch_size reads of it
+struct EvBatchSlot {
+    EvLinkSrc ls;
+    int n_new;
+    int pad;
 };
 
 // the delivery list of one drain in host-mapped memory
@@ -689,7 +697,8 @@ hipError_t launch_ev_append(hipStream_t s, const EvDev &e, const EvLinkSrc &ls, 
 // that append reads)
 hipError_t launch_ev_drain(hipStream_t s, const EvDev &e, const EvOut &out, int64_t time_us, uint32_t seq, uint32_t window,
                            const EvLinkSrc *fresh_ls = nullptr, const rm_tx_record *fresh_tx = nullptr, int fresh_n = 0, int64_t fresh_now = 0,
-                           int fresh_immediate = 0, const uint32_t *fresh_dropped = nullptr);
+                           int fresh_immediate = 0, const uint32_t *fresh_dropped = nullptr, bool batch = false);
+hipError_t launch_ev_batch_size(hipStream_t s, const EvDev &e, const EvBatchSlot *slots, int n, uint32_t *out);
 hipError_t launch_node_info(hipStream_t s, const EvDev &e, const NodesDev &nd, const int32_t *dev_nodes, int n, double base_rssi,
                             const NodeInfoOut &out, uint32_t seq);
 hipError_t launch_node_info_changed(hipStream_t s, const EvDev &e, const NodesDev &nd, int n, double base_rssi, double *rep_rssi,

@@ -351,11 +351,31 @@ RM_D void ev_write_deliveries(const EvDev &e, const EvOut &out, const int64_t gs
     }
 }
 
+// A drain of a batch (rm_events_process_batch): its deliveries and runs go behind the drains before it in the batch's block.
+// The running bases live on the device (EvState::out_base / run_base: zeroed by k_ev_batch_size, moved on by the workgroup
+// that finishes each drain), so the host issues all drains of the batch without waiting for any of them.  `out` spans the
+// whole block; what is left of it is this drain's (runs: at most g_cap, what run_rec holds).
+RM_D EvOut ev_batch_out(const EvDev &e, EvOut out)
+{
+    const uint32_t db = __hip_atomic_load(&e.st->out_base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t rb = __hip_atomic_load(&e.st->run_base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    out.dst += db;
+    out.rssi += db;
+    out.cap = out.cap > db ? out.cap - db : 0u;
+    out.run_packet += rb;
+    out.run_first += rb;
+    out.run_count += rb;
+    out.run_cap = min(out.run_cap > rb ? out.run_cap - rb : 0u, e.g_cap);
+    return out;
+}
+
 // k_ev_emit: one wave per fired group: its place in the pop order, and every event's (rank, event) key to the fields of
 // the node it touches (the last-writer contest).  The deliveries themselves are written by k_ev_apply: they depend on
 // nothing the contest decides, and their stores into host-mapped memory (PCIe-bound) then run under the state update.
-__global__ void __launch_bounds__(256) k_ev_emit(const EvDev e, const EvOut out, const int share, const int lds_keys)
+template <bool BATCH>
+__global__ void __launch_bounds__(256) k_ev_emit(const EvDev e, EvOut out, const int share, const int lds_keys)
 {
+    if (BATCH) out = ev_batch_out(e, out);
     const uint32_t G = min(e.st->n_groups, e.g_cap);
     const int lane = threadIdx.x & 63;
     // the groups' keys, once per workgroup: every wave's pass below reads all of them, and four waves fetching the same 40 KB
@@ -490,12 +510,15 @@ __global__ void __launch_bounds__(256) k_ev_emit(const EvDev e, const EvOut out,
     }
 }
 
+template <bool BATCH>
 RM_D void ev_finish_body(const EvDev &e, const EvOut &out, int64_t T, uint32_t seq);
 
 // k_ev_apply: the last writer of a field writes it (and clears its key); the workgroup that is done last finishes the drain.
-__global__ void __launch_bounds__(256) k_ev_apply(const EvDev e, const EvOut out, int64_t T, uint32_t seq, const int share)
+template <bool BATCH>
+__global__ void __launch_bounds__(256) k_ev_apply(const EvDev e, EvOut out, int64_t T, uint32_t seq, const int share)
 {
     __shared__ uint32_t s_lastwg;
+    if (BATCH) out = ev_batch_out(e, out);
     const uint32_t G = min(e.st->n_groups, e.g_cap);
     const int lane = threadIdx.x & 63;
     for (uint32_t g = blockIdx.x * 4 + wave_index(); g < G; g += gridDim.x * 4) { // wave-uniform
@@ -588,12 +611,13 @@ __global__ void __launch_bounds__(256) k_ev_apply(const EvDev e, const EvOut out
         __syncthreads();
         if (!s_lastwg) return;
         if (threadIdx.x == 0) e.st->done_apply = 0u;
-        ev_finish_body(e, out, T, seq);
+        ev_finish_body<BATCH>(e, out, T, seq);
     }
 }
 
 // k_ev_finish (one workgroup, after k_ev_apply): the fired groups' packets are marked, the ring heads move, the
 // queue's ladder rule for this drain (rm_evorder.hpp) is applied and the delivery list's header is published.
+template <bool BATCH>
 RM_D void ev_finish_body(const EvDev &e, const EvOut &out, int64_t T, uint32_t seq)
 {
     EvState &st = *e.st;
@@ -624,6 +648,7 @@ RM_D void ev_finish_body(const EvDev &e, const EvOut &out, int64_t T, uint32_t s
         total = st.n_deliv;
         runs = __hip_atomic_load(&st.n_dgroups, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (st.n_groups > e.g_cap) st.err |= 4u;
+        if (BATCH && runs > out.run_cap) st.err |= 4u; // (the batch's run region was sized by the host: never, but not silently)
         err = st.err | tl.err;
         // the ring head's own number: a tick that did not fit the rings was numbered but left nothing here, so
         // "next - pending" would skip packets that are still queued
@@ -643,6 +668,10 @@ RM_D void ev_finish_body(const EvDev &e, const EvOut &out, int64_t T, uint32_t s
         __syncthreads();
     }
     if (threadIdx.x != 0) return;
+    if (BATCH) { // the next drain of the batch places its deliveries and runs behind this one's (ev_batch_out)
+        st.out_base += min(total, out.cap);
+        st.run_base += min(runs, out.run_cap);
+    }
     st.n_groups = 0u;
     st.n_deliv = 0u;
     st.n_dgroups = 0u;
@@ -777,7 +806,7 @@ hipError_t launch_ev_append(hipStream_t s, const EvDev &e, const EvLinkSrc &ls, 
 
 hipError_t launch_ev_drain(hipStream_t s, const EvDev &e, const EvOut &out, int64_t time_us, uint32_t seq, uint32_t window,
                            const EvLinkSrc *fresh_ls, const rm_tx_record *fresh_tx, int fresh_n, int64_t fresh_now, int fresh_immediate,
-                           const uint32_t *fresh_dropped)
+                           const uint32_t *fresh_dropped, bool batch)
 {
     // Three launches.  Selection (what fires before time_us; `window`: the host's bound on the pending packets); every
     // fired group's wave finds its place in the pop order by counting, writes its deliveries and enters the last-writer
@@ -809,8 +838,53 @@ hipError_t launch_ev_drain(hipStream_t s, const EvDev &e, const EvOut &out, int6
     }
     static const int share = [] { const char *v = getenv("RM_EV_SHARE"); return v ? atoi(v) : 2; }(); // (0: every delivery from k_ev_apply)
     static const int lds_keys = [] { const char *v = getenv("RM_EV_EMIT_LDS"); return v ? atoi(v) : 1; }(); // (0: the rank pass reads global memory)
-    RM_KLAUNCH(k_ev_emit, dim3(512), dim3(256), 0, s, after, out, share, lds_keys);
-    RM_KLAUNCH(k_ev_apply, dim3(512), dim3(256), 0, s, after, out, time_us, seq, share);
+    if (batch) { // (a drain of rm_events_process_batch: placed behind the drain before it, ev_batch_out)
+        RM_KLAUNCH(k_ev_emit<true>, dim3(512), dim3(256), 0, s, after, out, share, lds_keys);
+        RM_KLAUNCH(k_ev_apply<true>, dim3(512), dim3(256), 0, s, after, out, time_us, seq, share);
+    } else {
+        RM_KLAUNCH(k_ev_emit<false>, dim3(512), dim3(256), 0, s, after, out, share, lds_keys);
+        RM_KLAUNCH(k_ev_apply<false>, dim3(512), dim3(256), 0, s, after, out, time_us, seq, share);
+    }
+    return hipGetLastError();
+}
+
+// k_ev_batch_size (rm_events_process_batch, before its drains): what bounds the batch's delivery list -- per slot the heard links its
+// append will copy (ev_append_body's `total`), and the links / packets already pending -- into host-mapped memory for the host to
+// size the block by; and the running bases of the drains' placement start at zero.  One workgroup per slot.
+__global__ void __launch_bounds__(256) k_ev_batch_size(const EvDev e, const EvBatchSlot *__restrict__ slots, int n, uint32_t *__restrict__ out)
+{
+    __shared__ uint32_t s_tot[4];
+    const int b = int(blockIdx.x);
+    const EvBatchSlot sl = slots[b];
+    uint32_t total = 0;
+    if (sl.n_new > 0) {
+        if (sl.ls.cnt) {
+            uint32_t part = 0;
+            for (int i = threadIdx.x; i < sl.ls.n_scan; i += 256) part += sl.ls.cnt[i];
+            for (int d = 32; d >= 1; d >>= 1) part += uint32_t(__shfl_xor(int(part), d));
+            if ((threadIdx.x & 63) == 0) s_tot[threadIdx.x >> 6] = part;
+            __syncthreads();
+            total = s_tot[0] + s_tot[1] + s_tot[2] + s_tot[3];
+        } else {
+            total = sl.ls.off[sl.n_new];
+        }
+    }
+    if (threadIdx.x != 0) return;
+    __hip_atomic_store(&out[2 + b], total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (b == 0) {
+        EvState &st = *e.st;
+        const EvTails tl = st.tails[e.par];
+        __hip_atomic_store(&out[0], tl.pool_tail - st.pool_head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&out[1], tl.pk_tail - st.pk_head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        st.out_base = 0u;
+        st.run_base = 0u;
+    }
+}
+
+hipError_t launch_ev_batch_size(hipStream_t s, const EvDev &e, const EvBatchSlot *slots, int n, uint32_t *out)
+{
+    if (n <= 0) return hipErrorInvalidValue;
+    RM_KLAUNCH(k_ev_batch_size, dim3(n), dim3(256), 0, s, e, slots, n, out);
     return hipGetLastError();
 }
 

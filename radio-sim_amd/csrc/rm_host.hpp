@@ -226,6 +226,16 @@ struct rm_context : TickSlot {
             int64_t now = 0;
             const uint32_t *dropped = nullptr;
         } pending;
+        // rm_events_process_batch: the ticks of the last rm_batch_run_* that may still be handed over (0: none), and the
+        // generation they were left in -- `gen` moves with whatever rewrites the slots, the node table or the medium, and with
+        // every drain (ev_touch), so a batch whose slots are no longer what it evaluated is refused
+        uint64_t gen = 0, batch_gen = 0;
+        int batch_n = 0;
+        bool batch_ok = false;    // ... and whether its form is one the hand-over takes (not the gathered / rm_dist_* forms)
+        char *h_batch = nullptr;  // host-mapped: the batch's per-tick headers, then its runs and deliveries (grows geometrically)
+        size_t h_batch_bytes = 0;
+        rm::EvBatchSlot *h_bslots = nullptr; // pinned, host-mapped: [RM_MAX_BATCH] what k_ev_batch_size reads of the slots ...
+        uint32_t *h_bsize = nullptr;         // ... and what it writes: pending links, pending packets, then per slot its links
     } ev;
     DevBuf<uint8_t> d_enabled;   // Transciever.isEnabled by node index
 
@@ -477,6 +487,8 @@ struct ProbeScope {
 rm::EvDev ev_dev(rm_context *c);
 int ev_ensure_nodes(rm_context *c);
 int ev_append(rm_context *c, TickSlot &ts, bool may_wait = false);
+inline void ev_touch(rm_context *c) { ++c->ev.gen; } // the slots / node table / medium changed, or a drain ran
+void ev_batch_ran(rm_context *c, int rc, int n_ticks, bool eligible); // after rm_batch_run_*: what rm_events_process_batch may take
 int ev_flush_append(rm_context *c);
 
 // ---- rm_api_tick.cpp: results of an evaluated tick, the host-mapped result block

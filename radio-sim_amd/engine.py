@@ -530,8 +530,27 @@ class Engine:
         from ._lib import DeliveryView
         v = DeliveryView()
         check(self._L.rm_events_process(self._h, int(time_us), C.byref(v)))
-        k = v.count
         self.oldest_pending_packet = v.oldest_packet   # every packet below it has fired its last event
+        return self._delivery_tuple(v, copy, runs)
+
+    def events_process_batch(self, times, copy=True, runs=False):
+        """The ticks of the last batch_run_device / batch_run_sources_device handed to the reception stage, slot b as tick b, each
+        followed by the drain events_process(times[b]) -- the same deliveries, bit for bit, as lone ticks and drains in turn.
+        Returns one tuple per tick, shaped as events_process returns it (copy=False: wrapped in place, valid until the next
+        events_process* call)."""
+        from ._lib import DeliveryView
+        t = np.ascontiguousarray(times, dtype=np.int64)
+        n = len(t)
+        views = (DeliveryView * max(n, 1))()
+        check(self._L.rm_events_process_batch(self._h, n, t.ctypes.data, views))
+        self.oldest_pending_packets = [views[b].oldest_packet for b in range(n)]   # per tick, as events_process leaves it
+        if n:
+            self.oldest_pending_packet = views[n - 1].oldest_packet
+        return [self._delivery_tuple(views[b], copy, runs) for b in range(n)]
+
+    @staticmethod
+    def _delivery_tuple(v, copy, runs):
+        k = v.count
 
         def arr(ptr, dtype, count=k):
             a = _wrap(ptr, dtype, count)

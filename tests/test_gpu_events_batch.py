@@ -1,0 +1,466 @@
+"""The ticks of a batch handed to the reception stage (rm_events_process_batch): per tick exactly what a lone tick followed by
+rm_events_process gives -- against the oracle's serial replay of the reference's event path (oracle/rm_events.c), and
+against the same session run through lone ticks -- plus the refusals that keep a stale batch out of the stage and the
+capacity reports."""
+import numpy as np
+import pytest
+
+from util import DeviceArray, KINDS, configure_engine, oracle_model, random_nodes, to_tx_records
+
+pytestmark = pytest.mark.gpu
+
+
+# ---------------------------------------------------------------- helpers (after tests/test_gpu_events.py)
+def oracle_deliveries(O, ev):
+    d = ev[ev["kind"] == O.EV_RX_END_DELIVERY]
+    return d["pkt"].astype(np.int64), d["node"].astype(np.int32), d["rssi"].astype(np.float64)
+
+
+def oracle_drain(O, sim, t, immediate=(), own=None):
+    pkt, dst, rssi = oracle_deliveries(O, sim.step(t))
+    if immediate:     # the constant-loss medium delivered synchronously, before the drain
+        pkt = np.concatenate([np.array([i[0] for i in immediate], dtype=np.int64), pkt])
+        dst = np.concatenate([np.array([i[1] for i in immediate], dtype=np.int32), dst])
+        rssi = np.concatenate([np.array([i[2] for i in immediate]), rssi])
+    if own is not None:
+        keep = (dst >= own[0]) & (dst < own[0] + own[1])
+        pkt, dst, rssi = pkt[keep], dst[keep], rssi[keep]
+    return pkt, dst, rssi
+
+
+def same_drain(got, want, what):
+    gp, gd, gr = got[:3]
+    pkt, dst, rssi = want
+    assert len(gp) == len(pkt), "%s: %d deliveries, oracle %d" % (what, len(gp), len(pkt))
+    np.testing.assert_array_equal(gp, pkt, err_msg=what + " packet order")
+    np.testing.assert_array_equal(gd, dst, err_msg=what + " destination order")
+    np.testing.assert_array_equal(gr.view(np.int64), rssi.view(np.int64), err_msg=what + " rssi bits")
+    return len(pkt)
+
+
+def check_nodes(eng, sim, nodes, what, own=None):
+    want_rssi, want_state = sim.node_info(enabled=nodes.enabled)
+    got_rssi, got_state, got_ch = eng.node_info()
+    sel = slice(None) if own is None else slice(own[0], own[0] + own[1])
+    np.testing.assert_array_equal(got_state[sel], want_state[sel], err_msg=what + " receiving state")
+    np.testing.assert_array_equal(got_rssi[sel], want_rssi[sel], err_msg=what + " rssi of node-info")
+    np.testing.assert_array_equal(got_ch, nodes.channel, err_msg=what + " channel")
+    # rm_node_info_changed: what it reported since the last call, applied to what it reported before, is the same table
+    cn, cr, cs, cc = eng.node_info_changed()
+    shadow = getattr(eng, "_batch_reported", None)
+    if shadow is None or len(shadow[0]) != len(got_rssi):
+        assert sorted(cn.tolist()) == list(range(len(got_rssi))), what + ": a first report names every node once"
+        shadow = [np.zeros(len(got_rssi)), np.zeros(len(got_rssi), dtype=np.int32), np.zeros(len(got_rssi), dtype=np.int32)]
+    else:
+        assert len(set(cn.tolist())) == len(cn), what + ": a node reported twice"
+        same = (shadow[0][cn].view(np.int64) == cr.view(np.int64)) & (shadow[1][cn] == cs) & (shadow[2][cn] == cc)
+        assert not same.any(), what + ": reported without a change"
+    shadow[0][cn], shadow[1][cn], shadow[2][cn] = cr, cs, cc
+    eng._batch_reported = shadow
+    np.testing.assert_array_equal(shadow[0].view(np.int64), got_rssi.view(np.int64), err_msg=what + " incremental rssi")
+    np.testing.assert_array_equal(shadow[1], got_state, err_msg=what + " incremental state")
+
+
+class Session:
+    """One engine and the oracle's serial replay of the same Simulator: ticks go in as a batch (handed over with
+    rm_events_process_batch), as lone ticks (rm_tick_* + rm_events_process) or not at all (a plain drain)."""
+
+    def __init__(self, O, rsa, eng, seed, kind, params, n=1500, per_tick=30, tick_styles=(1000,), aligned=False,
+                 hex_lengths=(0, 2, 20, 64, 254), matrix=None, sinr=False, own=None, draws=True, min_per_tick=0):
+        self.O, self.rsa, self.eng, self.kind, self.own, self.sinr = O, rsa, eng, kind, own, sinr
+        self.rng = rng = np.random.default_rng(seed)
+        self.n, self.per_tick, self.tick_styles, self.aligned, self.hex_lengths = n, per_tick, tick_styles, aligned, hex_lengths
+        self.min_per_tick = min_per_tick
+        side = 50.0 * np.sqrt(np.pi * n / 20.0)
+        self.nodes = nodes = random_nodes(O, n, side, seed)
+        if draws:
+            nodes.rxprob[rng.choice(n, n // 5, replace=False)] = 0.6
+            nodes.txprob[rng.choice(n, n // 20, replace=False)] = 0.5
+        nodes.enabled[rng.choice(n, n // 50, replace=False)] = 0
+        configure_engine(eng, nodes, kind, params, matrix)
+        if own is not None:
+            eng.set_partition(*own)
+        eng.seed(seed)
+        eng._batch_reported = None
+        eng.events_enable()
+        eng.set_time(0)
+        self.mdl = oracle_model(O, kind, params, matrix)
+        self.state = O.lib().orc_jrandom_seed(seed)
+        self.sim = O.Sim(n)
+        self.now, self.base, self.delivered = 0, 0, 0
+        self.onair = np.zeros(0, dtype=O.PACKET_DTYPE)
+        self.keep = []
+
+    def _packets(self, t_end):
+        rng, n = self.rng, self.n
+        t = int(rng.integers(self.min_per_tick, self.per_tick + 1))
+        src = np.sort(rng.choice(n, t, replace=False)).astype(np.int32)
+        if self.sinr:   # one start, one air time per tick (the frames are named by source indices)
+            return src, self.nodes.packets(src, self.now, 32 * int(rng.choice(self.hex_lengths)))
+        pk = self.nodes.packets(src, 0, 0)
+        pk["start_us"] = self.now if self.aligned else rng.integers(self.now - 50, t_end, t)   # a start before "now" is clamped
+        pk["air_us"] = 32 * rng.choice(self.hex_lengths, t)
+        return src, pk
+
+    def _oracle_tick(self, pk):
+        O = self.O
+        if self.sinr:
+            self.onair = self.onair[self.onair["start_us"] + self.onair["air_us"] > self.now]
+            want = O.tick(self.mdl, self.nodes, np.concatenate([self.onair, pk]), first_new=len(self.onair), rng_state=self.state)
+            self.onair = np.concatenate([self.onair, pk])
+        else:
+            want = O.tick(self.mdl, self.nodes, pk, rng_state=self.state)
+        self.state = want.rng_state
+        imm = self.sim.medium_calls(want, pk, pkt_base=self.base, const_loss=(self.kind == "udgm_const"))
+        self.base += len(pk)
+        return imm
+
+    def batch(self, k, what):
+        """k ticks through one rm_batch_run_* call, handed over in one rm_events_process_batch call"""
+        eng, O = self.eng, self.O
+        assert eng.events_next_packet() == self.base
+        t0, ends, srcs, pks = self.now, [], [], []
+        begins = []
+        for b in range(k):
+            t_end = self.now + int(self.rng.choice(self.tick_styles))
+            src, pk = self._packets(t_end)
+            begins.append(self.now)
+            ends.append(t_end)
+            srcs.append(src)
+            pks.append(pk)
+            self.now = t_end
+        self.now = t0
+        if self.sinr:
+            arrs = [DeviceArray(s) if len(s) else None for s in srcs]
+            eng.batch_run_sources_device(begins, ends, [a.ptr.value if a is not None else 0 for a in arrs], [len(s) for s in srcs],
+                                         begins, [int(p["air_us"][0]) if len(p) else 32 for p in pks])
+        else:
+            arrs = [DeviceArray(to_tx_records(self.rsa, p)) if len(p) else None for p in pks]
+            eng.batch_run_device(begins, ends, [a.ptr.value if a is not None else 0 for a in arrs], [len(p) for p in pks])
+        views = eng.events_process_batch(ends)
+        assert len(views) == k
+        for b in range(k):
+            imm = self._oracle_tick(pks[b])
+            self.delivered += same_drain(views[b], oracle_drain(O, self.sim, ends[b], imm, self.own), "%s batch tick %d" % (what, b))
+            self.now = ends[b]
+        assert eng.events_next_packet() == self.base
+        check_nodes(eng, self.sim, self.nodes, what + " after the batch", self.own)
+        for a in arrs:
+            if a is not None:
+                a.free()
+
+    def lone(self, what):
+        eng = self.eng
+        t_end = self.now + int(self.rng.choice(self.tick_styles))
+        src, pk = self._packets(t_end)
+        if self.sinr:
+            dev = DeviceArray(src) if len(src) else None
+            eng.tick_run_sources_device(self.now, t_end, dev.ptr.value if dev is not None else 0, len(src), self.now,
+                                        int(pk["air_us"][0]) if len(pk) else 32)
+        else:
+            dev = None
+            eng.tick(to_tx_records(self.rsa, pk), self.now, t_end)
+        imm = self._oracle_tick(pk)
+        self.drain(t_end, what, imm)
+        if dev is not None:
+            dev.free()
+
+    def drain(self, t, what, imm=()):
+        got = self.eng.events_process(t)
+        self.delivered += same_drain(got, oracle_drain(self.O, self.sim, t, imm, self.own), what)
+        check_nodes(self.eng, self.sim, self.nodes, what, self.own)
+        self.now = t
+
+    def finish(self):
+        self.drain(self.now + 10 ** 7, "final drain")
+        assert self.sim.pending == 0
+        assert self.eng.events_process(self.now + 1)[3] == 0
+        self.sim.close()
+        self.eng.events_disable()
+        return self.delivered
+
+
+def run_plan(s, plan):
+    for i, step in enumerate(plan):
+        if step == "lone":
+            s.lone("step %d lone" % i)
+        elif step == "drain":
+            s.drain(s.now + int(s.rng.integers(1, 3000)), "step %d drain" % i)
+        else:
+            s.batch(int(step), "step %d" % i)
+    return s.finish()
+
+
+PLAN = (7, "lone", 1, 64, "drain", "lone", 7, 3, "drain", 1)
+
+
+# ---------------------------------------------------------------- 1. against the oracle
+@pytest.mark.parametrize("seed", range(2))
+def test_udgm_draws_random_starts(O, rsa, engine, seed):
+    s = Session(O, rsa, engine, 100 + seed, "udgm", dict(udgm_success_ratio_rx=0.8), tick_styles=(1000, 1000, 10, 3000))
+    assert run_plan(s, PLAN) > 0
+
+
+def test_udgm_draws_batches_without_empty_ticks(O, rsa, engine):
+    """every tick transmits: the batches go through the batched sweep (an empty tick sends a batch through one launch sequence
+    per tick), whose slots must tell the stage that their verdicts were drawn"""
+    s = Session(O, rsa, engine, 150, "udgm", dict(udgm_success_ratio_rx=0.8), min_per_tick=1)
+    assert run_plan(s, (7, 3, "lone", 7, "drain", 16)) > 0
+
+
+def test_aligned_frames_tie_everywhere(O, rsa, engine):
+    s = Session(O, rsa, engine, 200, "udgm", {}, aligned=True, hex_lengths=(254,), per_tick=60)
+    assert run_plan(s, PLAN) > 0
+    s = Session(O, rsa, engine, 201, "udgm", {}, aligned=True, hex_lengths=(0, 0, 62), per_tick=60)
+    assert run_plan(s, (7, "lone", 64, 1)) > 0
+
+
+def test_constant_loss_delivers_first(O, rsa, engine):
+    assert run_plan(Session(O, rsa, engine, 500, "udgm_const", {}), PLAN) > 0
+
+
+def test_null_and_n2n(O, rsa, engine):
+    assert run_plan(Session(O, rsa, engine, 400, "null", {}, n=300, per_tick=6), PLAN) > 0
+    m = np.random.default_rng(5).uniform(0, 1, (300, 300))
+    assert run_plan(Session(O, rsa, engine, 401, "n2n", {}, n=300, per_tick=6, matrix=m), PLAN) > 0
+
+
+def test_logdist(O, rsa, engine):
+    s = Session(O, rsa, engine, 600, "logdist", dict(ld_sigma_db=4.0, ld_seed=77), n=3000, per_tick=40)
+    assert run_plan(s, PLAN) > 0
+
+
+@pytest.mark.parametrize("seed", range(2))
+def test_sinr_frames_on_the_air(O, rsa, engine, seed):
+    """SINR ticks named by source indices whose frames outlive their tick: the overlap batches of rm_api_airbatch.cpp"""
+    s = Session(O, rsa, engine, 700 + seed, "logdist", dict(ld_flags=1, ld_sigma_db=4.0, ld_seed=5 + seed), n=2500, per_tick=40,
+                hex_lengths=(10, 64, 254, 254), sinr=True, draws=False)
+    assert run_plan(s, (7, "lone", 1, 16, "drain", 7, "lone")) > 0
+
+
+def test_index_partition_keeps_its_own_events(O, rsa, engine):
+    s = Session(O, rsa, engine, 800, "udgm", {}, n=2000, own=(700, 900), draws=False, per_tick=40)
+    assert run_plan(s, PLAN) > 0
+
+
+# ---------------------------------------------------------------- 2. batch == lone ticks
+def lone_and_batch(rsa, eng, ticks, times, reset, sources_run, batch_run):
+    """the same ticks through lone ticks + rm_events_process and through one batch + rm_events_process_batch, on a fresh stage
+    each -- and a fresh medium (reset: the SINR medium's frames of the first run must not stay on the air for the second)"""
+    reset()
+    eng.events_enable(1 << 16, 1 << 22)
+    eng.set_time(0)
+    lone, lone_oldest = [], []
+    for b in range(len(ticks)):
+        sources_run(b)
+        lone.append(eng.events_process(times[b], runs=True))
+        lone_oldest.append(eng.oldest_pending_packet)
+    lone_info = eng.node_info()
+    lone_next = eng.events_next_packet()
+    reset()
+    eng.events_enable(1 << 16, 1 << 22)
+    eng.set_time(0)
+    batch_run()
+    got = eng.events_process_batch(times, runs=True)
+    assert eng.events_next_packet() == lone_next
+    assert eng.oldest_pending_packets == lone_oldest
+    for b, (x, y) in enumerate(zip(lone, got)):
+        for k, name in enumerate(("run packet", "run first", "run count", "dst")):
+            np.testing.assert_array_equal(x[k], y[k], err_msg="tick %d %s" % (b, name))
+        np.testing.assert_array_equal(x[4].view(np.int64), y[4].view(np.int64), err_msg="tick %d rssi bits" % b)
+        assert x[5] == y[5], "tick %d pending" % b
+    for x, y in zip(lone_info, eng.node_info()):
+        np.testing.assert_array_equal(x.view(np.int64) if x.dtype == np.float64 else x, y.view(np.int64) if y.dtype == np.float64 else y)
+    return sum(len(x[3]) for x in lone)
+
+
+def test_configs2_shape_sixty_four_ticks(O, rsa, engine):
+    """configs[2]: 100 k nodes, 1 000 frames of 8 128 us per 1 000 us tick, shadowing; 64 ticks in one batch"""
+    from radio_sim_amd import workload as W
+    n, t, k = 100_000, 1000, 64
+    nodes_w = W.make_nodes(n, 3)
+    nodes = O.NodeTable(n)
+    nodes.x, nodes.y = nodes_w.x, nodes_w.y
+    engine.upload_table(nodes)
+
+    def reset():
+        engine.set_model(rsa.MODEL_LOGDIST, ld_sigma_db=4.0, ld_seed=0xC0FFEE)
+    dev = [DeviceArray(W.choose_sources(n, t, 0xC0FFEE00 + 3, b)) for b in range(k)]
+    starts = [b * W.TICK_US for b in range(k)]
+    times = [s + W.TICK_US for s in starts]
+
+    def lone(b):
+        engine.tick_run_sources_device(starts[b], times[b], dev[b].ptr.value, t, starts[b], W.AIR_US)
+
+    def batch():
+        engine.batch_run_sources_device(starts, times, [d.ptr.value for d in dev], [t] * k, starts, [W.AIR_US] * k)
+    assert lone_and_batch(rsa, engine, dev, times, reset, lone, batch) > 100_000 * 10
+    engine.events_disable()
+    for d in dev:
+        d.free()
+
+
+@pytest.mark.parametrize("kind,params", [("udgm", dict(udgm_success_ratio_rx=0.7)), ("udgm_const", {}),
+                                         ("logdist", dict(ld_flags=1, ld_sigma_db=4.0, ld_seed=3))])
+def test_batch_equals_lone_ticks(O, rsa, engine, kind, params):
+    n, k = 4000, 24
+    rng = np.random.default_rng(31)
+    nodes = random_nodes(O, n, 50.0 * np.sqrt(np.pi * n / 20.0), 31)
+    if kind == "udgm":   # (draws; the SINR medium's overlapping batches take none)
+        nodes.rxprob[rng.choice(n, n // 5, replace=False)] = 0.6
+    configure_engine(engine, nodes, kind, params)
+    # (no empty tick: the batch goes through the batched kernels, not one launch sequence per tick)
+    srcs = [np.sort(rng.choice(n, int(rng.integers(1, 80)), replace=False)).astype(np.int32) for _ in range(k)]
+    dev = [DeviceArray(s) if len(s) else None for s in srcs]
+    starts = [b * 1000 for b in range(k)]
+    times = [s + 1000 for s in starts]
+    airs = [32 * int(rng.choice([10, 64, 254])) for _ in range(k)]
+    ptr = lambda b: dev[b].ptr.value if dev[b] is not None else 0
+
+    def lone(b):
+        engine.tick_run_sources_device(starts[b], times[b], ptr(b), len(srcs[b]), starts[b], airs[b])
+
+    def batch():
+        engine.batch_run_sources_device(starts, times, [ptr(b) for b in range(k)], [len(s) for s in srcs], starts, airs)
+    def reset():   # (rm_set_model takes the frames of the run before off the air; the generator starts over)
+        configure_engine(engine, nodes, kind, params)
+        engine.seed(9)
+    assert lone_and_batch(rsa, engine, srcs, times, reset, lone, batch) > 0
+    engine.events_disable()
+    for d in dev:
+        if d is not None:
+            d.free()
+
+
+# ---------------------------------------------------------------- 3. refusals and capacity
+def small_batch(rsa, s, k=3):
+    """a batch of k ticks that is NOT handed over: the oracle never sees it (deterministic medium: no draws consumed)"""
+    ends, arrs, cnt = [], [], []
+    t = s.now
+    for b in range(k):
+        src = np.sort(s.rng.choice(s.n, 20, replace=False)).astype(np.int32)
+        pk = s.nodes.packets(src, t, 32 * 64)
+        arrs.append(DeviceArray(to_tx_records(rsa, pk)))
+        cnt.append(len(pk))
+        ends.append(t + 1000)
+        t += 1000
+    s.eng.batch_run_device([e - 1000 for e in ends], ends, [a.ptr.value for a in arrs], cnt)
+    s.keep += arrs
+    return ends
+
+
+def refused(rsa, fn, code):
+    with pytest.raises(rsa.RadioMediumError) as ei:
+        fn()
+    assert ei.value.code == code, ei.value
+
+
+def test_refusals_leave_the_stage_usable(O, rsa, engine):
+    ERR_STATE, ERR_INVALID = -5, -1
+    s = Session(O, rsa, engine, 900, "udgm", {}, n=1500, draws=False)
+    eng = s.eng
+
+    def then(action, code, what, k=3):
+        ends = small_batch(rsa, s, k)
+        if action is not None:
+            action(ends)
+        before = eng.events_next_packet()
+        refused(rsa, lambda: eng.events_process_batch(ends), code)
+        assert eng.events_next_packet() == before, what + ": the refusal changed the numbering"
+        s.lone(what + ": lone tick after the refusal")
+    # nothing to hand over: a fresh stage, and a batch handed over already
+    refused(rsa, lambda: eng.events_process_batch([1000]), ERR_STATE)
+    s.batch(2, "a batch")
+    refused(rsa, lambda: eng.events_process_batch([s.now + 1000, s.now + 2000]), ERR_STATE)
+    ends = small_batch(rsa, s, 3)
+    refused(rsa, lambda: eng.events_process_batch(ends[:2]), ERR_INVALID)   # n_ticks differs ...
+    s.batch(3, "a new batch after the refusal")
+    then(lambda e: s.lone("a lone tick in between"), ERR_STATE, "lone tick")
+    def transmit(_):
+        eng.transmit(5, s.now, 10)             # (rm_transmit hands its packet to the stage at once: the oracle's too)
+        pk = s.nodes.packets([5], s.now, 320)
+        s.sim.medium_calls(O.tick(s.mdl, s.nodes, pk), pk, pkt_base=s.base)
+        s.base += 1
+    then(transmit, ERR_STATE, "rm_transmit")
+    then(lambda e: small_batch(rsa, s, 2), ERR_INVALID, "another batch of other size")
+    nd = s.nodes   # (the node table and the medium are set again as they are: the oracle's stay valid)
+    then(lambda e: eng.update_node(3, nd.x[3], nd.y[3], nd.z[3], nd.txpower[3], int(nd.channel[3]), int(nd.enabled[3]), nd.rxprob[3],
+                                   nd.txprob[3]), ERR_STATE, "rm_node_update")
+    then(lambda e: eng.move_nodes([4], nd.x[4:5], nd.y[4:5], nd.z[4:5]), ERR_STATE, "rm_nodes_move")
+    then(lambda e: eng.upload_table(nd), ERR_STATE, "rm_nodes_upload")
+    then(lambda e: eng.set_model(KINDS["udgm"]), ERR_STATE, "rm_set_model")
+    then(lambda e: s.drain(s.now + 500, "a drain in between"), ERR_STATE, "rm_events_process")
+    # events switched on after the batch ran
+    eng.events_disable()
+    ends = small_batch(rsa, s, 2)
+    refused(rsa, lambda: eng.events_process_batch(ends), ERR_STATE)       # (not enabled at all)
+    eng.events_enable()
+    refused(rsa, lambda: eng.events_process_batch(ends), ERR_STATE)
+    s.sim.close()
+    for a in s.keep:
+        a.free()
+    # a new session over the same engine after all of this: still the oracle's
+    s = Session(O, rsa, engine, 901, "udgm", {}, n=1500, draws=False)
+    assert run_plan(s, (3, "lone", 2)) > 0
+
+
+def test_gathered_and_spatial_forms_are_refused(O, rsa, engine):
+    s = Session(O, rsa, engine, 910, "udgm", {}, n=1500, draws=False)
+    eng = s.eng
+    src = np.sort(s.rng.choice(s.n, 20, replace=False)).astype(np.int32)
+    recs = DeviceArray(to_tx_records(rsa, s.nodes.packets(src, 0, 2048)))
+    try:
+        eng.batch_run_gathered_device([0], [1000], recs.ptr.value, 1, 20)
+    except rsa.RadioMediumError:
+        pass                                   # (the gathered form may refuse this table; the hand-over must refuse either way)
+    refused(rsa, lambda: eng.events_process_batch([1000]), -5)
+    s.lone("a lone tick after the gathered batch's refusal")
+    eng.set_partition_spatial(0, 2)
+    try:
+        small_batch(rsa, s, 1)
+    except rsa.RadioMediumError:
+        pass
+    refused(rsa, lambda: eng.events_process_batch([s.now + 1000]), -5)
+    recs.free()
+    for a in s.keep:
+        a.free()
+    s.sim.close()
+    eng.events_disable()
+
+
+def test_draws_pending_refused(O, rsa, engine):
+    s = Session(O, rsa, engine, 920, "udgm", dict(udgm_success_ratio_rx=0.5), n=1500, own=(0, 700))
+    eng = s.eng
+    pk = s.nodes.packets(np.arange(0, 1500, 50, dtype=np.int32), 0, 2048)
+    eng.tick_begin(0, 1000)
+    eng.enqueue_records(to_tx_records(rsa, pk))
+    eng.tick_run()                                              # partitioned + draws: waits for rm_tick_finish_draws
+    assert eng.draws_pending()
+    refused(rsa, lambda: eng.events_process_batch([1000]), -5)
+    s.sim.close()
+    eng.events_disable()
+
+
+def test_capacity_is_reported(O, rsa, engine):
+    ERR_CAPACITY = -4
+    n = 1500
+    nodes = random_nodes(O, n, 50.0 * np.sqrt(np.pi * n / 20.0), 930)
+    configure_engine(engine, nodes, "udgm", {})
+    rng = np.random.default_rng(930)
+    recs = [DeviceArray(to_tx_records(rsa, nodes.packets(np.sort(rng.choice(n, 40, replace=False)).astype(np.int32), 1000 * b, 2048)))
+            for b in range(4)]
+    ptrs = [r.ptr.value for r in recs]
+    starts = [1000 * b for b in range(4)]
+    ends = [s + 1000 for s in starts]
+    # the pending-link ring
+    engine.events_enable(0, 64)
+    engine.batch_run_device(starts, ends, ptrs, [40] * 4)
+    refused(rsa, lambda: engine.events_process_batch(ends), ERR_CAPACITY)
+    # a slot whose heard links overflowed the link capacity
+    engine.events_enable()
+    engine.set_link_capacity(50)
+    engine.batch_run_device(starts, ends, ptrs, [40] * 4)
+    refused(rsa, lambda: engine.events_process_batch(ends), ERR_CAPACITY)
+    engine.events_disable()
+    for r in recs:
+        r.free()
