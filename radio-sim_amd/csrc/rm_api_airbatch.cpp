@@ -110,6 +110,7 @@ int batch_run_overlap(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us,
     ms.flags &= ~RM_LD_SINR;
     ms.ld_level = ms.ld_sens;
     bool batched = true;
+    ParityGuard parity(slots_v.data(), plans_v.data()); // (every return before the launch below)
     for (int b = 0; b < n_ticks; ++b) {
         TickSlot &ts = *slot_of(c, b);
         slots_v[size_t(b)] = &ts;
@@ -118,6 +119,7 @@ int batch_run_overlap(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us,
         c->t_begin = t_begin_us[b];
         RM_TRY(prepare_tick(c, ts, pl, true, tx, n_per[b], 0, dev_src ? dev_src[b] : nullptr, dev_src ? start_us[b] : 0,
                             dev_src ? air_us[b] : 0, kAirBatch, 0, &knobs));
+        parity.planned();
         if (gathered || gathered_idx) {
             rm::TickDev &t = pl.t;
             if (gathered_idx) {
@@ -153,15 +155,9 @@ int batch_run_overlap(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us,
     }
     c->t_begin = t_begin_us[0];
     c->t_end = t_end_us[n_ticks - 1];
-    if (!batched) {
-        // (planned, never launched: a plan hands its slot's counters to the other parity because the tick's first kernel zeroes
-        // them for the tick after it -- a tick that is not launched has zeroed nothing, so the slots go back to where they were, or
-        // the next tick through the sweep kernels would start from the counters of the tick before last)
-        for (int b = 0; b < n_ticks; ++b)
-            if (!plans_v[size_t(b)].empty) slots_v[size_t(b)]->parity ^= 1;
+    if (!batched) // (planned, never launched: the guard hands the slots' counter parity back)
         return fail(RM_ERR_STATE, "the SINR medium carries frames that outlive their tick into the next one: run overlapping ticks one "
                                   "at a time (the batched form takes non-empty ticks of at most 8192 frames over an fp32 frame)");
-    }
     c->air_max_t_begin = std::max(c->air_max_t_begin, t_begin_us[n_ticks - 1]);
 
     // ---- the index's shape: time slots = the window's batches, then the ticks
@@ -362,6 +358,7 @@ int batch_run_overlap(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us,
         rf.t_first = t_begin_us[0];
         rf.batch_end = batch_end;
     }
+    parity.dismiss();
     const int rc = launch_batch(c, run_slots.data(), run_plans.data(), int(run_plans.size()), &ms, interference_stages, &arg,
                                 (rank_frames || digest_off >= 0) && gathered_idx ? &rf : nullptr);
     if (rc != RM_OK) return rc;

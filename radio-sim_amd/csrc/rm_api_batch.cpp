@@ -141,8 +141,10 @@ int rmh::launch_batch(rm_context *c, TickSlot *const *slots, const TickPlan *pla
     }
     // RM_BATCH_FRAMES=1: the batch through the one-frame-per-workgroup kernel of the closed-loop tick instead of the
     // three sweep stages (one launch; the compact arrays on demand, per slot)
+    // (not over a rank's frame list: k_tick_frames_batch writes no offsets by global packet number, which the result readers
+    // of such a slot take)
     static const bool batch_frames = std::getenv("RM_BATCH_FRAMES") != nullptr;
-    if (batch_frames && !cfg.stochastic && !plans[0].sinr && !after_sweep) {
+    if (batch_frames && !cfg.stochastic && !plans[0].sinr && !after_sweep && !(rank_frames && ticks[0].n_pub > 0)) {
         int seg_len = rm::frame_tick_segment(ticks[0], cfg, m);
         for (int b = 1; b < n && seg_len > 0; ++b) seg_len = std::min(seg_len, rm::frame_tick_segment(ticks[b], cfg, m));
         if (seg_len > 0) {
@@ -253,6 +255,7 @@ int rmh::batch_run(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us, co
     TickPlan *const plans = plans_v.data();
     bool batched = true;
     bool rank_frames = false;
+    ParityGuard parity(slots, plans); // (every return before the launch below)
     if (gathered_idx) {
         RM_TRY(prepare_nodes(c)); // (the partition's receivers: rank_frames_wanted asks for their number)
         rank_frames = rank_frames_wanted(c);
@@ -277,6 +280,7 @@ int rmh::batch_run(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us, co
                                          dev_src ? start_us[b] : 0, dev_src ? air_us[b] : 0, kAirNone, 0, &knobs);
         c->dev_records_from_caller = false;
         RM_TRY(rc_prep);
+        parity.planned();
         if (any_gathered) {
             rm::TickDev &t = plans[b].t;
             if (gathered_idx) {
@@ -308,30 +312,25 @@ int rmh::batch_run(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us, co
         c->air_tail = size_t(n_per[n_ticks - 1]);
         c->air_batches.push_back({n_per[n_ticks - 1], start_us[n_ticks - 1] + air_us[n_ticks - 1], 0u});
     }
-    if (any_gathered && !batched) {
-        for (int b = 0; b < n_ticks; ++b) // (planned, never launched: the slots' counter parity goes back, rm_api_airbatch.cpp)
-            if (!plans[b].empty) slots[b]->parity ^= 1;
+    if (any_gathered && !batched)
         return fail(RM_ERR_STATE, "gathered records go through the batched kernels only (sorted receiver table, fp32 frame, "
                                   "at most 8192 frames per tick, no empty tick)");
-    }
     if (batched) {
         // SINR ticks named by source indices: one start and one air time per tick, so all of a tick's frames overlap each other and
         // a heard link's interference is its receiver's sum over ALL the tick's candidates less its own power -- summed per receiver
         // by the exact stage, no per-receiver lists (RM_SINR_ACC=0 keeps the lists; records given by the caller have their own
         // time spans and keep them too)
+        // The sums live in the slots' link-sized buffers: a link capacity below the receiver count leaves no room for them,
+        // and the whole batch keeps the lists (whose size follows the heard links).
         const char *e_acc = std::getenv("RM_SINR_ACC");
-        const bool acc = sinr && (dev_src || gathered_idx) && !(e_acc && std::atoi(e_acc) == 0);
+        bool acc = sinr && (dev_src || gathered_idx) && !(e_acc && std::atoi(e_acc) == 0);
+        for (int b = 0; b < n_ticks && acc; ++b) acc = size_t(plans[b].t.n_rx) <= slots[b]->d_st_lin.n;
         if (sinr)
             for (int b = 0; b < n_ticks; ++b) {
                 rm::TickDev &t = plans[b].t;
                 if (acc) {
                     t.acc_lo = reinterpret_cast<unsigned long long *>(t.st_lin);   // (link-sized buffers of the slot: room for every receiver)
                     t.acc_hi = reinterpret_cast<unsigned long long *>(t.st_sinr);
-                    if (size_t(t.n_rx) > slots[b]->d_st_lin.n) {
-                        for (int k = 0; k < n_ticks; ++k) // (planned, never launched: the slots' counter parity goes back)
-                            if (!plans[k].empty) slots[k]->parity ^= 1;
-                        return fail(RM_ERR_CAPACITY, "link capacity below the receiver count");
-                    }
                 } else {
                     t.reset_heads = 1;
                 }
@@ -348,12 +347,14 @@ int rmh::batch_run(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us, co
         rf.mine = c->table_digest;
         rf.margin = 0.f;     // nothing of these ticks outlives them
         rf.use_chmask = 1;
+        parity.dismiss();
         const int rc = launch_batch(c, slots, plans, n_ticks, nullptr, nullptr, nullptr, (rank_frames || digest_off >= 0) && gathered_idx ? &rf : nullptr);
         g_clock.report();
         return rc;
     }
     // configurations the batched kernels do not cover (fp64 frame, unsorted table, very many frames,
     // empty ticks): the same ticks, one launch sequence each
+    parity.dismiss();
     for (int b = 0; b < n_ticks; ++b) RM_TRY(launch_tick(c, *slots[b], plans[b]));
     return RM_OK;
 }

@@ -450,6 +450,28 @@ struct TickPlan {
     bool empty = false; // nothing to sweep: the result is an empty one
 };
 
+// A batch that plans its ticks and then returns without launching them hands the slots' counter parity back.  prepare_tick
+// flips a slot to the other parity because the tick's first kernel zeroes the other parity's counters for the tick after it; a
+// tick that is never launched zeroed nothing, and the next tick through the sweep kernels would start from the counters of the
+// tick before last.  planned(): one more slot was flipped (a non-empty plan); dismiss(): the ticks are launched from here on.
+struct ParityGuard {
+    TickSlot *const *slots;
+    const TickPlan *plans;
+    int n = 0;
+    bool armed = true;
+    ParityGuard(TickSlot *const *s, const TickPlan *p) : slots(s), plans(p) {}
+    void planned() { ++n; }
+    void dismiss() { armed = false; }
+    ~ParityGuard()
+    {
+        if (!armed) return;
+        for (int b = 0; b < n; ++b)
+            if (!plans[b].empty) slots[b]->parity ^= 1;
+    }
+    ParityGuard(const ParityGuard &) = delete;
+    ParityGuard &operator=(const ParityGuard &) = delete;
+};
+
 // Buffers and descriptor of one tick in result slot `ts`; `tx` is the on-air list in device memory
 // (build mode: where the records of the source indices `src_list` are written).
 // kAirScan: `tx` holds every frame on the air (as for a rebuild), only the new ones are evaluated, their interferers are found

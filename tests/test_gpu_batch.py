@@ -251,6 +251,49 @@ def test_sinr_batch_of_self_contained_ticks(engine, rsa, O, monkeypatch, acc):
         d.free()
 
 
+@pytest.mark.parametrize("acc", ["1", "0"])
+@pytest.mark.parametrize("form", ["sources", "gathered"])
+def test_sinr_batch_with_link_capacity_below_the_receiver_count(engine, rsa, O, monkeypatch, acc, form):
+    """A link capacity below the receiver count, with every heard link fitting: the per-receiver sums have no room in the
+    link-sized buffers, so the batch takes the per-receiver lists -- the oracle's links either way (before, the default form
+    refused the batch with RM_ERR_CAPACITY).  Ticks by source indices and by gathered source indices (one rank)."""
+    monkeypatch.setenv("RM_SINR_ACC", acc)
+    n = 30011
+    nd = _layout(O, n, seed=51)
+    rng = np.random.default_rng(52)
+    nd.channel[:] = 11 + rng.integers(0, 16, n)
+    params = dict(ld_flags=1, ld_sigma_db=4.0, ld_seed=19)
+    configure_engine(engine, nd, "logdist", params)
+    mdl = oracle_model(O, "logdist", params)
+    engine.set_link_capacity(28000)          # (room for the lists' entries, none for a sum per receiver)
+    n_ticks, t = 4, 65
+    srcs = _ticks(n, n_ticks, t, seed=53)
+    tb = np.arange(n_ticks, dtype=np.int64) * 1000
+    if form == "sources":
+        dev = [DeviceArray(s) for s in srcs]
+        engine.batch_run_sources_device(tb, tb + 1000, [d.ptr.value for d in dev], [t] * n_ticks, tb, [1000] * n_ticks)
+    else:
+        dev = [DeviceArray(np.concatenate(srcs))]
+        engine.batch_run_gathered_sources_device(tb, tb + 1000, dev[0].ptr.value, 1, t, tb, 1000)
+    heard = 0
+    for b in range(n_ticks):
+        cpu = O.tick(mdl, nd, nd.packets(srcs[b], int(tb[b]), 1000))
+        assert cpu.count > 0
+        assert_same(engine.batch_result_copy(b, t), cpu, "tick %d" % b)
+        heard += cpu.count
+    # ... and the next batch, with room for the sums again, takes them (later: nothing of the first batch on the air)
+    engine.set_link_capacity(1 << 20)
+    tb = tb + 10_000
+    if form == "sources":
+        engine.batch_run_sources_device(tb, tb + 1000, [d.ptr.value for d in dev], [t] * n_ticks, tb, [1000] * n_ticks)
+    else:
+        engine.batch_run_gathered_sources_device(tb, tb + 1000, dev[0].ptr.value, 1, t, tb, 1000)
+    for b in range(n_ticks):
+        assert_same(engine.batch_result_copy(b, t), O.tick(mdl, nd, nd.packets(srcs[b], int(tb[b]), 1000)), "tick %d again" % b)
+    for d in dev:
+        d.free()
+
+
 def test_sinr_batch_with_lossy_links_draws_from_the_shared_generator(engine, rsa, O):
     """SINR capture and java.util.Random draws in the same medium (rx-loss / tx-loss on some nodes): the
     ticks of such a batch take one launch sequence each (the batched SINR kernels carry no pending

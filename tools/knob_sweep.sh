@@ -19,6 +19,9 @@
 # a time on tables and batches of any size (RM_NEAR_LISTS=2 RM_WG_RPT=4 RM_FILTER_TICKS_PER_WG=5 / 40 RM_FILTER_GROUP=1) and never (RM_FILTER_GROUP=0), the lone tick's
 # frames dealt to the XCDs in turn instead of in eighths (RM_TICK_XCD_MAP=0), the drain's rank pass from global memory (RM_EV_EMIT_LDS=0),
 # the reorder stage's waves with single frames / runs of 64 / of 8 consecutive frames (RM_REORDER_RUN).
+# Added with tests/test_gpu_variants.py (which holds every knob to the oracle on every GPU run): the knobs no sweep had -- the batch
+# through the one-launch kernel (RM_BATCH_FRAMES), fixed shard counts, the pack's and the overlap stages' grids, the table without
+# the channel order, no near-frame lists, one SINR workgroup per shard, a rank's margin of none / everything.
 B=${1:-24}
 FIRST=${2:-0}
 LAST=${3:-99}
@@ -28,7 +31,9 @@ K=("RM_FILTER=wg" "RM_FILTER=wg RM_WG_RPT=4" "RM_FILTER=wg RM_WG_RPT=2" "RM_FILT
    "RM_FILTER_TICKS_PER_WG=3" "RM_NO_ZERO_COPY=1" "RM_FPW=3" "RM_FPW=200" "RM_SINR_GX=5" "RM_GROUP_NO_RCCL=1" "RM_SINR_SCAN=0"
    "RM_DENSE_TICK=1" "RM_DENSE_TICK=0" "RM_NEAR_LISTS=2 RM_WG_RPT=4" "RM_EV_FUSE=0" "RM_EV_SHARE=0" "RM_EV_SHARE=1" "RM_OV_PAIR_CAP=4096"
    "RM_RANK_FRAMES=0" "RM_SINR_ACC=0" "RM_DENSE_LAZY=0" "RM_HOST_LINK_RSSI=1"
-   "RM_NEAR_LISTS=2 RM_WG_RPT=4 RM_FILTER_TICKS_PER_WG=5 RM_FILTER_GROUP=1" "RM_NEAR_LISTS=2 RM_WG_RPT=4 RM_FILTER_TICKS_PER_WG=40 RM_FILTER_GROUP=1" "RM_FILTER_GROUP=0" "RM_TICK_XCD_MAP=0" "RM_EV_EMIT_LDS=0" "RM_REORDER_RUN=0" "RM_REORDER_RUN=6" "RM_REORDER_RUN=3 RM_FPW=5")
+   "RM_NEAR_LISTS=2 RM_WG_RPT=4 RM_FILTER_TICKS_PER_WG=5 RM_FILTER_GROUP=1" "RM_NEAR_LISTS=2 RM_WG_RPT=4 RM_FILTER_TICKS_PER_WG=40 RM_FILTER_GROUP=1" "RM_FILTER_GROUP=0" "RM_TICK_XCD_MAP=0" "RM_EV_EMIT_LDS=0" "RM_REORDER_RUN=0" "RM_REORDER_RUN=6" "RM_REORDER_RUN=3 RM_FPW=5"
+   "RM_BATCH_FRAMES=1" "RM_BATCH_SHARDS=8" "RM_BATCH_SHARDS=16" "RM_BATCH_SHARDS=32" "RM_PACK_WGS=8" "RM_OV_PAIRS_WGS=1" "RM_OV_EXACT_GX=1"
+   "RM_CHANNEL_ORDER=0" "RM_NEAR_LISTS=0" "RM_SINR_GX=1" "RM_RANK_MARGIN=0" "RM_RANK_MARGIN=100000")
 for i in "${!K[@]}"; do
     if [ $i -lt $FIRST ] || [ $i -gt $LAST ]; then continue; fi
     knobs="${K[$i]}"
