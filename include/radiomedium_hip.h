@@ -423,6 +423,44 @@ int rm_air_batch_pairs(rm_context *ctx, uint64_t *pairs, uint64_t *frames, uint6
  * 256 sub-rings, and the entries a sub-ring holds -- more allocated than held: the ring has gone round (old entries were reclaimed) */
 int rm_air_ring_stats(rm_context *ctx, uint64_t *max_allocated, uint64_t *sub_ring_entries);
 
+/* ---- channel energy query (CCA / ED) over the frames on the air ------------------------------------------
+ * Not reference behaviour (the reference answers with the latched RSSI of a frame being received, or a constant:
+ * Transciever.getRSSI, AbstractRadioMedium.getBaseRSSI -- rm_node_info mirrors that); the read side of the RM_LD_SINR
+ * extension's state.  For node j, time t, channel c: a frame of the context's on-air window
+ * counts iff its record is live (src >= 0), start_us <= t < start_us + air_us, channel == c, src != j and its rssi at j
+ * (frame position from its record, node position from the table as it is now, shadowing as in E2) reaches ifloor_dbm;
+ * energy_dbm = 10 log10(exact Q80 sum of the counting frames' linear powers + noise); no counting frame: the noise level.
+ * flags: RM_ED_TRANSMITTING -- some live frame of j's own spans t, on any channel (the energy is still the sum over the
+ * others); RM_ED_BUSY -- energy_dbm >= cca_threshold_dbm (a NaN threshold never sets it).  channel RM_CHANNEL_OWN: every
+ * node on its own channel, else the given channel for every queried node.  The node's enabled / rxprob / txprob play no part.
+ *
+ * Frames get into the window through the lone ticks of every form (rm_tick_begin .. rm_tick_flush / rm_tick_run, rm_transmit,
+ * rm_tick_run_sources_device, rm_tick_run_records_device) and through batches of overlapping ticks
+ * (rm_batch_run_sources_device and the gathered-sources forms when frames outlive their tick).  A batch of self-contained
+ * ticks leaves nothing of its earlier ticks: by its contract they have left the air when the next tick begins; with source
+ * indices the LAST tick's frames stay in the window (they may outlive the batch), with records nothing does (the host cannot
+ * see their spans) -- and such a batch does not move the clock the query is checked against.  A frame that had left the air
+ * when a later tick began is gone for good.
+ *
+ * RM_ERR_STATE: the model is not RM_MODEL_LOGDIST with RM_LD_SINR (only that medium keeps frames on the air); between
+ * rm_tick_begin and rm_tick_flush; a context with a receiver partition (rm_set_partition*), or whose window was selected
+ * for a region (gathered batches over a partition) -- the rm_group_*, rm_dist_* and gathered forms are out of scope.
+ * RM_ERR_INVALID: time_us earlier than the latest t_begin a tick over the window has had (frames that had left the air by
+ * then are gone); a later time_us is fine: every frame's own span is tested and the window is not changed by a query; a
+ * node index outside 0 .. n_nodes-1 in a host list (before anything is launched) -- in a device list such an entry gets
+ * NaN energy and flags 0 and nothing else is disturbed.  An empty window is no error: the noise level everywhere.
+ * Pending node changes are applied first, as a tick does.  The query writes the caller's outputs and scratch of its own,
+ * nothing else: a tick, a batch or a drain after it gives what it gave without it. */
+#define RM_CHANNEL_OWN (-1)
+#define RM_ED_TRANSMITTING 1
+#define RM_ED_BUSY 2
+/* asynchronous on the context's stream; all pointers are device memory; dev_nodes NULL: nodes 0 .. n-1 */
+int rm_channel_energy_device(rm_context *ctx, int64_t time_us, const int32_t *dev_nodes, int32_t n, int32_t channel,
+                             double cca_threshold_dbm, double *dev_energy_dbm, uint8_t *dev_flags /* may be NULL */);
+/* host arrays; synchronises; nodes NULL: nodes 0 .. n-1 */
+int rm_channel_energy(rm_context *ctx, int64_t time_us, const int32_t *nodes, int32_t n, int32_t channel,
+                      double cca_threshold_dbm, double *energy_dbm, uint8_t *flags /* may be NULL */);
+
 /* ---- several devices behind one caller --------------------------------------------------------------
  * The reference host is ONE process (Main.java:65-73): a group drives n contexts from one host thread, one
  * per device (an ordinal may repeat: several partitions on one GPU).  Receivers are partitioned over the

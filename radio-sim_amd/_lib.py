@@ -16,6 +16,8 @@ _SO = os.environ.get("RM_LIBRARY") or os.path.join(_CSRC, "libradiomedium_hip.so
 MODEL_NULL, MODEL_UDGM, MODEL_UDGM_CONST, MODEL_N2N, MODEL_LOGDIST = range(5)
 UNHEARD, INTERFERED, DELIVERED = 0, 1, 2
 LD_SINR = 1
+CHANNEL_OWN = -1
+ED_TRANSMITTING, ED_BUSY = 1, 2
 MAX_BATCH = 512
 RM_OK, RM_ERR_INVALID, RM_ERR_NO_DEVICE, RM_ERR_HIP, RM_ERR_CAPACITY, RM_ERR_STATE = 0, -1, -2, -3, -4, -5
 
@@ -223,6 +225,8 @@ SIGNATURES = {
     "rm_events_process_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "rm_node_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rm_node_info_changed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "rm_channel_energy_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
+    "rm_channel_energy": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
     "rm_det_math": (C.c_double, [C.c_int32, C.c_double]),
     "rm_link_hash": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
     "rm_evq_init": (None, [C.c_void_p]),

@@ -319,6 +319,9 @@ void rm_destroy(rm_context *c)
         }
         if (o.h_flag) (void)hipHostFree(o.h_flag);
     }
+    c->ed.cnt.release(); c->ed.tx_mark.release(); c->ed.bucket_f.release(); c->ed.every_f.release(); c->ed.bucket_m.release(); c->ed.every_m.release();
+    if (c->ed.h_block) (void)hipHostFree(c->ed.h_block);
+    c->ed.h_block = nullptr;
     c->d_patch.release();
     c->d_enabled.release();
     c->d_member.release(); c->d_draw_nodes.release(); c->d_all_off.release(); c->d_all_nodes.release();

@@ -218,6 +218,24 @@ struct ScanDev {
     float half, inv;        // cell = int((x + half) * inv)
 };
 
+// The channel energy query (rm_energy.hip): the frames of the on-air window that are live at the
+// query's time, indexed from scratch per query -- a kEdG x kEdG grid over the fp32 frame with up to kEdK frames per cell, the rest
+// (and frames without a bound or a place) in a list every node looks at -- and per NODE the stamp of the last query that found
+// it on the air.  The buffers belong to the query (rm_context::Energy), not to a tick slot.
+constexpr int kEdG = 64, kEdCells = kEdG * kEdG, kEdK = 16;
+constexpr int kEdSmallWindow = 256; // a window of fewer records is not worth a grid: every live frame goes into the list
+static_assert(kEdG == kSgG, "sg_cell1 maps positions to the cells of a kSgG x kSgG grid");
+struct EnergyDev {
+    uint32_t *cnt;      // [0] entries of `every`, [1] largest cut-off radius in the grid (float bits), [2 ..][kEdCells] frames per cell
+    float4 *bucket_f;   // [kEdCells][kEdK] the cell's frames: position in the fp32 frame, squared cut-off at the interference floor ...
+    int4 *bucket_m;     // ... channel, index in the window, source node, scale of the link-hash table's bins (float bits)
+    float4 *every_f;    // [window] the same for the frames outside the grid
+    int4 *every_m;
+    uint32_t *tx_mark;  // [n] stamp of the last query in which the node was the source of a live frame
+    uint32_t stamp;     // this query's stamp (never 0)
+    float half, inv;    // cell = int((x + half) * inv)
+};
+
 // A BATCH of SINR ticks whose frames outlive their tick (rm_airbatch.hip; BASELINE configs[4]).  The frames the batch can
 // see -- the window of frames still on the air from earlier calls, then the batch's ticks one after the other -- are ONE
 // array, cut into time slots (a window batch or a tick each).  The heard links of all ticks come from the sweep of the medium
@@ -653,6 +671,8 @@ hipError_t launch_tick_frames(hipStream_t s, const NodesDev &nd, const ModelDev 
                               int seg_len, const ScanDev *scan = nullptr);
 // (rm_airscan.hip) second launch of the SINR medium's lone tick by scan: interference sums, sinr and verdicts of the new frames' heard links
 hipError_t launch_sinr_scan(hipStream_t s, const NodesDev &nd, const ModelDev &m, const TickDev &t, const ScanDev &sd, const LaunchCfg &cfg);
+hipError_t launch_energy(hipStream_t s, const NodesDev &nd, const ModelDev &m, const rm_tx_record *win, int n_win, int64_t t, const EnergyDev &ed,
+                         bool grid, const int32_t *nodes, int n, int channel, double cca_threshold, double *out_energy, uint8_t *out_flags); // (rm_energy.hip)
 hipError_t launch_air_expire(hipStream_t s, rm_tx_record *recs, int n, int64_t t_seen); // (the on-air window when the clock goes back)
 hipError_t launch_tick_frames_batch(hipStream_t s, const NodesDev &nd, const ModelDev &m, const TickDev *ticks, int n,
                                     const TickDev *dev_ticks, const LaunchCfg &cfg, int seg_len);

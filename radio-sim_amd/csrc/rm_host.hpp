@@ -332,6 +332,16 @@ struct rm_context : TickSlot {
         bool h_flag_used[2] = {false, false};
         uint64_t batches = 0, ticks_done = 0, last_frames = 0;
     } ov;
+    // the channel energy query (rm_api_energy.cpp, rm_energy.hip): its index of the live frames, built from scratch per query, the
+    // nodes' transmitting stamps, and the host form's pinned, host-mapped block (node list in, energies and flags out)
+    struct Energy {
+        DevBuf<uint32_t> cnt, tx_mark;
+        DevBuf<float4> bucket_f, every_f;
+        DevBuf<int4> bucket_m, every_m;
+        uint32_t stamp = 0;
+        char *h_block = nullptr;
+        size_t h_cap = 0; // nodes the block has room for
+    } ed;
     bool dev_records_from_caller = false; // the tick being prepared takes rm_tx_record arrays the caller built in device memory
     mutable rm::ModelDev mdev{};            // model_dev()'s last answer and what it was derived from
     mutable unsigned char mdev_key[320] = {};

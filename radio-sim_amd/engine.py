@@ -590,6 +590,27 @@ class Engine:
         check(self._L.rm_node_info_changed(self._h, nodes.ctypes.data, rssi.ctypes.data, rx.ctypes.data, ch.ctypes.data, n, C.byref(k)))
         return nodes[:k.value], rssi[:k.value], rx[:k.value], ch[:k.value]
 
+    def channel_energy(self, time_us, nodes=None, channel=None, cca_threshold_dbm=float("nan")):
+        """(energy in dBm, flags) per node -- all nodes, or the listed ones -- at `time_us`, over the frames on the air of the SINR
+        medium; channel None: every node on its own channel.  flags: ED_TRANSMITTING | ED_BUSY."""
+        if nodes is not None:
+            nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+            n = len(nodes)
+        else:
+            n = self._L.rm_node_count(self._h)
+        energy = np.empty(n, dtype=np.float64)
+        flags = np.empty(n, dtype=np.uint8)
+        check(self._L.rm_channel_energy(self._h, int(time_us), nodes.ctypes.data if nodes is not None else None, n,
+                                        _lib.CHANNEL_OWN if channel is None else int(channel), float(cca_threshold_dbm),
+                                        energy.ctypes.data, flags.ctypes.data))
+        return energy, flags
+
+    def channel_energy_device(self, time_us, dev_nodes_ptr, n, channel, cca_threshold_dbm, dev_energy_ptr, dev_flags_ptr):
+        """The raw form: device pointers, asynchronous on the context's stream (dev_nodes_ptr None: nodes 0 .. n-1)."""
+        check(self._L.rm_channel_energy_device(self._h, int(time_us), dev_nodes_ptr, int(n),
+                                               _lib.CHANNEL_OWN if channel is None else int(channel), float(cca_threshold_dbm),
+                                               dev_energy_ptr, dev_flags_ptr))
+
     def sync(self):
         check(self._L.rm_sync(self._h))
 

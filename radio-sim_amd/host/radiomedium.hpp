@@ -33,6 +33,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <deque>
@@ -567,6 +568,7 @@ protected:
         if (rm_set_model(ctx_, &params_) != RM_OK) throw std::invalid_argument(rm_last_error());
     }
     rm_context *ctx_ = nullptr;
+    bool syncNodes() { return !simulator || sync(simulator, simulator->getNodes()); } // the device mirrors the node table first
 
 private:
     bool sync(Simulator *sim, const std::vector<Node *> &nodes)
@@ -677,6 +679,31 @@ public:
     {
         params_.flags = on ? (params_.flags | RM_LD_SINR) : (params_.flags & ~RM_LD_SINR);
         apply();
+    }
+    // Clear-channel assessment / energy detection over the frames on the air (extension E5; needs setSinr(true)): the power in
+    // dBm that `node` sees on its own channel at time_us -- the noise level when nothing counts; NaN and lastError on a refusal.
+    // Transciever::getRSSI stays the reference's latched value.
+    double getChannelEnergy(const Node &node, int64_t time_us)
+    {
+        double energy = std::nan("");
+        const int32_t j = node.index;
+        if (!syncNodes() || rm_channel_energy(ctx_, time_us, &j, 1, RM_CHANNEL_OWN, std::nan(""), &energy, nullptr) != RM_OK) {
+            if (lastError.empty() || rm_last_error()[0]) lastError = rm_last_error();
+            return std::nan("");
+        }
+        return energy;
+    }
+    // clear: the energy on the node's channel is below threshold_dbm (a refusal is not clear)
+    bool isChannelClear(const Node &node, int64_t time_us, double threshold_dbm)
+    {
+        double energy = 0.0;
+        uint8_t flags = 0;
+        const int32_t j = node.index;
+        if (!syncNodes() || rm_channel_energy(ctx_, time_us, &j, 1, RM_CHANNEL_OWN, threshold_dbm, &energy, &flags) != RM_OK) {
+            if (lastError.empty() || rm_last_error()[0]) lastError = rm_last_error();
+            return false;
+        }
+        return (flags & RM_ED_BUSY) == 0;
     }
 };
 
