@@ -461,6 +461,42 @@ int rm_channel_energy_device(rm_context *ctx, int64_t time_us, const int32_t *de
 int rm_channel_energy(rm_context *ctx, int64_t time_us, const int32_t *nodes, int32_t n, int32_t channel,
                       double cca_threshold_dbm, double *energy_dbm, uint8_t *flags /* may be NULL */);
 
+/* ---- carrier-sense gated tick: candidates that find the channel busy defer, on the device --------------------
+ * Listen before talk in one call (not reference behaviour).  A gated tick has candidates src[0..n)
+ * (node indices, -1 = padding), one start_us and one air_us (as rm_tick_run_sources_device), a sample time cca_time_us and a
+ * threshold cca_threshold_dbm.
+ *  - For candidate i with src[i] = j >= 0, (energy_i, flags_i) is exactly the channel energy query above for node j at
+ *    t = cca_time_us on j's own channel with that threshold, over the on-air window as it is when the tick begins: after the
+ *    frames that had left the air by t_begin_us are gone and BEFORE any frame of this call joins it.  Candidates of one call
+ *    never defer each other: they all start at the same instant, after the sample.
+ *  - Candidate i is deferred iff flags_i != 0: RM_ED_BUSY (energy >= threshold) or RM_ED_TRANSMITTING (a frame of j's own
+ *    spans cca_time_us: a radio cannot start a second frame).  A NaN threshold never sets BUSY: then only TRANSMITTING defers.
+ *  - A deferred candidate becomes a padding record in its slot (what src = -1 means).  The tick is then, bit for bit, what
+ *    rm_tick_run_sources_device gives for the list with those entries replaced by -1: packet numbers keep their positions, a
+ *    deferred packet has an empty segment in pkt_offset, does not join the on-air window as a live frame, consumes no
+ *    java.util.Random draw, and with the reception stage on it counts as a packet number but queues nothing.
+ *  - Padding on input stays padding, with flags 0 and NaN energy.  The node's enabled / rxprob / txprob play no part in the
+ *    sensing.
+ * Refused before anything is launched, with nothing changed: RM_ERR_STATE under every condition under which
+ * rm_channel_energy returns it (not RM_MODEL_LOGDIST with RM_LD_SINR, between rm_tick_begin and rm_tick_flush, a receiver
+ * partition, a window selected for a region); RM_ERR_INVALID unless t_begin_us <= cca_time_us <= start_us (a sample may not
+ * look back behind the latest t_begin of the window, and a sample after the start would have to see the call's own frames), and
+ * for a host list entry outside -1 .. n_nodes-1 -- in a device list such an entry is treated as padding.
+ * The caller's list is not written: the gated list lives in a buffer of the context.
+ * The device form is asynchronous and deferral is padding -- no count comes back to the host -- so a host may issue many gated
+ * lone ticks back to back without waiting.  Batches are not gated: in a batch of self-contained ticks nothing of an earlier
+ * tick is on the air by contract, and in a batch of overlapping ticks tick b's gate would need tick b-1's gate result, a
+ * serial chain.  One sample time per call: a sample time per candidate (the records forms) needs per-node span information
+ * that the per-query RM_ED_TRANSMITTING stamp does not carry. */
+/* asynchronous on the context's stream; all pointers device memory; outputs may be NULL */
+int rm_tick_run_sources_cca_device(rm_context *ctx, int64_t t_begin_us, int64_t t_end_us, const int32_t *dev_src, int32_t n,
+                                   int64_t start_us, int64_t air_us, int64_t cca_time_us, double cca_threshold_dbm,
+                                   uint8_t *dev_cca_flags /* [n] RM_ED_* */, double *dev_cca_energy_dbm /* [n] */);
+/* host arrays in and out (outputs may be NULL); evaluates the tick, synchronises for the flags; results through rm_result_* as
+ * after rm_tick_run_sources_device */
+int rm_tick_run_sources_cca(rm_context *ctx, int64_t t_begin_us, int64_t t_end_us, const int32_t *src, int32_t n, int64_t start_us,
+                            int64_t air_us, int64_t cca_time_us, double cca_threshold_dbm, uint8_t *cca_flags, double *cca_energy_dbm);
+
 /* ---- several devices behind one caller --------------------------------------------------------------
  * The reference host is ONE process (Main.java:65-73): a group drives n contexts from one host thread, one
  * per device (an ordinal may repeat: several partitions on one GPU).  Receivers are partitioned over the

@@ -319,7 +319,7 @@ void rm_destroy(rm_context *c)
         }
         if (o.h_flag) (void)hipHostFree(o.h_flag);
     }
-    c->ed.cnt.release(); c->ed.tx_mark.release(); c->ed.bucket_f.release(); c->ed.every_f.release(); c->ed.bucket_m.release(); c->ed.every_m.release();
+    c->ed.cnt.release(); c->ed.tx_mark.release(); c->ed.bucket_f.release(); c->ed.every_f.release(); c->ed.bucket_m.release(); c->ed.every_m.release(); c->ed.gated.release();
     if (c->ed.h_block) (void)hipHostFree(c->ed.h_block);
     c->ed.h_block = nullptr;
     c->d_patch.release();

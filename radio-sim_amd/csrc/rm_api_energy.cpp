@@ -7,7 +7,7 @@
 
 using namespace rmh;
 
-namespace {
+namespace rmh {
 
 // what both forms refuse, before anything is launched
 int energy_check(rm_context *c, int64_t time_us, int32_t n, bool have_list)
@@ -27,9 +27,9 @@ int energy_check(rm_context *c, int64_t time_us, int32_t n, bool have_list)
     return RM_OK;
 }
 
-// index + sum on the context's stream; nodes / energy / flags are device-visible memory
+// index + sum (or, with `gated`, index + gate) on the context's stream; nodes / energy / flags are device-visible memory
 int energy_launch(rm_context *c, int64_t time_us, const int32_t *nodes, int32_t n, int32_t channel, double cca_threshold, double *energy,
-                  uint8_t *flags)
+                  uint8_t *flags, int32_t *gated)
 {
     RM_TRY(prepare_nodes(c)); // pending node changes first, as a tick does
     if (c->n_rx != c->n) return fail(RM_ERR_STATE, "internal: the receiver table does not hold every node");
@@ -72,12 +72,36 @@ int energy_launch(rm_context *c, int64_t time_us, const int32_t *nodes, int32_t 
     ProbeScope probe(c);
     c->tick_index = tick_index;
     sample_stage(probe.smp, RM_STAGE_SINR);
-    RM_HIP(rm::launch_energy(c->stream, nodes_dev(c), m, c->d_air.p + c->air_head, int(n_win), time_us, ed, grid, nodes, n, channel,
-                             cca_threshold, energy, flags));
+    if (gated)
+        RM_HIP(rm::launch_cca_gate(c->stream, nodes_dev(c), m, c->d_air.p + c->air_head, int(n_win), time_us, ed, grid, nodes, n, cca_threshold,
+                                   gated, energy, flags));
+    else
+        RM_HIP(rm::launch_energy(c->stream, nodes_dev(c), m, c->d_air.p + c->air_head, int(n_win), time_us, ed, grid, nodes, n, channel,
+                                 cca_threshold, energy, flags));
     return RM_OK;
 }
 
-} // namespace
+// one pinned, host-mapped block: the list in, energies and flags out -- the kernels read and write it in place (a lock-stepped
+// host asks for a few hundred nodes per tick: one small launch sequence and one synchronisation, no copy engine in between)
+int energy_host_block(rm_context *c, int32_t n, double **h_energy, int32_t **h_nodes, uint8_t **h_flags)
+{
+    rm_context::Energy &e = c->ed;
+    if (e.h_cap < size_t(n)) {
+        RM_HIP(hipStreamSynchronize(c->stream));
+        if (e.h_block) RM_HIP(hipHostFree(e.h_block));
+        e.h_block = nullptr;
+        e.h_cap = 0;
+        const size_t want = std::max<size_t>(size_t(n) + size_t(n) / 2, 1024);
+        RM_HIP(hipHostMalloc(reinterpret_cast<void **>(&e.h_block), pad64(want * 8) + pad64(want * 4) + pad64(want), hipHostMallocMapped));
+        e.h_cap = want;
+    }
+    *h_energy = reinterpret_cast<double *>(e.h_block);
+    *h_nodes = reinterpret_cast<int32_t *>(e.h_block + pad64(e.h_cap * 8));
+    *h_flags = reinterpret_cast<uint8_t *>(e.h_block + pad64(e.h_cap * 8) + pad64(e.h_cap * 4));
+    return RM_OK;
+}
+
+} // namespace rmh
 
 extern "C" {
 
@@ -101,21 +125,10 @@ int rm_channel_energy(rm_context *c, int64_t time_us, const int32_t *nodes, int3
         for (int32_t k = 0; k < n; ++k)
             if (nodes[k] < 0 || nodes[k] >= c->n) return fail(RM_ERR_INVALID, "node index out of range");
     RM_HIP(hipSetDevice(c->device));
-    // one pinned, host-mapped block: the list in, energies and flags out -- the kernels read and write it in place (a lock-stepped
-    // host asks for a few hundred nodes per tick: one small launch sequence and one synchronisation, no copy engine in between)
-    rm_context::Energy &e = c->ed;
-    if (e.h_cap < size_t(n)) {
-        RM_HIP(hipStreamSynchronize(c->stream));
-        if (e.h_block) RM_HIP(hipHostFree(e.h_block));
-        e.h_block = nullptr;
-        e.h_cap = 0;
-        const size_t want = std::max<size_t>(size_t(n) + size_t(n) / 2, 1024);
-        RM_HIP(hipHostMalloc(reinterpret_cast<void **>(&e.h_block), pad64(want * 8) + pad64(want * 4) + pad64(want), hipHostMallocMapped));
-        e.h_cap = want;
-    }
-    double *h_energy = reinterpret_cast<double *>(e.h_block);
-    int32_t *h_nodes = reinterpret_cast<int32_t *>(e.h_block + pad64(e.h_cap * 8));
-    uint8_t *h_flags = reinterpret_cast<uint8_t *>(e.h_block + pad64(e.h_cap * 8) + pad64(e.h_cap * 4));
+    double *h_energy;
+    int32_t *h_nodes;
+    uint8_t *h_flags;
+    RM_TRY(energy_host_block(c, n, &h_energy, &h_nodes, &h_flags));
     if (nodes) std::memcpy(h_nodes, nodes, size_t(n) * 4);
     RM_TRY(energy_launch(c, time_us, nodes ? h_nodes : nullptr, n, channel, cca_threshold_dbm, h_energy, h_flags));
     RM_HIP(hipStreamSynchronize(c->stream));

@@ -19,6 +19,7 @@
 //                    medium's link-hash table); the survivors of a wave are gathered in LDS and evaluated with full lanes
 //                    -- logdist_rssi in fp64, det_pow10, Q80 -- and added to their node's sum in LDS (integer adds: the
 //                    order does not matter).
+//   k_cca_gate       the gate of a carrier-sense gated tick (E6; further down): the same index, one WAVE per candidate.
 // The conservative tests only ever drop work: a frame that counts (E5) always reaches the exact evaluation, whatever the
 // grid, the lists' order or the path.
 #include "rm_device.hpp"
@@ -35,6 +36,28 @@ RM_D void ed_add_u128(unsigned long long *acc /*[2]: lo, hi*/, const U128 v)
     const unsigned long long old = atomicAdd(&acc[0], (unsigned long long)v.lo);
     const unsigned long long carry = (old + v.lo < old) ? 1ull : 0ull; // (the low words' running sum is exact mod 2^64: so is the carry count)
     if (v.hi + carry) atomicAdd(&acc[1], (unsigned long long)(v.hi + carry));
+}
+
+// The sweep's conservative tests for one (node, frame) pair, shared by the query (k_energy_sum) and the gate (k_cca_gate): same
+// channel, not the node's own frame (RM_ED_TRANSMITTING says that it is sending), fp32 distance against the squared cut-off (which
+// carries the fp32 frame's slack), the shadowed medium's link-hash table (tbl: its kShadowBins words, staged in LDS).  A node
+// outside the frame the fp32 slack was computed for (`wide`) takes every co-channel frame as a candidate.
+struct EdNode {
+    bool valid, wide, shadow;
+    int ch, j;
+    float px, py, pz; // position in the fp32 frame
+};
+RM_D bool ed_candidate(const ModelDev &m, const uint32_t *tbl, const EdNode &nv, const float4 &f, const int4 &fm)
+{
+    if (!(nv.valid && fm.x == nv.ch && fm.z != nv.j)) return false;
+    if (nv.wide) return true;
+    const float s2 = dist2_f32(nv.px - f.x, nv.py - f.y, nv.pz - f.z);
+    if (!(s2 <= f.w)) return false;
+    if (!nv.shadow) return true;
+    const int bin = min(kShadowBins - 1, int(s2 * __int_as_float(fm.w)));
+    const uint32_t a = uint32_t(fm.z), b = uint32_t(nv.j);
+    const uint64_t key = (uint64_t(a < b ? a : b) << 32) | uint64_t(a < b ? b : a);
+    return uint32_t(mix64(m.ld_seed_mixed ^ key) >> 32) <= tbl[bin];
 }
 
 template <bool GRID>
@@ -116,6 +139,7 @@ __global__ void __launch_bounds__(256) k_energy_sum(const NodesDev nd, const Mod
     const float px = float(rx_), py = float(ry_), pz = float(rz_);
     // a node outside the frame the fp32 slack was computed for takes every co-channel frame as a candidate
     const bool wide = !(fabs(rx_) <= m.coord_bound && fabs(ry_) <= m.coord_bound && fabs(rz_) <= m.coord_bound);
+    const EdNode nv{valid, wide, shadow, ch, j, px, py, pz};
     s_x[tid] = x;
     s_y[tid] = y;
     s_z[tid] = z;
@@ -147,19 +171,7 @@ __global__ void __launch_bounds__(256) k_energy_sum(const NodesDev nd, const Mod
         }
         np += cnt;
     };
-    // the sweep's conservative tests: same channel, not the node's own frame (RM_ED_TRANSMITTING says that it is sending), fp32
-    // distance against the squared cut-off (which carries the fp32 frame's slack), the shadowed medium's link-hash table
-    auto candidate = [&](const float4 &f, const int4 &fm) -> bool {
-        if (!(valid && fm.x == ch && fm.z != j)) return false;
-        if (wide) return true;
-        const float s2 = dist2_f32(px - f.x, py - f.y, pz - f.z);
-        if (!(s2 <= f.w)) return false;
-        if (!shadow) return true;
-        const int bin = min(kShadowBins - 1, int(s2 * __int_as_float(fm.w)));
-        const uint32_t a = uint32_t(fm.z), b = uint32_t(j);
-        const uint64_t key = (uint64_t(a < b ? a : b) << 32) | uint64_t(a < b ? b : a);
-        return uint32_t(mix64(m.ld_seed_mixed ^ key) >> 32) <= s_tbl[bin];
-    };
+    auto candidate = [&](const float4 &f, const int4 &fm) -> bool { return ed_candidate(m, s_tbl, nv, f, fm); };
 
     if (GRID) {
         // the cells that can hold a frame within reach: |dx| <= (largest radius), and positions map to cells monotonically
@@ -244,6 +256,131 @@ hipError_t launch_energy(hipStream_t s, const NodesDev &nd, const ModelDev &m, c
     if (n <= 0) return hipGetLastError();
     if (grid) RM_KLAUNCH((k_energy_sum<true>), dim3(cdiv(n, kBlock)), dim3(kBlock), 0, s, nd, m, win, ed, nodes, n, channel, cca_threshold, out_energy, out_flags);
     else RM_KLAUNCH((k_energy_sum<false>), dim3(cdiv(n, kBlock)), dim3(kBlock), 0, s, nd, m, win, ed, nodes, n, channel, cca_threshold, out_energy, out_flags);
+    return hipGetLastError();
+}
+
+// ---- the gate of a carrier-sense gated tick (rm_tick_run_sources_cca*) ----------------------------------
+// One WAVE per candidate transmitter.  The query's list form gives every lane a scattered node of its own, and the lane walks its
+// cells one dependent memory round trip after the other; here the lanes of a wave share one node: they read the counts of the cells
+// in reach together (one lane per cell), a wave prefix turns the counts into one flat range of entries, and the lanes stride over
+// that range and then over the EVERY list.  A lane evaluates its survivors where it stands (fp64, Q80) into a 128-bit partial sum
+// of its own; the wave adds the partial sums as integers -- 32-bit limbs, each summed in 64 bits across the lanes, carries
+// propagated once at the end -- so that the order cannot matter.  Lane 0 forms the energy and the flags and writes the gated
+// source: the candidate itself when the channel is clear, -1 (a padding record: make_tx_record) when it defers.
+RM_D unsigned long long wave_sum_u64(unsigned long long v)
+{
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+template <bool GRID>
+__global__ void __launch_bounds__(256) k_cca_gate(const NodesDev nd, const ModelDev m, const rm_tx_record *win, const EnergyDev ed,
+                                                   const int32_t *src, int n, double cca_threshold, int32_t *gated, double *out_energy,
+                                                   uint8_t *out_flags)
+{
+    __shared__ uint32_t s_tbl[kShadowBins];
+    __shared__ int s_off[kWavesPerBlock][65]; // a wave's cells of one round: first entry of each in the flat range ...
+    __shared__ int s_cell[kWavesPerBlock][64]; // ... and which cell it is
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = wave_index();
+    const bool shadow = m.shadow_tbl != nullptr;
+    s_tbl[tid] = shadow ? m.shadow_tbl[tid] : 0xFFFFFFFFu;
+    __syncthreads(); // (the table; the waves go their own ways from here)
+    const int i = blockIdx.x * kWavesPerBlock + wave; // wave-uniform
+    if (i >= n) return;
+    const int j = uniform_i(src[i]);
+    if (!(j >= 0 && j < nd.n)) { // padding stays padding
+        if (lane == 0) {
+            gated[i] = -1;
+            if (out_energy) out_energy[i] = __builtin_nan("");
+            if (out_flags) out_flags[i] = 0;
+        }
+        return;
+    }
+    const SrcRecord sr = nd.srec[j];
+    const double rx_ = sr.x - m.org_x, ry_ = sr.y - m.org_y, rz_ = sr.z - m.org_z;
+    const float px = float(rx_), py = float(ry_), pz = float(rz_);
+    const bool wide = !(fabs(rx_) <= m.coord_bound && fabs(ry_) <= m.coord_bound && fabs(rz_) <= m.coord_bound);
+    const EdNode nv{true, wide, shadow, sr.channel, j, px, py, pz};
+
+    U128 acc = {0ull, 0ull};
+    auto look = [&](const float4 &f, const int4 &fm) {
+        if (!ed_candidate(m, s_tbl, nv, f, fm)) return;
+        const double rssi = logdist_rssi(m, win[fm.y], sr.x, sr.y, sr.z, j);
+        if (rssi >= m.ld_ifloor) acc = u128_add(acc, q80_from_double(det_pow10(rssi / 10.0)));
+    };
+
+    if (GRID) {
+        // the cells that can hold a frame within reach (as the query: |dx| <= largest radius, positions map to cells monotonically)
+        const float rmax = __uint_as_float(ed.cnt[1]);
+        const float reach = rmax * (1.0f + 2e-5f) + 1e-3f / ed.inv;
+        int cx0 = 0, cy0 = 0, cx1 = kEdG - 1, cy1 = kEdG - 1;
+        if (!wide) {
+            cx0 = sg_cell1(px - reach, ed.half, ed.inv);
+            cx1 = sg_cell1(px + reach, ed.half, ed.inv);
+            cy0 = sg_cell1(py - reach, ed.half, ed.inv);
+            cy1 = sg_cell1(py + reach, ed.half, ed.inv);
+        }
+        cx0 = uniform_i(cx0), cx1 = uniform_i(cx1), cy0 = uniform_i(cy0), cy1 = uniform_i(cy1);
+        const int ncx = cx1 - cx0 + 1, ncells = ncx * (cy1 - cy0 + 1);
+        for (int c0 = 0; c0 < ncells; c0 += 64) { // wave-uniform; one round for a node inside the frame with the usual reach
+            const int c = c0 + lane;
+            int cell = 0, cnt = 0;
+            if (c < ncells) {
+                cell = (cy0 + c / ncx) * kEdG + cx0 + c % ncx;
+                cnt = int(min(ed.cnt[2 + cell], uint32_t(kEdK))); // first round trip: every cell's count at once
+            }
+            int incl = cnt; // inclusive prefix over the wave
+            for (int d = 1; d < 64; d <<= 1) {
+                const int up = __shfl_up(incl, d);
+                if (lane >= d) incl += up;
+            }
+            const int total = uniform_i(__shfl(incl, 63));
+            if (total == 0) continue;
+            s_off[wave][lane] = incl - cnt;
+            s_cell[wave][lane] = cell;
+            if (lane == 63) s_off[wave][64] = total;
+            __builtin_amdgcn_wave_barrier(); // (LDS traffic of one wave is in order; the compiler must not move it either)
+            for (int e = lane; e < total; e += 64) { // second round trip: the entries, whichever cell they are in
+                int lo = 0;                              // the last cell whose first entry is <= e (empty cells before it share its offset)
+                for (int step = 32; step > 0; step >>= 1)
+                    if (s_off[wave][lo + step] <= e) lo += step;
+                const int at = s_cell[wave][lo] * kEdK + (e - s_off[wave][lo]);
+                look(ed.bucket_f[at], ed.bucket_m[at]);
+            }
+            __builtin_amdgcn_wave_barrier(); // (the next round rewrites the offsets)
+        }
+    }
+    const int n_every = uniform_i(int(ed.cnt[0]));
+    for (int e = lane; e < n_every; e += 64) look(ed.every_f[e], ed.every_m[e]);
+
+    // the wave's sum: four 32-bit limbs, each added across the lanes in 64 bits (64 x 2^32 fits easily), carries once
+    const unsigned long long l0 = wave_sum_u64(acc.lo & 0xFFFFFFFFull), l1 = wave_sum_u64(acc.lo >> 32);
+    const unsigned long long l2 = wave_sum_u64(acc.hi & 0xFFFFFFFFull), l3 = wave_sum_u64(acc.hi >> 32);
+    if (lane != 0) return;
+    U128 sum, part;
+    sum.lo = l0, sum.hi = l2;
+    part.lo = l1 << 32, part.hi = (l1 >> 32) + (l3 << 32); // (mod 2^128, as the query's sums)
+    sum = u128_add(sum, part);
+    const double energy = 10.0 * det_log10(q80_to_double(sum) + m.ld_noise_lin);
+    uint32_t flags = 0u;
+    if (ed.tx_mark[j] == ed.stamp) flags |= uint32_t(RM_ED_TRANSMITTING);
+    if (energy >= cca_threshold) flags |= uint32_t(RM_ED_BUSY); // (a NaN threshold never sets it)
+    gated[i] = flags ? -1 : j;
+    if (out_energy) out_energy[i] = energy;
+    if (out_flags) out_flags[i] = uint8_t(flags);
+}
+
+hipError_t launch_cca_gate(hipStream_t s, const NodesDev &nd, const ModelDev &m, const rm_tx_record *win, int n_win, int64_t t, const EnergyDev &ed,
+                           bool grid, const int32_t *src, int n, double cca_threshold, int32_t *gated, double *out_energy, uint8_t *out_flags)
+{
+    if (n_win > 0) {
+        if (grid) RM_KLAUNCH((k_energy_index<true>), dim3(cdiv(n_win, 256)), dim3(256), 0, s, m, win, n_win, nd.n, t, ed);
+        else RM_KLAUNCH((k_energy_index<false>), dim3(cdiv(n_win, 256)), dim3(256), 0, s, m, win, n_win, nd.n, t, ed);
+    }
+    if (n <= 0) return hipGetLastError();
+    if (grid) RM_KLAUNCH((k_cca_gate<true>), dim3(cdiv(n, kWavesPerBlock)), dim3(kBlock), 0, s, nd, m, win, ed, src, n, cca_threshold, gated, out_energy, out_flags);
+    else RM_KLAUNCH((k_cca_gate<false>), dim3(cdiv(n, kWavesPerBlock)), dim3(kBlock), 0, s, nd, m, win, ed, src, n, cca_threshold, gated, out_energy, out_flags);
     return hipGetLastError();
 }
 

@@ -673,6 +673,9 @@ hipError_t launch_tick_frames(hipStream_t s, const NodesDev &nd, const ModelDev 
 hipError_t launch_sinr_scan(hipStream_t s, const NodesDev &nd, const ModelDev &m, const TickDev &t, const ScanDev &sd, const LaunchCfg &cfg);
 hipError_t launch_energy(hipStream_t s, const NodesDev &nd, const ModelDev &m, const rm_tx_record *win, int n_win, int64_t t, const EnergyDev &ed,
                          bool grid, const int32_t *nodes, int n, int channel, double cca_threshold, double *out_energy, uint8_t *out_flags); // (rm_energy.hip)
+// the gate of a carrier-sense gated tick: the query's index at time t, then one wave per candidate src[i] -> gated[i] = src[i] or -1
+hipError_t launch_cca_gate(hipStream_t s, const NodesDev &nd, const ModelDev &m, const rm_tx_record *win, int n_win, int64_t t, const EnergyDev &ed,
+                           bool grid, const int32_t *src, int n, double cca_threshold, int32_t *gated, double *out_energy, uint8_t *out_flags);
 hipError_t launch_air_expire(hipStream_t s, rm_tx_record *recs, int n, int64_t t_seen); // (the on-air window when the clock goes back)
 hipError_t launch_tick_frames_batch(hipStream_t s, const NodesDev &nd, const ModelDev &m, const TickDev *ticks, int n,
                                     const TickDev *dev_ticks, const LaunchCfg &cfg, int seg_len);

@@ -336,6 +336,7 @@ struct rm_context : TickSlot {
     // nodes' transmitting stamps, and the host form's pinned, host-mapped block (node list in, energies and flags out)
     struct Energy {
         DevBuf<uint32_t> cnt, tx_mark;
+        DevBuf<int32_t> gated; // a gated tick's source list after the gate (rm_api_cca.cpp): the caller's list is never written
         DevBuf<float4> bucket_f, every_f;
         DevBuf<int4> bucket_m, every_m;
         uint32_t stamp = 0;
@@ -548,6 +549,16 @@ int air_window_expire(rm_context *c, int64_t t_begin_us);
 int air_window_reserve(rm_context *c, size_t n_more);
 int result_device(rm_context *c, TickSlot &ts, rm_device_result *out);
 int result_count(rm_context *c, TickSlot &ts, uint32_t *count, uint32_t *dropped);
+
+// ---- rm_api_energy.cpp
+// what the channel energy query refuses before anything is launched (the gated tick refuses the same)
+int energy_check(rm_context *c, int64_t time_us, int32_t n, bool have_list);
+// the query's index of the frames live at time_us, then the sum over `nodes` -- or, with `gated`, the gate of a gated tick over the
+// candidates `nodes` (rm_energy.hip) -- on the context's stream; nodes / energy / flags are device-visible memory
+int energy_launch(rm_context *c, int64_t time_us, const int32_t *nodes, int32_t n, int32_t channel, double cca_threshold, double *energy,
+                  uint8_t *flags, int32_t *gated = nullptr);
+// the host forms' pinned, host-mapped block with room for n nodes: energies, node list, flags
+int energy_host_block(rm_context *c, int32_t n, double **h_energy, int32_t **h_nodes, uint8_t **h_flags);
 
 // ---- rm_api_comm.cpp
 int comm_all_gather(rm_context *c, const void *mine, void *all, size_t bytes);

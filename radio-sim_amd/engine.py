@@ -611,6 +611,24 @@ class Engine:
                                                _lib.CHANNEL_OWN if channel is None else int(channel), float(cca_threshold_dbm),
                                                dev_energy_ptr, dev_flags_ptr))
 
+    def tick_run_sources_cca(self, t_begin, t_end, src, start_us, air_us, cca_time_us, cca_threshold_dbm=float("nan")):
+        """A carrier-sense gated tick: the candidates `src` (node indices, -1 = padding) are sensed at
+        `cca_time_us` on the device and only the ones with flags 0 go on the air.  -> (flags, energy in dBm) per candidate; the
+        tick's results through result_copy(len(src)) as after tick_run_sources_device."""
+        src = np.ascontiguousarray(src, dtype=np.int32)
+        n = len(src)
+        flags = np.empty(n, dtype=np.uint8)
+        energy = np.empty(n, dtype=np.float64)
+        check(self._L.rm_tick_run_sources_cca(self._h, int(t_begin), int(t_end), src.ctypes.data, n, int(start_us), int(air_us),
+                                              int(cca_time_us), float(cca_threshold_dbm), flags.ctypes.data, energy.ctypes.data))
+        return flags, energy
+
+    def tick_run_sources_cca_device(self, t_begin, t_end, dev_src_ptr, n, start_us, air_us, cca_time_us, cca_threshold_dbm,
+                                    dev_flags_ptr=None, dev_energy_ptr=None):
+        """The raw form: device pointers, asynchronous on the context's stream; the caller's list is not written."""
+        check(self._L.rm_tick_run_sources_cca_device(self._h, int(t_begin), int(t_end), dev_src_ptr, int(n), int(start_us), int(air_us),
+                                                     int(cca_time_us), float(cca_threshold_dbm), dev_flags_ptr, dev_energy_ptr))
+
     def sync(self):
         check(self._L.rm_sync(self._h))
 

@@ -705,6 +705,58 @@ public:
         }
         return (flags & RM_ED_BUSY) == 0;
     }
+    // Listen before talk for several nodes at once (extension E6; needs setSinr(true)): every listed node wants to send one packet
+    // of hex_length characters starting at start_us; each senses its own channel at cca_time_us (<= start_us) on the device, and
+    // only the ones that find it clear -- and are not on the air themselves -- transmit.  Returns the nodes' flags (0: sent,
+    // else RM_ED_BUSY | RM_ED_TRANSMITTING: deferred); an empty vector and lastError on a refusal.  A sent packet generates its
+    // events as transmit() does, a deferred one generates none.  The packets belong to the medium (sentIfClear()).  The medium's
+    // own call order, not for the tick mode or the reception stage on the device.
+    std::vector<uint8_t> transmitIfClear(const std::vector<Node *> &senders, int64_t start_us, int64_t hex_length, int64_t cca_time_us,
+                                         double threshold_dbm)
+    {
+        lastError.clear();
+        Simulator *sim = simulator;
+        if (!sim) { lastError = "No simulator"; return {}; }
+        if (!syncNodes()) return {};
+        const std::vector<Node *> &nodes = sim->getNodes();
+        rm_set_time(ctx_, sim->getTime());
+        const int32_t n = int32_t(senders.size());
+        std::vector<int32_t> src(senders.size());
+        for (size_t i = 0; i < senders.size(); ++i) src[i] = senders[i] ? senders[i]->index : -1;
+        std::vector<uint8_t> flags(senders.size(), 0);
+        if (rm_tick_run_sources_cca(ctx_, cca_time_us, start_us, src.data(), n, start_us, rm_air_time_us(hex_length), cca_time_us,
+                                    threshold_dbm, flags.data(), nullptr) != RM_OK) {
+            lastError = rm_last_error();
+            return {};
+        }
+        std::vector<uint32_t> off(senders.size() + 1, 0);
+        uint32_t heard = 0;
+        if (ccaDst_.empty()) { ccaDst_.resize(1024); ccaVerdict_.resize(1024); ccaRssi_.resize(1024); }
+        for (int attempt = 0; attempt < 2; ++attempt) { // (the count comes back with the refusal of buffers that are too small)
+            const int rc = rm_result_copy(ctx_, nullptr, ccaDst_.data(), ccaVerdict_.data(), ccaRssi_.data(), nullptr, uint32_t(ccaDst_.size()),
+                                          &heard, nullptr, off.data());
+            if (rc == RM_OK) break;
+            if (attempt == 1 || heard <= ccaDst_.size()) { lastError = rm_last_error(); return {}; }
+            ccaDst_.resize(heard); ccaVerdict_.resize(heard); ccaRssi_.resize(heard);
+        }
+        const std::string data(size_t(hex_length), '0');
+        for (size_t i = 0; i < senders.size(); ++i) {
+            if (src[i] < 0 || flags[i]) continue;
+            ccaSent_.emplace_back(new RadioPacket(senders[i], start_us, data));
+            RadioPacket &packet = *ccaSent_.back();
+            sim->generateTransmissionEvents(packet);
+            for (uint32_t k = off[i]; k < off[i + 1]; ++k)
+                sim->generateReceptionEvents(packet, nodes[size_t(ccaDst_[k])], ccaRssi_[k], ccaVerdict_[k] == RM_DELIVERED);
+        }
+        return flags;
+    }
+    const std::vector<std::unique_ptr<RadioPacket>> &sentIfClear() const { return ccaSent_; }
+
+private:
+    std::vector<std::unique_ptr<RadioPacket>> ccaSent_;
+    std::vector<int32_t> ccaDst_;
+    std::vector<uint8_t> ccaVerdict_;
+    std::vector<double> ccaRssi_;
 };
 
 // The same contract over SEVERAL devices (or several partitions of one device): one rm_group behind one medium
