@@ -43,6 +43,82 @@ bool rank_frames_wanted(rm_context *c)
     return part_count(c) != c->n && part_count(c) > 0;
 }
 
+void nbr_cache_report(rm_context *c)
+{
+    if (!g_clock.on || !c->nc.ctr.p) return;
+    unsigned long long v[3] = {0, 0, 0};
+    if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(v, c->nc.ctr.p, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return;
+    std::fprintf(stderr, "rm source candidate cache: %llu frames served from a list, %llu swept (%.1f %% hits); %llu arena entries of %zu handed out in "
+                         "the last epoch (%u epochs)\n",
+                 v[1], v[2], (v[1] + v[2]) ? 100.0 * double(v[1]) / double(v[1] + v[2]) : 0.0, v[0], c->nc.arena.n, c->nc.epoch);
+}
+
+// The source candidate cache (rm::NbrCacheDev) for the batch in `ticks`, or nothing.  It serves batches whose frames are named
+// by source indices (records built from the node table) over the WHOLE sorted table of a geometric medium without the SINR
+// extension; partitions, gathered batches, caller-supplied records and everything that is not the plain four-stage sequence keep
+// the sweep as it is.
+static int plan_nbr_cache(rm_context *c, rm::TickDev *ticks, const TickPlan *plans, int n)
+{
+    const rm::LaunchCfg &cfg = plans[0].cfg;
+    if (c->n <= 0 || !is_geometric(c) || is_sinr(c) || part_spatial(c) || part_count(c) != c->n || !cfg.sorted || !cfg.bbox || cfg.f64_filter) return RM_OK;
+    int max_cnt = 0;
+    for (int b = 0; b < n; ++b) {
+        const rm::TickDev &t = ticks[b];
+        if (plans[b].sinr || !t.src_list || t.gather_idx || t.gather_src || t.n_pub > 0 || t.first_eval != 0 || t.first_new != 0 || t.cnt_base != 0 ||
+            t.filter_mode != rm::kFilterWg || t.use_matrix || t.air.pool || t.acc_lo || t.reset_heads || t.n_rx != c->n)
+            return RM_OK;
+        max_cnt = std::max(max_cnt, t.n_cnt);
+    }
+    rm_context::NbrCache &nc = c->nc;
+    hipStream_t s = c->stream;
+    const size_t nodes = size_t(c->n);
+    // the arena: 96 entries per node (the bench shape keeps some 50 per source), half a gigabyte at most
+    const size_t arena = std::min<size_t>(nodes * 96, size_t(1) << 27);
+    if (nc.nodes != c->n || !nc.state.p) {
+        RM_HIP(nc.state.ensure(nodes));
+        RM_HIP(nc.off.ensure(nodes));
+        RM_HIP(nc.len.ensure(nodes));
+        RM_HIP(nc.arena.ensure(arena));
+        if (!nc.ctr.p) {
+            RM_HIP(nc.ctr.ensure(3));
+            RM_HIP(hipMemsetAsync(nc.ctr.p, 0, 3 * sizeof(unsigned long long), s));
+        }
+        nc.nodes = c->n;
+        nc.epoch = 0x7FFFFFFFu; // (the state words are zeroed below)
+        nc.seen = 0;
+    }
+    if (nc.seen != nc.change) { // a new epoch: every list is stale
+        nc.seen = nc.change;
+        if (nc.epoch >= 0x7FFFFFFEu) {
+            RM_HIP(hipMemsetAsync(nc.state.p, 0, nc.state.n * sizeof(uint32_t), s));
+            nc.epoch = 0;
+        }
+        nc.epoch++;
+        RM_HIP(hipMemsetAsync(nc.ctr.p, 0, sizeof(unsigned long long), s));
+    }
+    const size_t per = size_t(std::max(max_cnt, 1));
+    RM_HIP(nc.tick_cnt.ensure(size_t(n) * 4));
+    RM_HIP(nc.hit.ensure(size_t(n) * per));
+    RM_HIP(nc.fill.ensure(size_t(n) * per));
+    RM_HIP(nc.cur.ensure(size_t(n) * per));
+    RM_HIP(hipMemsetAsync(nc.tick_cnt.p, 0, size_t(n) * 4 * sizeof(uint32_t), s));
+    for (int b = 0; b < n; ++b) {
+        rm::NbrCacheDev &d = ticks[b].nc;
+        d.state = nc.state.p;
+        d.off = nc.off.p;
+        d.len = nc.len.p;
+        d.arena = nc.arena.p;
+        d.ctr = nc.ctr.p;
+        d.arena_len = uint32_t(arena);
+        d.word = (nc.epoch << 1) | 1u;
+        d.tick_cnt = nc.tick_cnt.p + size_t(b) * 4;
+        d.hit = nc.hit.p + size_t(b) * per;
+        d.fill = nc.fill.p + size_t(b) * per;
+        d.cur = nc.cur.p + size_t(b) * per;
+    }
+    return RM_OK;
+}
+
 int plan_rank_frames(rm_context *c, TickSlot &ts, rm::TickDev &t, int n_pub)
 {
     (void)c;
@@ -92,6 +168,11 @@ int rmh::launch_batch(rm_context *c, TickSlot *const *slots, const TickPlan *pla
             }
         }
     }
+    // RM_BATCH_FRAMES=1: the batch through the one-frame-per-workgroup kernel of the closed-loop tick instead of the
+    // three sweep stages (one launch; the compact arrays on demand, per slot)
+    static const bool batch_frames = std::getenv("RM_BATCH_FRAMES") != nullptr;
+    if (!m_override && !after_sweep && !rank_frames && !batch_frames) RM_TRY(plan_nbr_cache(c, ticks, plans, n));
+    const bool use_nc = ticks[0].nc.state != nullptr;
     // the descriptors go to device memory (k_store_ticks, ordered on the stream after the previous
     // batch's kernels, which read the same array)
     RM_HIP(c->d_ticks.ensure(RM_MAX_BATCH));
@@ -139,11 +220,8 @@ int rmh::launch_batch(rm_context *c, TickSlot *const *slots, const TickPlan *pla
         rf.sweep_level = m.ld_level;
         RM_HIP(rm::launch_rank_frames(s, nd, model_dev(c), dev_ticks, n, max_frames, rf));
     }
-    // RM_BATCH_FRAMES=1: the batch through the one-frame-per-workgroup kernel of the closed-loop tick instead of the
-    // three sweep stages (one launch; the compact arrays on demand, per slot)
-    // (not over a rank's frame list: k_tick_frames_batch writes no offsets by global packet number, which the result readers
+    // (RM_BATCH_FRAMES; not over a rank's frame list: k_tick_frames_batch writes no offsets by global packet number, which the result readers
     // of such a slot take)
-    static const bool batch_frames = std::getenv("RM_BATCH_FRAMES") != nullptr;
     if (batch_frames && !cfg.stochastic && !plans[0].sinr && !after_sweep && !(rank_frames && ticks[0].n_pub > 0)) {
         int seg_len = rm::frame_tick_segment(ticks[0], cfg, m);
         for (int b = 1; b < n && seg_len > 0; ++b) seg_len = std::min(seg_len, rm::frame_tick_segment(ticks[b], cfg, m));
@@ -163,6 +241,7 @@ int rmh::launch_batch(rm_context *c, TickSlot *const *slots, const TickPlan *pla
     RM_TRY(stage(RM_STAGE_FILTER));
     RM_HIP(rm::launch_batch_stage(s, 0, nd, m, ticks, n, dev_ticks, cfg));
     c->last_tile_reuse = rm::filter_ticks_per_wg(ticks[0], n);
+    if (use_nc) RM_HIP(rm::launch_nbr_cache_batch(s, ticks, n, dev_ticks));
     RM_TRY(stage(RM_STAGE_EXACT));
     RM_HIP(rm::launch_batch_stage(s, 1, nd, m, ticks, n, dev_ticks, cfg));
     if (plans[0].sinr && ticks[0].acc_lo == nullptr) { // (the per-receiver lists: SELF entries, then the walks; sums per receiver need neither)

@@ -469,6 +469,17 @@ RM_D void tick_prep_body(const NodesDev &nd, const ModelDev &m, const TickDev &t
     float4 f;
     double thr64;
     tx_prefilter(m, tx, f, thr64);
+    if (t.nc.state != nullptr) { // (block-uniform) the source candidate cache: a frame whose source has a valid list is not swept
+        uint2 h = make_uint2(0u, 0u);
+        if (tx.src >= 0 && t.nc.state[tx.src] == t.nc.word) h = make_uint2(t.nc.len[tx.src] + 1u, t.nc.off[tx.src]);
+        t.nc.hit[e] = h;
+        const bool swept = h.x == 0u && f.w >= 0.f;
+        if (h.x) f.w = -1.f; // (never near: the near-frame lists and phase A drop it)
+        const uint64_t sm = ballot64(swept), hm = ballot64(h.x != 0u);
+        const int lane = threadIdx.x & 63;
+        if (sm && lane == __ffsll((long long)sm) - 1) atomicAdd(&t.nc.tick_cnt[0], uint32_t(__popcll(sm)));
+        if (hm && lane == __ffsll((long long)hm) - 1) atomicAdd(&t.nc.tick_cnt[2], uint32_t(__popcll(hm)));
+    }
     const float inv = prefilter_inv(m, f);
     t.p_txf[e] = f;
     t.p_ch[e] = tx.channel;
@@ -775,15 +786,30 @@ RM_D void filter_wg_tick(const NodesDev &nd, const ModelDev &m, const TickDev &t
     __syncthreads(); // (the next tick of this workgroup reuses the LDS lists)
 }
 
+// the source candidate cache served every frame of these ticks: nothing is left for the sweep (block-uniform)
+RM_D bool nc_nothing_to_sweep(const TickDev *__restrict__ ticks, const int first, const int count)
+{
+    if (ticks[first].nc.state == nullptr) return false;
+    for (int b = 0; b < count; ++b)
+        if (uniform_u(ticks[first + b].nc.tick_cnt[0]) != 0u) return false;
+    return true;
+}
+
 // `ticks[first .. first + count)`: the ticks this workgroup sweeps one after the other against ITS receivers, which stay
 // in registers (and their boxes) for all of them -- at a million receivers the 16 MB of pre-filter records then leave HBM
 // once per `count` ticks instead of once per tick.
 template <int RPT, bool SHADOW>
 RM_D void filter_wg_body(const NodesDev &nd, const ModelDev &m, const TickDev *__restrict__ ticks, const int first, const int count)
 {
+    if (nc_nothing_to_sweep(ticks, first, count)) return;
     WgRx<RPT> rx;
     wg_rx_load<RPT, SHADOW>(nd, ticks[first], rx); // (the receiver tiling is the same for every tick of a launch)
-    for (int b = 0; b < count; ++b) filter_wg_tick<RPT, SHADOW>(nd, m, ticks[first + b], rx, b == 0, uint32_t(first + b));
+    bool first_of_wg = true;
+    for (int b = 0; b < count; ++b) {
+        if (nc_nothing_to_sweep(ticks, first + b, 1)) continue; // (block-uniform)
+        filter_wg_tick<RPT, SHADOW>(nd, m, ticks[first + b], rx, first_of_wg, uint32_t(first + b));
+        first_of_wg = false;
+    }
 }
 
 template <int RPT, bool SHADOW>
@@ -1144,6 +1170,7 @@ k_filter_wg_group(const NodesDev nd, const ModelDev m, const TickDev *__restrict
     const int sb = wg / kNearSb;
     const int slab = wg * kWavesPerBlock + wave;
     const int jbase = slab * (kGroup * RPT);
+    if (nc_nothing_to_sweep(ticks, first, count)) return;
     WgRx<RPT> rx;
     wg_rx_load<RPT, SHADOW>(nd, ticks[first], rx); // (the receiver tiling is the same for every tick of a launch)
     const bool live = slab < ticks[first].n_slabs;
@@ -1352,7 +1379,157 @@ k_filter_wg_group(const NodesDev nd, const ModelDev m, const TickDev *__restrict
     }
 }
 
+// ============================================================================ the source candidate cache (NbrCacheDev)
+// Three launches between the sweep and the exact stage of a batch.  The sweep has appended the candidates of the frames the
+// pre-pass left to it; a list written here is read by LATER launch sequences only (the pre-pass of this one has run), so the
+// order of the stream is all the ordering there is.
+
+// one thread per frame: a swept frame whose source has no list in this epoch claims one (compare-and-swap on the state word: a
+// node that transmits in two ticks of the batch is filled once) and takes its room from the arena.  A source with more
+// candidates than kNcListCap, or one the arena has no room for, keeps the claim and stays uncached for the epoch.
+__global__ void __launch_bounds__(256) k_nc_claim_batch(const TickDev *__restrict__ ticks)
+{
+    const TickDev &t = ticks[blockIdx.z];
+    if (t.nc.state == nullptr) return;
+    const int n_eval = t.n_active - t.first_eval;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e == 0) {
+        atomicAdd(&t.nc.ctr[1], (unsigned long long)t.nc.tick_cnt[2]);
+        atomicAdd(&t.nc.ctr[2], (unsigned long long)t.nc.tick_cnt[0]);
+    }
+    const int lane = threadIdx.x & 63;
+    // (a tick whose shards overflowed has gaps where runs were dropped: none of its frames leaves a list)
+    bool mine = false;
+    int s = -1;
+    uint32_t cnt = 0;
+    if (e < n_eval && t.nc.hit[e].x == 0u && t.stage_count[1] == 0u) {
+        s = t.p_src[e];
+        if (s >= 0) {
+            const uint32_t st = t.nc.state[s];
+            if ((st >> 1) != (t.nc.word >> 1) && atomicCAS(&t.nc.state[s], st, t.nc.word & ~1u) == st) {
+                cnt = t.cand_tot[e - t.cnt_base];
+                mine = cnt <= kNcListCap;
+            }
+        }
+    }
+    // the wave's lists follow each other in the arena: one allocation per wave
+    const uint32_t want = mine ? cnt : 0u;
+    const uint32_t inc = wave_inclusive_scan(want, lane);
+    const uint32_t wave_total = uint32_t(__shfl(int(inc), 63));
+    unsigned long long o = 0;
+    if (wave_total) {
+        if (lane == 0) o = atomicAdd(&t.nc.ctr[0], (unsigned long long)wave_total);
+        o = (unsigned long long)uint32_t(__shfl(int(uint32_t(o)), 0)) | ((unsigned long long)uint32_t(__shfl(int(uint32_t(o >> 32)), 0)) << 32);
+        o += inc - want;
+    }
+    int32_t fill = -1;
+    if (mine && o + cnt <= (unsigned long long)t.nc.arena_len) {
+        t.nc.off[s] = uint32_t(o);
+        t.nc.len[s] = cnt;
+        t.nc.state[s] = t.nc.word; // (this thread owns the word; read by later launch sequences only)
+        if (cnt) fill = int32_t(o);
+    }
+    if (e >= n_eval) return;
+    t.nc.fill[e] = fill;
+    t.nc.cur[e] = 0u;
+    const uint64_t fm = ballot64(fill >= 0);
+    if (fm && int(threadIdx.x & 63) == __ffsll((long long)fm) - 1) atomicAdd(&t.nc.tick_cnt[1], uint32_t(__popcll(fm)));
+}
+
+// one workgroup per shard of a tick that claimed lists: the shard's entries (the sweep's: the cached ones are appended
+// afterwards) whose frame fills a list go there, one atomic per run of entries of one frame
+__global__ void __launch_bounds__(256) k_nc_fill_batch(const TickDev *__restrict__ ticks)
+{
+    const TickDev &t = ticks[blockIdx.z];
+    if (t.nc.state == nullptr || uniform_u(t.nc.tick_cnt[1]) == 0u) return;
+    const uint32_t shard = blockIdx.y;
+    if (shard > t.shard_mask || t.stage_count[1] != 0u) return;
+    const uint32_t n = uniform_u(min(t.shard_count[shard * kShardStride], t.seg_cap));
+    const int lane = threadIdx.x & 63;
+    for (uint32_t i0 = 0; i0 < n; i0 += blockDim.x) { // block-uniform
+        const uint32_t i = i0 + threadIdx.x;
+        const uint32_t idx = shard * t.seg_cap + i;
+        int e = -1, fo = -1;
+        if (i < n) {
+            e = t.st_pkt[idx];
+            fo = t.nc.fill[e];
+        }
+        const RunInfo ri = run_prefix(e, fo >= 0, lane);
+        uint32_t base = 0;
+        if (fo >= 0 && lane == ri.start) base = atomicAdd(&t.nc.cur[e], ri.total);
+        base = uint32_t(__shfl(int(base), ri.start));
+        if (fo >= 0) {
+            const uint32_t k = uint32_t(fo) + base + ri.before;
+            if (k < t.nc.arena_len) t.nc.arena[k] = t.st_dst[idx];
+        }
+    }
+}
+
+// one wave per 64 frames: the list of each one the pre-pass took out of the sweep goes into one of the tick's shards as a run
+// of (frame, engine position) entries, all of the wave's lists copied with full lanes (an entry finds its frame by bisection over the lanes' running
+// counts), and every list's length into its frame's candidate count -- what the sweep would have appended (the order inside
+// a shard never mattered: the reorder stage ranks by node index)
+__global__ void __launch_bounds__(256) k_nc_expand_batch(const TickDev *__restrict__ ticks)
+{
+    const TickDev &t = ticks[blockIdx.z];
+    if (t.nc.state == nullptr || uniform_u(t.nc.tick_cnt[2]) == 0u) return;
+    const int lane = threadIdx.x & 63;
+    const int e0 = int(blockIdx.x) * kBlock + wave_index() * 64;
+    const int e = e0 + lane;
+    uint2 h = make_uint2(0u, 0u);
+    if (e < t.n_active - t.first_eval) h = t.nc.hit[e];
+    uint32_t cnt = h.x > 1u ? h.x - 1u : 0u; // (0: swept, or an empty list)
+    // a list is one run in one shard (the sweep's runs are no longer: a shard has room for cap / shards entries)
+    uint32_t dst = 0;
+    if (cnt) {
+        atomicAdd(&t.cand_tot[e - t.cnt_base], cnt);
+        const uint32_t shard = (uint32_t(e) * 37u + uint32_t(blockIdx.z) * 101u) & t.shard_mask;
+        const uint32_t base = atomicAdd(&t.shard_count[shard * kShardStride], cnt);
+        if (base + cnt > t.seg_cap) { // the shard is full: drop the run, flag the tick
+            t.stage_count[1] = 1u;
+            cnt = 0u;
+        }
+        dst = shard * t.seg_cap + base;
+    }
+    const uint32_t inc = wave_inclusive_scan(cnt, lane);
+    const uint32_t total = uniform_u(uint32_t(__shfl(int(inc), 63)));
+    for (uint32_t j0 = 0; j0 < total; j0 += 64u) { // wave-uniform
+        const uint32_t j = j0 + uint32_t(lane);
+        int lo = 0, hi = 63; // the first lane whose running count is above j
+#pragma unroll
+        for (int step = 0; step < 6; ++step) {
+            const int mid = (lo + hi) >> 1;
+            const bool above = uint32_t(__shfl(int(inc), mid)) > j;
+            hi = above ? mid : hi;
+            lo = above ? lo : mid + 1;
+        }
+        const int f = min(lo, 63);
+        const uint32_t f_inc = uint32_t(__shfl(int(inc), f)), f_cnt = uint32_t(__shfl(int(cnt), f)), f_off = uint32_t(__shfl(int(h.y), f));
+        const uint32_t f_dst = uint32_t(__shfl(int(dst), f));
+        if (j < total) {
+            const uint32_t k = j - (f_inc - f_cnt);
+            t.st_pkt[f_dst + k] = e0 + f;
+            t.st_dst[f_dst + k] = t.nc.arena[f_off + k];
+        }
+    }
+}
+
 // ============================================================================ launchers
+
+hipError_t launch_nbr_cache_batch(hipStream_t s, const TickDev *ticks, int n, const TickDev *b)
+{
+    int max_eval = 0;
+    uint32_t shards = 1;
+    for (int i = 0; i < n; ++i) {
+        max_eval = max(max_eval, ticks[i].n_active - ticks[i].first_eval);
+        shards = max(shards, ticks[i].shard_mask + 1u);
+    }
+    if (max_eval <= 0) return hipSuccess;
+    RM_KLAUNCH(k_nc_claim_batch, dim3(cdiv(max_eval, 256), 1, n), dim3(256), 0, s, b);
+    RM_KLAUNCH(k_nc_fill_batch, dim3(1, shards, n), dim3(256), 0, s, b);
+    RM_KLAUNCH(k_nc_expand_batch, dim3(cdiv(max_eval, kBlock), 1, n), dim3(kBlock), 0, s, b);
+    return hipGetLastError();
+}
 
 hipError_t launch_patch_nodes(hipStream_t s, const NodesDev &nd, const NodePatch *dev_list, int n, const NodePatch &one)
 {
