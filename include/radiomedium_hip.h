@@ -484,10 +484,9 @@ int rm_channel_energy(rm_context *ctx, int64_t time_us, const int32_t *nodes, in
  * for a host list entry outside -1 .. n_nodes-1 -- in a device list such an entry is treated as padding.
  * The caller's list is not written: the gated list lives in a buffer of the context.
  * The device form is asynchronous and deferral is padding -- no count comes back to the host -- so a host may issue many gated
- * lone ticks back to back without waiting.  Batches are not gated: in a batch of self-contained ticks nothing of an earlier
- * tick is on the air by contract, and in a batch of overlapping ticks tick b's gate would need tick b-1's gate result, a
- * serial chain.  One sample time per call: a sample time per candidate (the records forms) needs per-node span information
- * that the per-query RM_ED_TRANSMITTING stamp does not carry. */
+ * lone ticks back to back without waiting.  A batch of ticks is gated by rm_batch_run_sources_cca* below.  One sample time per
+ * tick: a sample time per candidate (the records forms) needs per-node span information that the per-query
+ * RM_ED_TRANSMITTING stamp does not carry. */
 /* asynchronous on the context's stream; all pointers device memory; outputs may be NULL */
 int rm_tick_run_sources_cca_device(rm_context *ctx, int64_t t_begin_us, int64_t t_end_us, const int32_t *dev_src, int32_t n,
                                    int64_t start_us, int64_t air_us, int64_t cca_time_us, double cca_threshold_dbm,
@@ -496,6 +495,42 @@ int rm_tick_run_sources_cca_device(rm_context *ctx, int64_t t_begin_us, int64_t 
  * after rm_tick_run_sources_device */
 int rm_tick_run_sources_cca(rm_context *ctx, int64_t t_begin_us, int64_t t_end_us, const int32_t *src, int32_t n, int64_t start_us,
                             int64_t air_us, int64_t cca_time_us, double cca_threshold_dbm, uint8_t *cca_flags, double *cca_energy_dbm);
+
+/* ---- carrier-sense gated batch: listen before talk across a batch of ticks ------------------------------------
+ * (not reference behaviour.)  The first eight arguments are those of rm_batch_run_sources_device;
+ * cca_time_us[b] is tick b's sample time, t_begin_us[b] <= cca_time_us[b] <= start_us[b]; one threshold for the batch.  The
+ * outputs are flat arrays of n_src[0] + ... + n_src[n_ticks-1] entries in tick order; either may be NULL.
+ *  - For candidate i of tick b with src = j >= 0, (energy, flags) is the channel energy query for node j at t = cca_time_us[b]
+ *    on j's own channel, over the on-air window as the batch finds it PLUS the kept frames of ticks 0 .. b-1 of this batch.  A
+ *    candidate that an earlier tick deferred is not on the air: it is not sensed and does not set RM_ED_TRANSMITTING for its
+ *    node.  Candidates of tick b itself never see each other.  Lists hold distinct nodes within a tick.
+ *  - The candidate is deferred iff flags != 0, as in a gated lone tick.  Padding on input stays padding (flags 0, NaN energy); a
+ *    device-list entry outside 0 .. n_nodes-1 is padding, in a host list it is RM_ERR_INVALID.
+ *  - After the gate the call is, bit for bit, rm_batch_run_sources_device over the same arguments with every deferred entry
+ *    replaced by -1: result slots, pkt_offset (an empty segment per deferred packet), the frames that join the window, and
+ *    rm_events_process_batch afterwards.  The caller's lists are not written: the gated lists live in a buffer of the context.
+ * It follows that a gated batch equals the same ticks issued as rm_tick_run_sources_cca* calls one by one, and any split into
+ * smaller gated batches and gated lone ticks.
+ * Refused before anything is launched, with the window unchanged: RM_ERR_STATE for everything rm_tick_run_sources_cca* refuses
+ * with it, and for what rm_batch_run_sources_device refuses for the same arguments (links that can draw in a batch of
+ * overlapping ticks, overlapping ticks out of time order, an unsorted receiver table, an overlapping tick of more than 8192
+ * candidates, an fp64 frame); RM_ERR_INVALID for n_ticks outside
+ * 1 .. RM_MAX_BATCH, a cca_time_us[b] outside [t_begin_us[b], start_us[b]] or behind the t_begin_us of an earlier tick of the
+ * batch, a cca_time_us[0] behind the window's clock, an air time of 2^32 us or more, a bad host index.  (What only the sweep's
+ * plan of a tick can tell -- a developer knob that takes the filter off its workgroup form -- is refused by the batch itself,
+ * after the gate has run: the outputs are written, no frame joins the window.)
+ * The device form waits once, inside the call, for the count that sizes the gate's pair list; everything else is asynchronous.
+ * The gathered forms, rm_dist_* and rm_group_* are not gated. */
+/* dev_src[b]: device memory; outputs device memory, may be NULL */
+int rm_batch_run_sources_cca_device(rm_context *ctx, int32_t n_ticks, const int64_t *t_begin_us, const int64_t *t_end_us,
+                                    const int32_t *const *dev_src, const int32_t *n_src, const int64_t *start_us,
+                                    const int64_t *air_us, const int64_t *cca_time_us, double cca_threshold_dbm,
+                                    uint8_t *dev_cca_flags /* RM_ED_* */, double *dev_cca_energy_dbm);
+/* host lists in, host arrays out (may be NULL); synchronises; results through rm_batch_result_* as after
+ * rm_batch_run_sources_device */
+int rm_batch_run_sources_cca(rm_context *ctx, int32_t n_ticks, const int64_t *t_begin_us, const int64_t *t_end_us,
+                             const int32_t *const *src, const int32_t *n_src, const int64_t *start_us, const int64_t *air_us,
+                             const int64_t *cca_time_us, double cca_threshold_dbm, uint8_t *cca_flags, double *cca_energy_dbm);
 
 /* ---- several devices behind one caller --------------------------------------------------------------
  * The reference host is ONE process (Main.java:65-73): a group drives n contexts from one host thread, one

@@ -231,6 +231,10 @@ SIGNATURES = {
                                                  C.c_double, C.c_void_p, C.c_void_p]),
     "rm_tick_run_sources_cca": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
                                           C.c_double, C.c_void_p, C.c_void_p]),
+    "rm_batch_run_sources_cca_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    "rm_batch_run_sources_cca": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
     "rm_det_math": (C.c_double, [C.c_int32, C.c_double]),
     "rm_link_hash": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
     "rm_evq_init": (None, [C.c_void_p]),

@@ -204,6 +204,35 @@ RM_D RunInfo run_prefix(int key, bool pred, int lane)
 // test uses the very same expression (monotone in each |d|)
 RM_D float dist2_f32(float dx, float dy, float dz) { return fmaf(dz, dz, fmaf(dy, dy, dx * dx)); }
 
+// The sweep's conservative tests for one (node, frame) pair, shared by the query (k_energy_sum), the gate (k_cca_gate) and the gated batch (rm_ccabatch.hip): same
+// channel, not the node's own frame (RM_ED_TRANSMITTING says that it is sending), fp32 distance against the squared cut-off (which
+// carries the fp32 frame's slack), the shadowed medium's link-hash table (tbl: its kShadowBins words, staged in LDS).  A node
+// outside the frame the fp32 slack was computed for (`wide`) takes every co-channel frame as a candidate.
+struct EdNode {
+    bool valid, wide, shadow;
+    int ch, j;
+    float px, py, pz; // position in the fp32 frame
+};
+RM_D bool ed_candidate(const ModelDev &m, const uint32_t *tbl, const EdNode &nv, const float4 &f, const int4 &fm)
+{
+    if (!(nv.valid && fm.x == nv.ch && fm.z != nv.j)) return false;
+    if (nv.wide) return true;
+    const float s2 = dist2_f32(nv.px - f.x, nv.py - f.y, nv.pz - f.z);
+    if (!(s2 <= f.w)) return false;
+    if (!nv.shadow) return true;
+    const int bin = min(kShadowBins - 1, int(s2 * __int_as_float(fm.w)));
+    const uint32_t a = uint32_t(fm.z), b = uint32_t(nv.j);
+    const uint64_t key = (uint64_t(a < b ? a : b) << 32) | uint64_t(a < b ? b : a);
+    return uint32_t(mix64(m.ld_seed_mixed ^ key) >> 32) <= tbl[bin];
+}
+
+// a 64-bit sum over the lanes of a wave (the gates add 128-bit Q80 sums limb by limb: integer adds, the order cannot matter)
+RM_D unsigned long long wave_sum_u64(unsigned long long v)
+{
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
 // ---- one link, the reference's way
 
 struct LinkEval {

@@ -38,28 +38,6 @@ RM_D void ed_add_u128(unsigned long long *acc /*[2]: lo, hi*/, const U128 v)
     if (v.hi + carry) atomicAdd(&acc[1], (unsigned long long)(v.hi + carry));
 }
 
-// The sweep's conservative tests for one (node, frame) pair, shared by the query (k_energy_sum) and the gate (k_cca_gate): same
-// channel, not the node's own frame (RM_ED_TRANSMITTING says that it is sending), fp32 distance against the squared cut-off (which
-// carries the fp32 frame's slack), the shadowed medium's link-hash table (tbl: its kShadowBins words, staged in LDS).  A node
-// outside the frame the fp32 slack was computed for (`wide`) takes every co-channel frame as a candidate.
-struct EdNode {
-    bool valid, wide, shadow;
-    int ch, j;
-    float px, py, pz; // position in the fp32 frame
-};
-RM_D bool ed_candidate(const ModelDev &m, const uint32_t *tbl, const EdNode &nv, const float4 &f, const int4 &fm)
-{
-    if (!(nv.valid && fm.x == nv.ch && fm.z != nv.j)) return false;
-    if (nv.wide) return true;
-    const float s2 = dist2_f32(nv.px - f.x, nv.py - f.y, nv.pz - f.z);
-    if (!(s2 <= f.w)) return false;
-    if (!nv.shadow) return true;
-    const int bin = min(kShadowBins - 1, int(s2 * __int_as_float(fm.w)));
-    const uint32_t a = uint32_t(fm.z), b = uint32_t(nv.j);
-    const uint64_t key = (uint64_t(a < b ? a : b) << 32) | uint64_t(a < b ? b : a);
-    return uint32_t(mix64(m.ld_seed_mixed ^ key) >> 32) <= tbl[bin];
-}
-
 template <bool GRID>
 __global__ void __launch_bounds__(256) k_energy_index(const ModelDev m, const rm_tx_record *win, int n_win, int n_nodes, int64_t t, const EnergyDev ed)
 {
@@ -267,12 +245,6 @@ hipError_t launch_energy(hipStream_t s, const NodesDev &nd, const ModelDev &m, c
 // of its own; the wave adds the partial sums as integers -- 32-bit limbs, each summed in 64 bits across the lanes, carries
 // propagated once at the end -- so that the order cannot matter.  Lane 0 forms the energy and the flags and writes the gated
 // source: the candidate itself when the channel is clear, -1 (a padding record: make_tx_record) when it defers.
-RM_D unsigned long long wave_sum_u64(unsigned long long v)
-{
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
 template <bool GRID>
 __global__ void __launch_bounds__(256) k_cca_gate(const NodesDev nd, const ModelDev m, const rm_tx_record *win, const EnergyDev ed,
                                                    const int32_t *src, int n, double cca_threshold, int32_t *gated, double *out_energy,

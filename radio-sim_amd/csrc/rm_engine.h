@@ -236,6 +236,47 @@ struct EnergyDev {
     float half, inv;    // cell = int((x + half) * inv)
 };
 
+// A carrier-sense gated BATCH (rm_ccabatch.hip): every candidate of every tick is sensed over the window's
+// frames plus the KEPT frames of the earlier ticks of the batch.  All frames that could count -- the window's records and the records
+// of all candidates as if every one were kept (a scratch array, never the window) -- are indexed once, as the query indexes the
+// window (a kEdG x kEdG grid, kCbK frames per cell, the rest in a list every candidate looks at; the nodes' own frames in chains).
+// One wave per candidate then evaluates its pairs: a window frame goes into the candidate's base sum, a frame of an earlier tick
+// becomes a (frame, Q80 term) pair of the candidate's segment -- sized by a counting pass and a scan, nothing is guessed.  What is
+// left to the one serial pass (k_ccab_resolve, tick after tick) is an integer sum over the pairs whose frame was kept.
+constexpr int kCbK = 64; // frames per cell (a batch indexes some ten times the frames a lone gate does)
+struct CcaTick {
+    const int32_t *src;                 // the caller's list of the tick
+    int64_t start_us, air_us, cca_us;   // the tick's frames, its sample time
+    int first, n;                       // its candidates in the flat order of the batch
+};
+struct CcaBatchDev {
+    const rm_tx_record *win;  // the on-air window: frames 0 .. n_win-1
+    rm_tx_record *scr;        // [n_cand] the candidates' records as if kept: frames n_win ..
+    const CcaTick *ticks;     // [n_ticks] (device memory)
+    int n_win, n_cand, n_ticks;
+    int64_t t_lo, t_hi;       // earliest and latest sample time of the batch (window frames live at neither end are left out)
+    int32_t *cand;            // [n_cand] the candidate's node, -1: padding
+    int32_t *fr_tick;         // [n_win + n_cand] the frame's tick, -1: a window frame
+    uint32_t *cnt;            // [0] entries of `every`, [1] largest cut-off radius in the grid (float bits), [2 ..][kEdCells] frames per cell
+    float4 *bucket_f, *every_f; // as EnergyDev's, with the frame's index in place of the window index
+    int4 *bucket_m, *every_m;
+    int32_t *bucket_t, *every_t; // the frame's tick again, next to its entry
+    unsigned long long *self_slot; // [n] stamp << 32 | a frame of the node, the head of its chain
+    int32_t *self_next;       // [n_win + n_cand] the node's next frame, -1: none
+    uint32_t stamp;
+    float half, inv;
+    uint32_t *pair_cnt;       // [n_cand] upper bound of the candidate's pairs (the counting pass: the conservative tests)
+    uint32_t *pair_off;       // [n_cand + 1] its segment (k_ccab_scan_*)
+    unsigned long long *pair_base; // [workgroups of the scan] pairs before the workgroup's first candidate
+    uint32_t *pair_fill;      // [n_cand] pairs that count (the exact evaluation)
+    uint32_t *pair_slot;      // the pair's frame: candidate slot, bit 31: a frame of the candidate's own node (RM_ED_TRANSMITTING if kept)
+    ulonglong2 *pair_term;    // ... and its Q80 term
+    ulonglong2 *base;         // [n_cand] Q80 sum over the window's frames
+    uint8_t *base_flags;      // [n_cand] RM_ED_TRANSMITTING from a window frame
+    uint8_t *kept;            // [n_cand] after the resolve pass: the candidate went on the air
+    uint32_t *h_info;         // pinned: [0] pairs over all segments (0xFFFFFFFF: more than 2^32 - 2), [1] a segment ran over (cannot happen: sticky)
+};
+
 // A BATCH of SINR ticks whose frames outlive their tick (rm_airbatch.hip; BASELINE configs[4]).  The frames the batch can
 // see -- the window of frames still on the air from earlier calls, then the batch's ticks one after the other -- are ONE
 // array, cut into time slots (a window batch or a tick each).  The heard links of all ticks come from the sweep of the medium
@@ -701,6 +742,11 @@ hipError_t launch_energy(hipStream_t s, const NodesDev &nd, const ModelDev &m, c
 // the gate of a carrier-sense gated tick: the query's index at time t, then one wave per candidate src[i] -> gated[i] = src[i] or -1
 hipError_t launch_cca_gate(hipStream_t s, const NodesDev &nd, const ModelDev &m, const rm_tx_record *win, int n_win, int64_t t, const EnergyDev &ed,
                            bool grid, const int32_t *src, int n, double cca_threshold, int32_t *gated, double *out_energy, uint8_t *out_flags);
+// the gate of a carrier-sense gated batch (rm_ccabatch.hip), in two parts around the one place where the host has to size a buffer:
+// descriptors + index + counting pass + scan (h_info[0] holds the pair count once the stream has drained), then pairs + resolve
+hipError_t launch_ccab_count(hipStream_t s, const NodesDev &nd, const ModelDev &m, const CcaBatchDev &cb, const CcaTick *h_ticks, CcaTick *d_ticks, bool grid);
+hipError_t launch_ccab_resolve(hipStream_t s, const NodesDev &nd, const ModelDev &m, const CcaBatchDev &cb, bool grid, double cca_threshold,
+                               int32_t *gated, double *out_energy, uint8_t *out_flags);
 hipError_t launch_air_expire(hipStream_t s, rm_tx_record *recs, int n, int64_t t_seen); // (the on-air window when the clock goes back)
 hipError_t launch_tick_frames_batch(hipStream_t s, const NodesDev &nd, const ModelDev &m, const TickDev *ticks, int n,
                                     const TickDev *dev_ticks, const LaunchCfg &cfg, int seg_len);

@@ -342,6 +342,28 @@ struct rm_context : TickSlot {
         uint32_t stamp = 0;
         char *h_block = nullptr;
         size_t h_cap = 0; // nodes the block has room for
+        // the gate of a gated batch (rm_api_cca.cpp, rm_ccabatch.hip; rm::CcaBatchDev): its own index (every frame of the window and of the
+        // batch), the candidates' records as if kept, their pair segments; `gated` holds the gated lists of all ticks, one after the other
+        struct Batch {
+            DevBuf<rm::CcaTick> ticks;
+            DevBuf<rm_tx_record> scr;
+            DevBuf<int32_t> cand, fr_tick, self_next, bucket_t, every_t;
+            DevBuf<uint32_t> cnt, pair_cnt, pair_off, pair_fill, pair_slot;
+            DevBuf<float4> bucket_f, every_f;
+            DevBuf<int4> bucket_m, every_m;
+            DevBuf<ulonglong2> pair_term, base;
+            DevBuf<unsigned long long> pair_base;
+            DevBuf<uint8_t> base_flags, kept;
+            char *h_desc = nullptr; // pinned, host-mapped: CcaTick[RM_MAX_BATCH], then the words the device hands back (CcaBatchDev::h_info)
+            void release_all()
+            {
+                ticks.release(); scr.release(); cand.release(); fr_tick.release(); self_next.release(); bucket_t.release(); every_t.release();
+                cnt.release(); pair_cnt.release(); pair_off.release(); pair_fill.release(); pair_slot.release(); bucket_f.release();
+                every_f.release(); bucket_m.release(); every_m.release(); pair_term.release(); base.release(); pair_base.release(); base_flags.release(); kept.release();
+                if (h_desc) (void)hipHostFree(h_desc);
+                h_desc = nullptr;
+            }
+        } cb;
     } ed;
     bool dev_records_from_caller = false; // the tick being prepared takes rm_tx_record arrays the caller built in device memory
     mutable rm::ModelDev mdev{};            // model_dev()'s last answer and what it was derived from

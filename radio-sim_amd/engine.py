@@ -629,6 +629,41 @@ class Engine:
         check(self._L.rm_tick_run_sources_cca_device(self._h, int(t_begin), int(t_end), dev_src_ptr, int(n), int(start_us), int(air_us),
                                                      int(cca_time_us), float(cca_threshold_dbm), dev_flags_ptr, dev_energy_ptr))
 
+    def _cca_batch_args(self, t_begin, t_end, n_src, start_us, air_us, cca_time_us):
+        i64 = lambda v: np.ascontiguousarray(v, dtype=np.int64)
+        tb, te, st, ai, tc = i64(t_begin), i64(t_end), i64(start_us), i64(air_us), i64(cca_time_us)
+        cnt = np.ascontiguousarray(n_src, dtype=np.int32)
+        assert len(tb) == len(te) == len(st) == len(ai) == len(tc) == len(cnt)
+        return tb, te, st, ai, tc, cnt
+
+    def batch_run_sources_cca(self, t_begin, t_end, src_lists, start_us, air_us, cca_time_us, cca_threshold_dbm=float("nan")):
+        """A carrier-sense gated batch: tick b's candidates src_lists[b] (node indices, -1 = padding) are
+        sensed at cca_time_us[b] over the window plus the kept frames of the earlier ticks of the batch.  -> (flags, energy in dBm),
+        one array per tick; the ticks' results through batch_result_copy(b, len(src_lists[b])) as after batch_run_sources_device."""
+        lists = [np.ascontiguousarray(s, dtype=np.int32) for s in src_lists]
+        tb, te, st, ai, tc, cnt = self._cca_batch_args(t_begin, t_end, [len(s) for s in lists], start_us, air_us, cca_time_us)
+        assert len(lists) == len(tb)
+        ptrs = np.array([s.ctypes.data if len(s) else 0 for s in lists], dtype=np.uint64)
+        total = int(cnt.sum())
+        flags = np.empty(max(total, 1), dtype=np.uint8)
+        energy = np.empty(max(total, 1), dtype=np.float64)
+        check(self._L.rm_batch_run_sources_cca(self._h, len(lists), tb.ctypes.data, te.ctypes.data, ptrs.ctypes.data, cnt.ctypes.data,
+                                               st.ctypes.data, ai.ctypes.data, tc.ctypes.data, float(cca_threshold_dbm),
+                                               flags.ctypes.data, energy.ctypes.data))
+        cuts = np.cumsum(cnt)[:-1]
+        return np.split(flags[:total], cuts), np.split(energy[:total], cuts)
+
+    def batch_run_sources_cca_device(self, t_begin, t_end, dev_src_ptrs, n_src, start_us, air_us, cca_time_us, cca_threshold_dbm,
+                                     dev_flags_ptr=None, dev_energy_ptr=None):
+        """The raw form: device lists, flat device outputs in tick order (sum(n_src) entries each, or None); the callers' lists are
+        not written."""
+        tb, te, st, ai, tc, cnt = self._cca_batch_args(t_begin, t_end, n_src, start_us, air_us, cca_time_us)
+        ptrs = np.ascontiguousarray([p or 0 for p in dev_src_ptrs], dtype=np.uint64)
+        assert len(ptrs) == len(tb)
+        check(self._L.rm_batch_run_sources_cca_device(self._h, len(ptrs), tb.ctypes.data, te.ctypes.data, ptrs.ctypes.data, cnt.ctypes.data,
+                                                      st.ctypes.data, ai.ctypes.data, tc.ctypes.data, float(cca_threshold_dbm),
+                                                      dev_flags_ptr, dev_energy_ptr))
+
     def sync(self):
         check(self._L.rm_sync(self._h))
 

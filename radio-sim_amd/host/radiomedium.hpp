@@ -751,6 +751,66 @@ public:
         return flags;
     }
     const std::vector<std::unique_ptr<RadioPacket>> &sentIfClear() const { return ccaSent_; }
+    // The same across a batch of ticks (extension E7): tick b's senders want to start at start_us[b] and sense at cca_time_us[b]
+    // (t_begin_us[b] <= cca_time_us[b] <= start_us[b]); a tick senses the window plus the KEPT frames of the ticks before it.
+    // Returns the flags per tick (empty and lastError on a refusal); receptions are generated from the result slots.
+    std::vector<std::vector<uint8_t>> transmitIfClearBatch(const std::vector<std::vector<Node *>> &senders, const std::vector<int64_t> &t_begin_us,
+                                                           const std::vector<int64_t> &start_us, int64_t hex_length,
+                                                           const std::vector<int64_t> &cca_time_us, double threshold_dbm)
+    {
+        lastError.clear();
+        Simulator *sim = simulator;
+        if (!sim) { lastError = "No simulator"; return {}; }
+        const size_t nt = senders.size();
+        if (nt == 0 || t_begin_us.size() != nt || start_us.size() != nt || cca_time_us.size() != nt) { lastError = "one entry per tick"; return {}; }
+        if (!syncNodes()) return {};
+        const std::vector<Node *> &nodes = sim->getNodes();
+        rm_set_time(ctx_, sim->getTime());
+        std::vector<std::vector<int32_t>> src(nt);
+        std::vector<const int32_t *> lists(nt);
+        std::vector<int32_t> n_src(nt);
+        std::vector<int64_t> air(nt, rm_air_time_us(hex_length));
+        size_t total = 0;
+        for (size_t b = 0; b < nt; ++b) {
+            src[b].resize(senders[b].size());
+            for (size_t i = 0; i < senders[b].size(); ++i) src[b][i] = senders[b][i] ? senders[b][i]->index : -1;
+            lists[b] = src[b].data();
+            n_src[b] = int32_t(src[b].size());
+            total += src[b].size();
+        }
+        std::vector<uint8_t> flat(std::max<size_t>(total, 1), 0);
+        if (rm_batch_run_sources_cca(ctx_, int32_t(nt), t_begin_us.data(), start_us.data(), lists.data(), n_src.data(), start_us.data(), air.data(),
+                                     cca_time_us.data(), threshold_dbm, flat.data(), nullptr) != RM_OK) {
+            lastError = rm_last_error();
+            return {};
+        }
+        std::vector<std::vector<uint8_t>> flags(nt);
+        if (ccaDst_.empty()) { ccaDst_.resize(1024); ccaVerdict_.resize(1024); ccaRssi_.resize(1024); }
+        const std::string data(size_t(hex_length), '0');
+        size_t at = 0;
+        for (size_t b = 0; b < nt; ++b) {
+            flags[b].assign(flat.begin() + at, flat.begin() + at + src[b].size());
+            at += src[b].size();
+            std::vector<uint32_t> off(src[b].size() + 1, 0);
+            uint32_t heard = 0;
+            for (int attempt = 0; attempt < 2; ++attempt) {
+                const int rc = rm_batch_result_copy(ctx_, int32_t(b), nullptr, ccaDst_.data(), ccaVerdict_.data(), ccaRssi_.data(), nullptr,
+                                                    uint32_t(ccaDst_.size()), &heard, nullptr, off.data());
+                if (rc == RM_OK) break;
+                if (attempt == 1 || heard <= ccaDst_.size()) { lastError = rm_last_error(); return {}; }
+                ccaDst_.resize(heard); ccaVerdict_.resize(heard); ccaRssi_.resize(heard);
+            }
+            for (size_t i = 0; i < src[b].size(); ++i) {
+                if (src[b][i] < 0 || flags[b][i]) continue;
+                ccaSent_.emplace_back(new RadioPacket(senders[b][i], start_us[b], data));
+                RadioPacket &packet = *ccaSent_.back();
+                sim->generateTransmissionEvents(packet);
+                for (uint32_t k = off[i]; k < off[i + 1]; ++k)
+                    sim->generateReceptionEvents(packet, nodes[size_t(ccaDst_[k])], ccaRssi_[k], ccaVerdict_[k] == RM_DELIVERED);
+            }
+        }
+        return flags;
+    }
 
 private:
     std::vector<std::unique_ptr<RadioPacket>> ccaSent_;
