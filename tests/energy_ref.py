@@ -40,9 +40,10 @@ def from_fixed(q):
     return math.ldexp(float(keep), drop - 80)    # keep may be 2^53: still exact
 
 
-def channel_energy(O, mdl, nd, frames, t, nodes=None, channel=None, threshold=float("nan")):
+def channel_energy(O, mdl, nd, frames, t, nodes=None, channel=None, threshold=float("nan"), q80=False):
     """-> (energy float64[n], flags uint8[n], counting frames int32[n]) for `nodes` (default: all) at time t; `frames`: every
-    frame handed to the medium so far (oracle PACKET_DTYPE; their recorded positions), nd: the node table as it is now."""
+    frame handed to the medium so far (oracle PACKET_DTYPE; their recorded positions), nd: the node table as it is now.
+    q80=True: a fourth value, the integer Q80 sum per node (Python integers)."""
     L = O.lib()
     ns = nd.as_struct()
     frames = np.ascontiguousarray(frames)
@@ -55,6 +56,7 @@ def channel_energy(O, mdl, nd, frames, t, nodes=None, channel=None, threshold=fl
     energy = np.empty(len(nodes))
     flags = np.zeros(len(nodes), dtype=np.uint8)
     counting = np.zeros(len(nodes), dtype=np.int32)
+    sums = []
     for i, j in enumerate(nodes.tolist()):
         c = int(nd.channel[j]) if channel is None else channel
         acc = 0
@@ -65,6 +67,7 @@ def channel_energy(O, mdl, nd, frames, t, nodes=None, channel=None, threshold=fl
             if r >= mdl.ld_ifloor_dbm:
                 acc += to_fixed(L.orc_det_pow10(r / 10.0))
                 counting[i] += 1
+        sums.append(acc)
         energy[i] = 10.0 * L.orc_det_log10(from_fixed(acc) + noise)
         flags[i] = (ED_TRANSMITTING if j in sending else 0) | (ED_BUSY if energy[i] >= threshold else 0)
-    return energy, flags, counting
+    return (energy, flags, counting, sums) if q80 else (energy, flags, counting)

@@ -24,10 +24,11 @@ def _times(sc, first, last):
 
 def _batch(eng, sc, lists, first, form, thr, air=CR.AIR):
     """ticks first .. first+len(lists)-1 of the scene's clock as ONE gated batch -> per tick (flags, energy); the device form through
-    device arrays, with the caller's lists checked to be unwritten"""
+    device arrays, with the caller's lists checked to be unwritten.  `air`: one air time for every tick, or a list with one per tick"""
     lists = [np.ascontiguousarray(s, dtype=np.int32) for s in lists]
     tb, te, tc, ts = _times(sc, first, first + len(lists))
-    airs = [air] * len(lists)
+    airs = list(air) if isinstance(air, (list, tuple)) else [air] * len(lists)
+    assert len(airs) == len(lists)
     if form == "host":
         f, e = eng.batch_run_sources_cca(tb, te, lists, ts, airs, tc, thr)
         return list(zip(f, e))
