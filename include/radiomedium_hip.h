@@ -532,6 +532,71 @@ int rm_batch_run_sources_cca(rm_context *ctx, int32_t n_ticks, const int64_t *t_
                              const int32_t *const *src, const int32_t *n_src, const int64_t *start_us, const int64_t *air_us,
                              const int64_t *cca_time_us, double cca_threshold_dbm, uint8_t *cca_flags, double *cca_energy_dbm);
 
+/* ---- CSMA-CA gated batch: a deferred candidate backs off and tries again, on the device -------------------------
+ * (not reference behaviour.)  Unslotted CSMA-CA over the ticks of ONE gated batch.  Candidate k of
+ * tick b is a PACKET with flat index o = n_src[0] + ... + n_src[b-1] + k, whatever its entry holds (a padding entry is a packet
+ * that never attempts).  Attempt 0 of a packet is in tick b; if attempt a is made and deferred and a < max_backoffs, attempt
+ * a + 1 is in tick T(a+1) = T(a) + 1 + r with BE = min(min_be + a, max_be), r = 0 if BE = 0 else h2 >> (64 - BE),
+ * h1 = mix64(mix64(seed + 0x9E3779B97F4A7C15) ^ uint64(cca_time_us[b])) (b: the ORIGIN tick), h2 = mix64(h1 ^ (uint64(k) << 8 | a)),
+ * mix64 = the SplitMix64 finaliser of E2.  The schedule depends on the tick times, the list lengths and the parameters only:
+ * rm_csma_schedule computes it without a device.
+ *  - The EXPANDED list of tick T: its n_src[T] own entries, then every attempt a >= 1 of any packet with T(a) = T, ordered by
+ *    (origin tick, origin slot); n_exp[T] entries.  Packet numbers of tick T are positions in that list.  Attempts that fall at
+ *    T >= n_ticks are not part of the batch.
+ *  - An attempt is MADE iff its entry is a node 0 .. n_nodes-1 and every earlier attempt of its packet was made and deferred;
+ *    otherwise its slot is padding (nothing sensed).  A made attempt of node j in tick T is sensed exactly as a candidate of tick T
+ *    of rm_batch_run_sources_cca*: the window as the batch finds it plus the KEPT frames of ticks 0 .. T-1.
+ *  - One frame per radio per tick: among a node's slots of a tick with flags 0 the first in list order is kept; a later one gets
+ *    RM_ED_TRANSMITTING or-ed into its flags and counts as deferred.  (This replaces E7's "distinct nodes within a tick", which
+ *    a caller cannot guarantee for retries; the own lists still hold distinct nodes per tick.)
+ *  - Per packet: RM_CSMA_NONE (padding entry; attempts 0, pkt -1), RM_CSMA_SENT (tick = the kept attempt's tick, pkt = its
+ *    position in that tick's expanded list), RM_CSMA_FAILED (attempt max_backoffs made and deferred; pkt -1), RM_CSMA_PENDING (the
+ *    next attempt falls at tick >= n_ticks; tick = that batch-relative tick, pkt -1).  attempts = attempts made; flags and
+ *    energy_dbm are those of the last attempt made (0 and NaN if none).  tick is -1 where the table has none.
+ *  - After the gate the call is, bit for bit, rm_batch_run_sources_device over the same tick times with n_exp and the gated
+ *    expanded lists (result slots, pkt_offset, the frames that join the window, java.util.Random untouched,
+ *    rm_events_process_batch afterwards).  The caller's lists are never written.  With max_backoffs = 0 the call is
+ *    rm_batch_run_sources_cca* bit for bit.
+ * Refused before anything is launched, window unchanged: everything rm_batch_run_sources_cca* refuses, with its codes (the
+ * 8192-candidate limit of an overlapping tick applies to n_exp[T]); RM_ERR_INVALID for parameters out of range or reserved != 0.
+ * Not promised: invariance under splitting a batch -- a pending packet's chain ends with the batch; carrying a chain into the next
+ * batch (an attempt offset on input) is a follow-up.  The gathered forms, rm_dist_* and rm_group_* are not gated. */
+#define RM_CSMA_NONE 0
+#define RM_CSMA_SENT 1
+#define RM_CSMA_FAILED 2
+#define RM_CSMA_PENDING 3
+typedef struct rm_csma_params {
+    int32_t max_backoffs; /* 0 .. 5: busy samples after the first before giving up (macMaxCSMABackoffs; 802.15.4 default 4) */
+    int32_t min_be;       /* 0 .. max_be */
+    int32_t max_be;       /* min_be .. 8 */
+    int32_t reserved;     /* 0 */
+    uint64_t seed;
+} rm_csma_params;
+typedef struct rm_csma_result { /* flat, one entry per packet (sum of n_src); any pointer may be NULL */
+    uint8_t *status;
+    uint8_t *attempts;
+    int32_t *tick;
+    int32_t *pkt;
+    uint8_t *flags;
+    double *energy_dbm;
+} rm_csma_result;
+void rm_csma_defaults(rm_csma_params *p); /* 4, 3, 5, 0, seed 0 */
+/* pure host function, no device needed: n_exp[n_ticks]; origin[] (flat packet index) / attempt[] per expanded slot in tick order
+ * (may be NULL; cap entries); *total = sum of n_exp even when cap is too small (then RM_ERR_CAPACITY) */
+int rm_csma_schedule(const rm_csma_params *p, int32_t n_ticks, const int32_t *n_src, const int64_t *cca_time_us, int32_t *n_exp,
+                     int32_t *origin, uint8_t *attempt, int64_t cap, int64_t *total);
+/* dev_src[b]: device memory; dev_out's pointers device memory; n_exp: host, [n_ticks], may be NULL.  Waits once inside the call, as
+ * rm_batch_run_sources_cca_device */
+int rm_batch_run_sources_csma_device(rm_context *ctx, int32_t n_ticks, const int64_t *t_begin_us, const int64_t *t_end_us,
+                                     const int32_t *const *dev_src, const int32_t *n_src, const int64_t *start_us,
+                                     const int64_t *air_us, const int64_t *cca_time_us, double cca_threshold_dbm,
+                                     const rm_csma_params *p, const rm_csma_result *dev_out, int32_t *n_exp);
+/* host lists in, host arrays out; synchronises; results through rm_batch_result_* with n_exp[b] packets in tick b */
+int rm_batch_run_sources_csma(rm_context *ctx, int32_t n_ticks, const int64_t *t_begin_us, const int64_t *t_end_us,
+                              const int32_t *const *src, const int32_t *n_src, const int64_t *start_us, const int64_t *air_us,
+                              const int64_t *cca_time_us, double cca_threshold_dbm, const rm_csma_params *p,
+                              const rm_csma_result *out, int32_t *n_exp);
+
 /* ---- several devices behind one caller --------------------------------------------------------------
  * The reference host is ONE process (Main.java:65-73): a group drives n contexts from one host thread, one
  * per device (an ordinal may repeat: several partitions on one GPU).  Receivers are partitioned over the

@@ -18,6 +18,7 @@ UNHEARD, INTERFERED, DELIVERED = 0, 1, 2
 LD_SINR = 1
 CHANNEL_OWN = -1
 ED_TRANSMITTING, ED_BUSY = 1, 2
+CSMA_NONE, CSMA_SENT, CSMA_FAILED, CSMA_PENDING = 0, 1, 2, 3
 MAX_BATCH = 512
 RM_OK, RM_ERR_INVALID, RM_ERR_NO_DEVICE, RM_ERR_HIP, RM_ERR_CAPACITY, RM_ERR_STATE = 0, -1, -2, -3, -4, -5
 
@@ -26,6 +27,15 @@ class RadioMediumError(RuntimeError):
     def __init__(self, code, message):
         super().__init__("rm error %d: %s" % (code, message))
         self.code = code
+
+
+class CsmaParams(C.Structure):
+    _fields_ = [("max_backoffs", C.c_int32), ("min_be", C.c_int32), ("max_be", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+
+class CsmaResult(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("attempts", C.c_void_p), ("tick", C.c_void_p), ("pkt", C.c_void_p), ("flags", C.c_void_p),
+                ("energy_dbm", C.c_void_p)]
 
 
 class ModelParams(C.Structure):
@@ -235,6 +245,13 @@ SIGNATURES = {
                                                   C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
     "rm_batch_run_sources_cca": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    "rm_csma_defaults": (None, [C.c_void_p]),
+    "rm_csma_schedule": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                   C.POINTER(C.c_int64)]),
+    "rm_batch_run_sources_csma_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_batch_run_sources_csma": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rm_det_math": (C.c_double, [C.c_int32, C.c_double]),
     "rm_link_hash": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
     "rm_evq_init": (None, [C.c_void_p]),

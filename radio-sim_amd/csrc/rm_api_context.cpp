@@ -326,6 +326,7 @@ void rm_destroy(rm_context *c)
     if (c->ed.h_block) (void)hipHostFree(c->ed.h_block);
     c->ed.h_block = nullptr;
     c->ed.cb.release_all();
+    c->ed.cs.release_all();
     c->d_patch.release();
     c->d_enabled.release();
     c->d_member.release(); c->d_draw_nodes.release(); c->d_all_off.release(); c->d_all_nodes.release();

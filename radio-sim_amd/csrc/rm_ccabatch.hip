@@ -34,9 +34,6 @@ __global__ void __launch_bounds__(256) k_ccab_begin(const CcaTick *h_ticks, int 
     if (i < cnt_len) cnt[i] = 0u;
 }
 
-// live at t: start <= t < start + air (the end of a span is exclusive; the query's test)
-RM_D bool cb_live(int64_t t, int64_t start_us, int64_t air_us) { return !(t < start_us || t - start_us >= air_us); }
-
 template <bool GRID>
 __global__ void __launch_bounds__(256) k_ccab_index(const NodesDev nd, const ModelDev m, const CcaBatchDev cb)
 {
@@ -66,37 +63,7 @@ __global__ void __launch_bounds__(256) k_ccab_index(const NodesDev nd, const Mod
         cb.fr_tick[f] = tk;
         if (r.src < 0) return;
     }
-    if (r.air_us <= 0) return; // (never live)
-    if (r.src < nd.n) {
-        const unsigned long long stamp = (unsigned long long)cb.stamp << 32;
-        const unsigned long long old = atomicExch(&cb.self_slot[r.src], stamp | (unsigned long long)uint32_t(f));
-        cb.self_next[f] = (uint32_t(old >> 32) == cb.stamp) ? int(uint32_t(old)) : -1;
-    }
-    float4 p;
-    double thr64;
-    tx_prefilter_at(m, m.ld_ifloor, r, p, thr64);
-    if (!(p.w >= 0.f)) return; // reaches the floor nowhere
-    float inv = 0.f;           // squared fp32 distance -> bin of the link-hash table (k_energy_index)
-    if (m.shadow_tbl != nullptr && p.w > 0.f && p.w < __builtin_inff()) {
-        const float cut = __builtin_sqrtf(p.w);
-        if (1.01f * (2.0f * float(m.f32_slack)) / (0.15f * cut) + 1e-5f <= float(kShadowPad)) inv = float(kShadowBins) / p.w;
-    }
-    const int4 meta = make_int4(r.channel, f, r.src, __float_as_int(inv));
-    if (GRID && p.w < __builtin_inff()) {
-        const int cell = sg_cell1(p.y, cb.half, cb.inv) * kEdG + sg_cell1(p.x, cb.half, cb.inv);
-        atomicMax(&cb.cnt[1], __float_as_uint(sqrt_up(p.w)));
-        const uint32_t k = atomicAdd(&cb.cnt[2 + cell], 1u);
-        if (k < uint32_t(kCbK)) {
-            cb.bucket_f[cell * kCbK + int(k)] = p;
-            cb.bucket_m[cell * kCbK + int(k)] = meta;
-            cb.bucket_t[cell * kCbK + int(k)] = tk;
-            return;
-        }
-    }
-    const uint32_t e = atomicAdd(&cb.cnt[0], 1u); // (at most one entry per frame: the list has room for every frame)
-    cb.every_f[e] = p;
-    cb.every_m[e] = meta;
-    cb.every_t[e] = tk;
+    cb_index_frame<GRID>(nd, m, cb, f, r, tk);
 }
 
 template <bool GRID, bool FILL>
@@ -165,49 +132,7 @@ __global__ void __launch_bounds__(256) k_ccab_pairs(const NodesDev nd, const Mod
         else acc = u128_add(acc, q);
     };
 
-    if (GRID) {
-        // the cells that can hold a frame within reach (as the query: |dx| <= largest radius, positions map to cells monotonically)
-        const float rmax = __uint_as_float(cb.cnt[1]);
-        const float reach = rmax * (1.0f + 2e-5f) + 1e-3f / cb.inv;
-        int cx0 = 0, cy0 = 0, cx1 = kEdG - 1, cy1 = kEdG - 1;
-        if (!wide) {
-            cx0 = sg_cell1(px - reach, cb.half, cb.inv);
-            cx1 = sg_cell1(px + reach, cb.half, cb.inv);
-            cy0 = sg_cell1(py - reach, cb.half, cb.inv);
-            cy1 = sg_cell1(py + reach, cb.half, cb.inv);
-        }
-        cx0 = uniform_i(cx0), cx1 = uniform_i(cx1), cy0 = uniform_i(cy0), cy1 = uniform_i(cy1);
-        const int ncx = cx1 - cx0 + 1, ncells = ncx * (cy1 - cy0 + 1);
-        for (int c0 = 0; c0 < ncells; c0 += 64) { // wave-uniform
-            const int c = c0 + lane;
-            int cell = 0, cnt = 0;
-            if (c < ncells) {
-                cell = (cy0 + c / ncx) * kEdG + cx0 + c % ncx;
-                cnt = int(min(cb.cnt[2 + cell], uint32_t(kCbK))); // every cell's count at once
-            }
-            int incl = cnt; // inclusive prefix over the wave
-            for (int d = 1; d < 64; d <<= 1) {
-                const int up = __shfl_up(incl, d);
-                if (lane >= d) incl += up;
-            }
-            const int total = uniform_i(__shfl(incl, 63));
-            if (total == 0) continue;
-            s_off[wave][lane] = incl - cnt;
-            s_cell[wave][lane] = cell;
-            if (lane == 63) s_off[wave][64] = total;
-            __builtin_amdgcn_wave_barrier(); // (LDS traffic of one wave is in order; the compiler must not move it either)
-            for (int e = lane; e < total; e += 64) { // the entries, whichever cell they are in
-                int lo = 0;                              // the last cell whose first entry is <= e
-                for (int step = 32; step > 0; step >>= 1)
-                    if (s_off[wave][lo + step] <= e) lo += step;
-                const int at = s_cell[wave][lo] * kCbK + (e - s_off[wave][lo]);
-                look(cb.bucket_f[at], cb.bucket_m[at], cb.bucket_t[at]);
-            }
-            __builtin_amdgcn_wave_barrier(); // (the next round rewrites the offsets)
-        }
-    }
-    const int n_every = uniform_i(int(cb.cnt[0]));
-    for (int e = lane; e < n_every; e += 64) look(cb.every_f[e], cb.every_m[e], cb.every_t[e]);
+    cb_walk<GRID>(cb, s_off[wave], s_cell[wave], lane, wide, px, py, look);
 
     // the node's own frames (its chain): a window frame that spans the sample says RM_ED_TRANSMITTING now, a frame of an earlier tick
     // of the batch says it if that frame was kept -- on any channel, whatever its reach
@@ -232,15 +157,8 @@ __global__ void __launch_bounds__(256) k_ccab_pairs(const NodesDev nd, const Mod
         if (lane == 0) cb.pair_cnt[i] = uint32_t(n);
         return;
     }
-    // the wave's base sum: four 32-bit limbs, each added across the lanes in 64 bits, carries once (k_cca_gate)
-    const unsigned long long l0 = wave_sum_u64(acc.lo & 0xFFFFFFFFull), l1 = wave_sum_u64(acc.lo >> 32);
-    const unsigned long long l2 = wave_sum_u64(acc.hi & 0xFFFFFFFFull), l3 = wave_sum_u64(acc.hi >> 32);
-    __builtin_amdgcn_wave_barrier();
+    const U128 sum = wave_sum_u128(acc); // the wave's base sum
     if (lane != 0) return;
-    U128 sum, part;
-    sum.lo = l0, sum.hi = l2;
-    part.lo = l1 << 32, part.hi = (l1 >> 32) + (l3 << 32); // (mod 2^128, as the query's sums)
-    sum = u128_add(sum, part);
     cb.base[i] = make_ulonglong2(sum.lo, sum.hi);
     cb.base_flags[i] = uint8_t(tx);
     cb.pair_fill[i] = min(s_np[wave], cap);
@@ -357,10 +275,26 @@ __global__ void __launch_bounds__(kCbResolve) k_ccab_resolve(const CcaBatchDev c
     }
 }
 
-hipError_t launch_ccab_count(hipStream_t s, const NodesDev &nd, const ModelDev &m, const CcaBatchDev &cb, const CcaTick *h_ticks, CcaTick *d_ticks, bool grid)
+// the descriptors and the index's counters; the counts' scan: the CSMA-CA gated batch (rm_csma.hip) takes both as they are
+hipError_t launch_ccab_begin(hipStream_t s, const CcaBatchDev &cb, const CcaTick *h_ticks, CcaTick *d_ticks, bool grid)
 {
     const int cnt_len = grid ? 2 + kEdCells : 2;
     RM_KLAUNCH(k_ccab_begin, dim3(cdiv(max(cb.n_ticks, cnt_len), 256)), dim3(256), 0, s, h_ticks, cb.n_ticks, d_ticks, cb.cnt, cnt_len);
+    return hipGetLastError();
+}
+
+hipError_t launch_ccab_scan(hipStream_t s, const CcaBatchDev &cb)
+{
+    const int n_blocks = cdiv(cb.n_cand, kCbResolve);
+    RM_KLAUNCH(k_ccab_scan_sums, dim3(n_blocks), dim3(kCbResolve), 0, s, cb);
+    RM_KLAUNCH(k_ccab_scan_top, dim3(1), dim3(kCbResolve), 0, s, cb, n_blocks);
+    RM_KLAUNCH(k_ccab_scan_offsets, dim3(n_blocks), dim3(kCbResolve), 0, s, cb);
+    return hipGetLastError();
+}
+
+hipError_t launch_ccab_count(hipStream_t s, const NodesDev &nd, const ModelDev &m, const CcaBatchDev &cb, const CcaTick *h_ticks, CcaTick *d_ticks, bool grid)
+{
+    (void)launch_ccab_begin(s, cb, h_ticks, d_ticks, grid);
     const int n_frames = cb.n_win + cb.n_cand;
     if (grid) {
         RM_KLAUNCH((k_ccab_index<true>), dim3(cdiv(n_frames, 256)), dim3(256), 0, s, nd, m, cb);
@@ -369,11 +303,7 @@ hipError_t launch_ccab_count(hipStream_t s, const NodesDev &nd, const ModelDev &
         RM_KLAUNCH((k_ccab_index<false>), dim3(cdiv(n_frames, 256)), dim3(256), 0, s, nd, m, cb);
         RM_KLAUNCH((k_ccab_pairs<false, false>), dim3(cdiv(cb.n_cand, kWavesPerBlock)), dim3(kBlock), 0, s, nd, m, cb);
     }
-    const int n_blocks = cdiv(cb.n_cand, kCbResolve);
-    RM_KLAUNCH(k_ccab_scan_sums, dim3(n_blocks), dim3(kCbResolve), 0, s, cb);
-    RM_KLAUNCH(k_ccab_scan_top, dim3(1), dim3(kCbResolve), 0, s, cb, n_blocks);
-    RM_KLAUNCH(k_ccab_scan_offsets, dim3(n_blocks), dim3(kCbResolve), 0, s, cb);
-    return hipGetLastError();
+    return launch_ccab_scan(s, cb);
 }
 
 hipError_t launch_ccab_resolve(hipStream_t s, const NodesDev &nd, const ModelDev &m, const CcaBatchDev &cb, bool grid, double cca_threshold,

@@ -587,4 +587,112 @@ static inline int batch_scan_variant(const TickDev *ticks, int n)
     return scan;
 }
 
+// ---- what the gated batch (rm_ccabatch.hip) and the CSMA-CA gated batch (rm_csma.hip) share: the index entry of one frame, one
+// wave's walk over the indexed frames within its node's reach, the wave's 128-bit sum
+
+// live at t: start <= t < start + air (the end of a span is exclusive; the query's test)
+RM_D bool cb_live(int64_t t, int64_t start_us, int64_t air_us) { return !(t < start_us || t - start_us >= air_us); }
+
+// frame f (record r, of tick tk; -1: a window frame) joins its source node's chain and the grid or the EVERY list; CHAIN_ALL: a frame
+// that is never live joins the chain too (the CSMA-CA batch finds a node's slots of one tick there)
+template <bool GRID, bool CHAIN_ALL = false>
+RM_D void cb_index_frame(const NodesDev &nd, const ModelDev &m, const CcaBatchDev &cb, const int f, const rm_tx_record &r, const int tk)
+{
+    if (!CHAIN_ALL && r.air_us <= 0) return; // (never live)
+    if (r.src < nd.n) {
+        const unsigned long long stamp = (unsigned long long)cb.stamp << 32;
+        const unsigned long long old = atomicExch(&cb.self_slot[r.src], stamp | (unsigned long long)uint32_t(f));
+        cb.self_next[f] = (uint32_t(old >> 32) == cb.stamp) ? int(uint32_t(old)) : -1;
+    }
+    if (CHAIN_ALL && r.air_us <= 0) return;
+    float4 p;
+    double thr64;
+    tx_prefilter_at(m, m.ld_ifloor, r, p, thr64);
+    if (!(p.w >= 0.f)) return; // reaches the floor nowhere
+    float inv = 0.f;           // squared fp32 distance -> bin of the link-hash table (k_energy_index)
+    if (m.shadow_tbl != nullptr && p.w > 0.f && p.w < __builtin_inff()) {
+        const float cut = __builtin_sqrtf(p.w);
+        if (1.01f * (2.0f * float(m.f32_slack)) / (0.15f * cut) + 1e-5f <= float(kShadowPad)) inv = float(kShadowBins) / p.w;
+    }
+    const int4 meta = make_int4(r.channel, f, r.src, __float_as_int(inv));
+    if (GRID && p.w < __builtin_inff()) {
+        const int cell = sg_cell1(p.y, cb.half, cb.inv) * kEdG + sg_cell1(p.x, cb.half, cb.inv);
+        atomicMax(&cb.cnt[1], __float_as_uint(sqrt_up(p.w)));
+        const uint32_t k = atomicAdd(&cb.cnt[2 + cell], 1u);
+        if (k < uint32_t(kCbK)) {
+            cb.bucket_f[cell * kCbK + int(k)] = p;
+            cb.bucket_m[cell * kCbK + int(k)] = meta;
+            cb.bucket_t[cell * kCbK + int(k)] = tk;
+            return;
+        }
+    }
+    const uint32_t e = atomicAdd(&cb.cnt[0], 1u); // (at most one entry per frame: the list has room for every frame)
+    cb.every_f[e] = p;
+    cb.every_m[e] = meta;
+    cb.every_t[e] = tk;
+}
+
+// one wave, a node at (px, py) of the fp32 frame: look(entry, meta, tick) for every frame of the grid's cells within reach and of
+// the EVERY list, a lane per frame.  w_off[65] / w_cell[64]: the wave's own words of LDS.
+template <bool GRID, class Look>
+RM_D void cb_walk(const CcaBatchDev &cb, int *w_off, int *w_cell, const int lane, const bool wide, const float px, const float py, Look &&look)
+{
+    if (GRID) {
+        // the cells that can hold a frame within reach (as the query: |dx| <= largest radius, positions map to cells monotonically)
+        const float rmax = __uint_as_float(cb.cnt[1]);
+        const float reach = rmax * (1.0f + 2e-5f) + 1e-3f / cb.inv;
+        int cx0 = 0, cy0 = 0, cx1 = kEdG - 1, cy1 = kEdG - 1;
+        if (!wide) {
+            cx0 = sg_cell1(px - reach, cb.half, cb.inv);
+            cx1 = sg_cell1(px + reach, cb.half, cb.inv);
+            cy0 = sg_cell1(py - reach, cb.half, cb.inv);
+            cy1 = sg_cell1(py + reach, cb.half, cb.inv);
+        }
+        cx0 = uniform_i(cx0), cx1 = uniform_i(cx1), cy0 = uniform_i(cy0), cy1 = uniform_i(cy1);
+        const int ncx = cx1 - cx0 + 1, ncells = ncx * (cy1 - cy0 + 1);
+        for (int c0 = 0; c0 < ncells; c0 += 64) { // wave-uniform
+            const int c = c0 + lane;
+            int cell = 0, cnt = 0;
+            if (c < ncells) {
+                cell = (cy0 + c / ncx) * kEdG + cx0 + c % ncx;
+                cnt = int(min(cb.cnt[2 + cell], uint32_t(kCbK))); // every cell's count at once
+            }
+            int incl = cnt; // inclusive prefix over the wave
+            for (int d = 1; d < 64; d <<= 1) {
+                const int up = __shfl_up(incl, d);
+                if (lane >= d) incl += up;
+            }
+            const int total = uniform_i(__shfl(incl, 63));
+            if (total == 0) continue;
+            w_off[lane] = incl - cnt;
+            w_cell[lane] = cell;
+            if (lane == 63) w_off[64] = total;
+            __builtin_amdgcn_wave_barrier(); // (LDS traffic of one wave is in order; the compiler must not move it either)
+            for (int e = lane; e < total; e += 64) { // the entries, whichever cell they are in
+                int lo = 0;                              // the last cell whose first entry is <= e
+                for (int step = 32; step > 0; step >>= 1)
+                    if (w_off[lo + step] <= e) lo += step;
+                const int at = w_cell[lo] * kCbK + (e - w_off[lo]);
+                look(cb.bucket_f[at], cb.bucket_m[at], cb.bucket_t[at]);
+            }
+            __builtin_amdgcn_wave_barrier(); // (the next round rewrites the offsets)
+        }
+    }
+    const int n_every = uniform_i(int(cb.cnt[0]));
+    for (int e = lane; e < n_every; e += 64) look(cb.every_f[e], cb.every_m[e], cb.every_t[e]);
+}
+
+// the wave's sum of 128-bit values: four 32-bit limbs, each added across the lanes in 64 bits, carries once (k_cca_gate); mod 2^128,
+// as the query's sums
+RM_D U128 wave_sum_u128(const U128 acc)
+{
+    const unsigned long long l0 = wave_sum_u64(acc.lo & 0xFFFFFFFFull), l1 = wave_sum_u64(acc.lo >> 32);
+    const unsigned long long l2 = wave_sum_u64(acc.hi & 0xFFFFFFFFull), l3 = wave_sum_u64(acc.hi >> 32);
+    __builtin_amdgcn_wave_barrier();
+    U128 sum, part;
+    sum.lo = l0, sum.hi = l2;
+    part.lo = l1 << 32, part.hi = (l1 >> 32) + (l3 << 32);
+    return u128_add(sum, part);
+}
+
 } // namespace rm

@@ -277,6 +277,27 @@ struct CcaBatchDev {
     uint32_t *h_info;         // pinned: [0] pairs over all segments (0xFFFFFFFF: more than 2^32 - 2), [1] a segment ran over (cannot happen: sticky)
 };
 
+// A CSMA-CA gated batch (rm_csma.hip): the gated batch over EXPANDED lists.  Every attempt of every
+// packet has its tick before the batch starts (the backoff draw is a hash of the packet and the attempt number: rm_csma_schedule),
+// so every attempt is a slot of its tick -- CcaBatchDev's "candidate", with ticks[T].first / n over the expanded list and
+// ticks[b].src the caller's own list of tick b -- and the serial pass carries one state per packet on top of the kept bits.
+constexpr uint32_t kCsOwn = 0x80000000u;     // pair_slot: a frame of the slot's own node, of an earlier tick (RM_ED_TRANSMITTING if kept)
+constexpr uint32_t kCsSibling = 0x40000000u; // pair_slot: a slot of the same node at a lower position of the SAME tick (first wins)
+constexpr uint32_t kCsSlot = 0x3FFFFFFFu;
+constexpr uint8_t kCsHasSibling = 0x80;      // slot_flags: the slot's segment holds sibling pairs
+struct CsmaDev {
+    CcaBatchDev cb;            // n_cand = expanded slots of all ticks
+    const int32_t *origin;     // [slots] the slot's packet (flat index over the own lists) ...
+    const uint8_t *attempt;    // ... and attempt number: the pinned block that carries the tick descriptors
+    const int32_t *next_tick;  // [slots] the tick of the packet's next attempt (may be >= n_ticks), -1: this is attempt max_backoffs
+    const int32_t *own_first;  // [n_ticks + 1] packets before tick b's own list
+    int n_pkt;
+    uint8_t *state;            // [n_pkt] RM_CSMA_* while the ticks are walked; 0xFF: trying
+    uint8_t *tentative;        // [slots] made, flags 0 before the first-wins rule
+    uint8_t *slot_flags;       // [slots] the slot's flags before the first-wins rule | kCsHasSibling
+    rm_csma_result out;        // per packet, device memory; any pointer may be NULL
+};
+
 // A BATCH of SINR ticks whose frames outlive their tick (rm_airbatch.hip; BASELINE configs[4]).  The frames the batch can
 // see -- the window of frames still on the air from earlier calls, then the batch's ticks one after the other -- are ONE
 // array, cut into time slots (a window batch or a tick each).  The heard links of all ticks come from the sweep of the medium
@@ -747,6 +768,11 @@ hipError_t launch_cca_gate(hipStream_t s, const NodesDev &nd, const ModelDev &m,
 hipError_t launch_ccab_count(hipStream_t s, const NodesDev &nd, const ModelDev &m, const CcaBatchDev &cb, const CcaTick *h_ticks, CcaTick *d_ticks, bool grid);
 hipError_t launch_ccab_resolve(hipStream_t s, const NodesDev &nd, const ModelDev &m, const CcaBatchDev &cb, bool grid, double cca_threshold,
                                int32_t *gated, double *out_energy, uint8_t *out_flags);
+hipError_t launch_ccab_begin(hipStream_t s, const CcaBatchDev &cb, const CcaTick *h_ticks, CcaTick *d_ticks, bool grid);
+hipError_t launch_ccab_scan(hipStream_t s, const CcaBatchDev &cb);
+// the gate of a CSMA-CA gated batch (rm_csma.hip): the same two parts over the expanded slots
+hipError_t launch_csma_count(hipStream_t s, const NodesDev &nd, const ModelDev &m, const CsmaDev &cs, const CcaTick *h_ticks, CcaTick *d_ticks, bool grid);
+hipError_t launch_csma_resolve(hipStream_t s, const NodesDev &nd, const ModelDev &m, const CsmaDev &cs, bool grid, double cca_threshold, int32_t *gated);
 hipError_t launch_air_expire(hipStream_t s, rm_tx_record *recs, int n, int64_t t_seen); // (the on-air window when the clock goes back)
 hipError_t launch_tick_frames_batch(hipStream_t s, const NodesDev &nd, const ModelDev &m, const TickDev *ticks, int n,
                                     const TickDev *dev_ticks, const LaunchCfg &cfg, int seg_len);

@@ -354,7 +354,8 @@ struct rm_context : TickSlot {
             DevBuf<ulonglong2> pair_term, base;
             DevBuf<unsigned long long> pair_base;
             DevBuf<uint8_t> base_flags, kept;
-            char *h_desc = nullptr; // pinned, host-mapped: CcaTick[RM_MAX_BATCH], then the words the device hands back (CcaBatchDev::h_info)
+            char *h_desc = nullptr; // pinned, host-mapped: CcaTick[RM_MAX_BATCH], then the words the device hands back (CcaBatchDev::h_info),
+            size_t h_desc_extra = 0; // then this many bytes a CSMA-CA batch uploads its schedule from (cca_desc_block)
             void release_all()
             {
                 ticks.release(); scr.release(); cand.release(); fr_tick.release(); self_next.release(); bucket_t.release(); every_t.release();
@@ -362,8 +363,22 @@ struct rm_context : TickSlot {
                 every_f.release(); bucket_m.release(); every_m.release(); pair_term.release(); base.release(); pair_base.release(); base_flags.release(); kept.release();
                 if (h_desc) (void)hipHostFree(h_desc);
                 h_desc = nullptr;
+                h_desc_extra = 0;
             }
         } cb;
+        // what a CSMA-CA gated batch adds to it (rm_api_csma.cpp, rm_csma.hip; rm::CsmaDev): the schedule on the device, the packets'
+        // states, the slots' tentative bits; the host form's outputs before they are copied out
+        struct Csma {
+            DevBuf<char> sched;
+            DevBuf<uint8_t> state, tentative, slot_flags, o_status, o_attempts, o_flags;
+            DevBuf<int32_t> o_tick, o_pkt;
+            DevBuf<double> o_energy;
+            void release_all()
+            {
+                sched.release(); state.release(); tentative.release(); slot_flags.release(); o_status.release(); o_attempts.release();
+                o_flags.release(); o_tick.release(); o_pkt.release(); o_energy.release();
+            }
+        } cs;
     } ed;
     bool dev_records_from_caller = false; // the tick being prepared takes rm_tx_record arrays the caller built in device memory
     mutable rm::ModelDev mdev{};            // model_dev()'s last answer and what it was derived from
@@ -594,6 +609,19 @@ int energy_launch(rm_context *c, int64_t time_us, const int32_t *nodes, int32_t 
                   uint8_t *flags, int32_t *gated = nullptr);
 // the host forms' pinned, host-mapped block with room for n nodes: energies, node list, flags
 int energy_host_block(rm_context *c, int32_t n, double **h_energy, int32_t **h_nodes, uint8_t **h_flags);
+
+// ---- rm_api_cca.cpp
+// what a gated batch refuses before anything is launched: the arguments as such, then the ticks with the candidates each one senses
+int cca_batch_check_lists(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us, const int64_t *t_end_us, const int32_t *const *src,
+                          const int32_t *n_src, const int64_t *start_us, const int64_t *air_us, const int64_t *cca_time_us);
+int cca_batch_check_ticks(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us, const int32_t *n_per, const int64_t *start_us,
+                          const int64_t *air_us, const int64_t *cca_time_us);
+// the gated batches' pinned, host-mapped block: tick descriptors, the device's words, `extra` bytes to upload from
+int cca_desc_block(rm_context *c, size_t extra, rm::CcaTick **h_ticks, uint32_t **h_info, char **h_extra);
+// the gate's buffers and device view for n_cand candidates (all of rm::CcaBatchDev but the pair list), descriptors written, gated_v[b] set
+int cca_batch_dev(rm_context *c, size_t n_cand, int32_t n_ticks, const int32_t *const *src, const int32_t *n_per, const int64_t *start_us,
+                  const int64_t *air_us, const int64_t *cca_time_us, size_t extra, rm::CcaBatchDev *out, bool *use_grid, rm::CcaTick **h_ticks_out,
+                  const int32_t **gated_v, char **h_extra);
 
 // ---- rm_api_comm.cpp
 int comm_all_gather(rm_context *c, const void *mine, void *all, size_t bytes);

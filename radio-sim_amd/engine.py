@@ -664,6 +664,74 @@ class Engine:
                                                       st.ctypes.data, ai.ctypes.data, tc.ctypes.data, float(cca_threshold_dbm),
                                                       dev_flags_ptr, dev_energy_ptr))
 
+    @staticmethod
+    def csma_params(max_backoffs=None, min_be=None, max_be=None, seed=None, reserved=None):
+        """rm_csma_params: the library's defaults (4, 3, 5, seed 0) with the given fields replaced"""
+        p = _lib.CsmaParams()
+        _lib.lib().rm_csma_defaults(C.byref(p))
+        for name, v in (("max_backoffs", max_backoffs), ("min_be", min_be), ("max_be", max_be), ("seed", seed), ("reserved", reserved)):
+            if v is not None:
+                setattr(p, name, int(v))
+        return p
+
+    @staticmethod
+    def csma_schedule(params, n_src, cca_time_us, cap=None):
+        """The CSMA-CA schedule of a batch, on the host alone: -> (n_exp per tick, origin per expanded slot --
+        a flat packet index --, attempt per expanded slot); cap: the room offered for origin / attempt (default: what is needed)."""
+        cnt = np.ascontiguousarray(n_src, dtype=np.int32)
+        tc = np.ascontiguousarray(cca_time_us, dtype=np.int64)
+        assert len(cnt) == len(tc)
+        n_exp = np.zeros(len(cnt), dtype=np.int32)
+        total = C.c_int64(-1)
+        L = _lib.lib()
+        if cap is None:
+            check(L.rm_csma_schedule(C.byref(params), len(cnt), cnt.ctypes.data, tc.ctypes.data, n_exp.ctypes.data, None, None, 0, C.byref(total)))
+            cap = total.value
+        origin = np.zeros(max(int(cap), 1), dtype=np.int32)
+        attempt = np.zeros(max(int(cap), 1), dtype=np.uint8)
+        try:
+            check(L.rm_csma_schedule(C.byref(params), len(cnt), cnt.ctypes.data, tc.ctypes.data, n_exp.ctypes.data, origin.ctypes.data,
+                                     attempt.ctypes.data, int(cap), C.byref(total)))
+        except _lib.RadioMediumError as err:
+            err.total = total.value
+            raise
+        return n_exp, origin[:total.value], attempt[:total.value]
+
+    CSMA_FIELDS = (("status", np.uint8), ("attempts", np.uint8), ("tick", np.int32), ("pkt", np.int32), ("flags", np.uint8),
+                   ("energy_dbm", np.float64))
+
+    def batch_run_sources_csma(self, t_begin, t_end, src_lists, start_us, air_us, cca_time_us, cca_threshold_dbm, params, fields=None):
+        """A CSMA-CA gated batch: the gated batch in which a deferred candidate backs off and senses again in a
+        later tick.  -> ({field: flat array over the packets}, n_exp per tick); the ticks' results through batch_result_copy(b, n_exp[b]).
+        fields: the outputs to ask for (default: all of CSMA_FIELDS)."""
+        lists = [np.ascontiguousarray(s, dtype=np.int32) for s in src_lists]
+        tb, te, st, ai, tc, cnt = self._cca_batch_args(t_begin, t_end, [len(s) for s in lists], start_us, air_us, cca_time_us)
+        assert len(lists) == len(tb)
+        ptrs = np.array([s.ctypes.data if len(s) else 0 for s in lists], dtype=np.uint64)
+        total = int(cnt.sum())
+        want = [f for f, _ in self.CSMA_FIELDS] if fields is None else list(fields)
+        out = {f: np.empty(max(total, 1), dtype=t) for f, t in self.CSMA_FIELDS if f in want}
+        res = _lib.CsmaResult(**{f: a.ctypes.data for f, a in out.items()})
+        n_exp = np.zeros(len(lists), dtype=np.int32)
+        check(self._L.rm_batch_run_sources_csma(self._h, len(lists), tb.ctypes.data, te.ctypes.data, ptrs.ctypes.data, cnt.ctypes.data,
+                                                st.ctypes.data, ai.ctypes.data, tc.ctypes.data, float(cca_threshold_dbm), C.byref(params),
+                                                C.byref(res), n_exp.ctypes.data))
+        return {f: a[:total] for f, a in out.items()}, n_exp
+
+    def batch_run_sources_csma_device(self, t_begin, t_end, dev_src_ptrs, n_src, start_us, air_us, cca_time_us, cca_threshold_dbm, params,
+                                      dev_out=None):
+        """The raw form: device lists; dev_out: {field: device pointer} for the outputs wanted (flat, sum(n_src) entries each); the
+        callers' lists are not written.  -> n_exp per tick."""
+        tb, te, st, ai, tc, cnt = self._cca_batch_args(t_begin, t_end, n_src, start_us, air_us, cca_time_us)
+        ptrs = np.ascontiguousarray([p or 0 for p in dev_src_ptrs], dtype=np.uint64)
+        assert len(ptrs) == len(tb)
+        res = _lib.CsmaResult(**(dev_out or {}))
+        n_exp = np.zeros(len(ptrs), dtype=np.int32)
+        check(self._L.rm_batch_run_sources_csma_device(self._h, len(ptrs), tb.ctypes.data, te.ctypes.data, ptrs.ctypes.data, cnt.ctypes.data,
+                                                       st.ctypes.data, ai.ctypes.data, tc.ctypes.data, float(cca_threshold_dbm),
+                                                       C.byref(params), C.byref(res) if dev_out is not None else None, n_exp.ctypes.data))
+        return n_exp
+
     def sync(self):
         check(self._L.rm_sync(self._h))
 

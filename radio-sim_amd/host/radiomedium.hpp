@@ -811,6 +811,103 @@ public:
         }
         return flags;
     }
+    // The CSMA-CA schedule of a batch (extension E8), on the host alone: the expanded lists' lengths, and per expanded slot in tick
+    // order its packet (flat index over the ticks' own lists) and attempt number.  false and lastError on a refusal.
+    struct CsmaSchedule {
+        std::vector<int32_t> n_exp, origin;
+        std::vector<uint8_t> attempt;
+    };
+    bool csmaSchedule(const rm_csma_params &p, const std::vector<int32_t> &n_src, const std::vector<int64_t> &cca_time_us, CsmaSchedule &out)
+    {
+        lastError.clear();
+        if (n_src.empty() || n_src.size() != cca_time_us.size()) { lastError = "one entry per tick"; return false; }
+        out.n_exp.assign(n_src.size(), 0);
+        int64_t total = 0;
+        if (rm_csma_schedule(&p, int32_t(n_src.size()), n_src.data(), cca_time_us.data(), out.n_exp.data(), nullptr, nullptr, 0, &total) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        out.origin.assign(size_t(total) + 1, 0);
+        out.attempt.assign(size_t(total) + 1, 0);
+        if (rm_csma_schedule(&p, int32_t(n_src.size()), n_src.data(), cca_time_us.data(), out.n_exp.data(), out.origin.data(), out.attempt.data(),
+                             total, &total) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        out.origin.resize(size_t(total));
+        out.attempt.resize(size_t(total));
+        return true;
+    }
+    // Listen before talk with retries across a batch of ticks (extension E8): as transmitIfClearBatch, but a sender that defers
+    // backs off and senses again in a later tick of the batch (rm_csma_params), up to max_backoffs times.  Returns one entry per
+    // sender in tick order (empty and lastError on a refusal); a packet that was sent starts at the start_us of the tick it was
+    // sent in, and generates its events there, in the order of that tick's expanded list.
+    struct CsmaOutcome {
+        uint8_t status, attempts, flags; // RM_CSMA_*, attempts made, RM_ED_* of the last one
+        int32_t tick, pkt;               // sent: the tick and the position in its expanded list; pending: the tick of the next attempt
+    };
+    std::vector<CsmaOutcome> transmitCsmaBatch(const std::vector<std::vector<Node *>> &senders, const std::vector<int64_t> &t_begin_us,
+                                               const std::vector<int64_t> &start_us, int64_t hex_length, const std::vector<int64_t> &cca_time_us,
+                                               double threshold_dbm, const rm_csma_params &p)
+    {
+        lastError.clear();
+        Simulator *sim = simulator;
+        if (!sim) { lastError = "No simulator"; return {}; }
+        const size_t nt = senders.size();
+        if (nt == 0 || t_begin_us.size() != nt || start_us.size() != nt || cca_time_us.size() != nt) { lastError = "one entry per tick"; return {}; }
+        if (!syncNodes()) return {};
+        const std::vector<Node *> &nodes = sim->getNodes();
+        rm_set_time(ctx_, sim->getTime());
+        std::vector<std::vector<int32_t>> src(nt);
+        std::vector<const int32_t *> lists(nt);
+        std::vector<int32_t> n_src(nt), n_exp(nt, 0);
+        std::vector<int64_t> air(nt, rm_air_time_us(hex_length));
+        std::vector<Node *> flat;
+        for (size_t b = 0; b < nt; ++b) {
+            src[b].resize(senders[b].size());
+            for (size_t i = 0; i < senders[b].size(); ++i) src[b][i] = senders[b][i] ? senders[b][i]->index : -1;
+            lists[b] = src[b].data();
+            n_src[b] = int32_t(src[b].size());
+            flat.insert(flat.end(), senders[b].begin(), senders[b].end());
+        }
+        const size_t total = flat.size();
+        std::vector<uint8_t> status(total + 1, 0), attempts(total + 1, 0), flags(total + 1, 0);
+        std::vector<int32_t> tick(total + 1, -1), pkt(total + 1, -1);
+        const rm_csma_result res = {status.data(), attempts.data(), tick.data(), pkt.data(), flags.data(), nullptr};
+        if (rm_batch_run_sources_csma(ctx_, int32_t(nt), t_begin_us.data(), start_us.data(), lists.data(), n_src.data(), start_us.data(), air.data(),
+                                      cca_time_us.data(), threshold_dbm, &p, &res, n_exp.data()) != RM_OK) {
+            lastError = rm_last_error();
+            return {};
+        }
+        std::vector<CsmaOutcome> out(total);
+        std::vector<std::vector<std::pair<int32_t, size_t>>> sent(nt); // per tick: (position in the expanded list, packet)
+        for (size_t o = 0; o < total; ++o) {
+            out[o] = CsmaOutcome{status[o], attempts[o], flags[o], tick[o], pkt[o]};
+            if (status[o] == RM_CSMA_SENT) sent[size_t(tick[o])].emplace_back(pkt[o], o);
+        }
+        if (ccaDst_.empty()) { ccaDst_.resize(1024); ccaVerdict_.resize(1024); ccaRssi_.resize(1024); }
+        const std::string data(size_t(hex_length), '0');
+        for (size_t b = 0; b < nt; ++b) {
+            std::sort(sent[b].begin(), sent[b].end());
+            std::vector<uint32_t> off(size_t(n_exp[b]) + 1, 0);
+            uint32_t heard = 0;
+            for (int attempt = 0; attempt < 2; ++attempt) {
+                const int rc = rm_batch_result_copy(ctx_, int32_t(b), nullptr, ccaDst_.data(), ccaVerdict_.data(), ccaRssi_.data(), nullptr,
+                                                    uint32_t(ccaDst_.size()), &heard, nullptr, off.data());
+                if (rc == RM_OK) break;
+                if (attempt == 1 || heard <= ccaDst_.size()) { lastError = rm_last_error(); return {}; }
+                ccaDst_.resize(heard); ccaVerdict_.resize(heard); ccaRssi_.resize(heard);
+            }
+            for (const std::pair<int32_t, size_t> &q : sent[b]) {
+                ccaSent_.emplace_back(new RadioPacket(flat[q.second], start_us[b], data));
+                RadioPacket &packet = *ccaSent_.back();
+                sim->generateTransmissionEvents(packet);
+                for (uint32_t k = off[size_t(q.first)]; k < off[size_t(q.first) + 1]; ++k)
+                    sim->generateReceptionEvents(packet, nodes[size_t(ccaDst_[k])], ccaRssi_[k], ccaVerdict_[k] == RM_DELIVERED);
+            }
+        }
+        return out;
+    }
 
 private:
     std::vector<std::unique_ptr<RadioPacket>> ccaSent_;
