@@ -559,8 +559,8 @@ int rm_batch_run_sources_cca(rm_context *ctx, int32_t n_ticks, const int64_t *t_
  *    rm_batch_run_sources_cca* bit for bit.
  * Refused before anything is launched, window unchanged: everything rm_batch_run_sources_cca* refuses, with its codes (the
  * 8192-candidate limit of an overlapping tick applies to n_exp[T]); RM_ERR_INVALID for parameters out of range or reserved != 0.
- * Not promised: invariance under splitting a batch -- a pending packet's chain ends with the batch; carrying a chain into the next
- * batch (an attempt offset on input) is a follow-up.  The gathered forms, rm_dist_* and rm_group_* are not gated. */
+ * A pending packet's chain ends with the batch; rm_batch_run_sources_csma_carry* below (E9) takes it into the next batch, and with it
+ * any split into consecutive batches gives the result of the whole.  The gathered forms, rm_dist_* and rm_group_* are not gated. */
 #define RM_CSMA_NONE 0
 #define RM_CSMA_SENT 1
 #define RM_CSMA_FAILED 2
@@ -596,6 +596,73 @@ int rm_batch_run_sources_csma(rm_context *ctx, int32_t n_ticks, const int64_t *t
                               const int32_t *const *src, const int32_t *n_src, const int64_t *start_us, const int64_t *air_us,
                               const int64_t *cca_time_us, double cca_threshold_dbm, const rm_csma_params *p,
                               const rm_csma_result *out, int32_t *n_exp);
+
+/* ---- CSMA-CA gated batch with a carry: pending packets go on in the next batch ------------------------------------
+ * (not reference behaviour.)  rm_batch_run_sources_csma* plus a list of CARRIED packets: packets
+ * of earlier batches whose next attempt was behind their batch's last tick (RM_CSMA_PENDING).  A carried packet is a packet like
+ * any other: its attempt number `attempt` is in tick `tick` of THIS batch, and its later attempts follow E8's formula with h1 made of
+ * origin_cca_time_us, k = origin_slot and the attempt number running on.
+ *  - The EXPANDED list of tick T holds, in this order: the tick's own entries; the attempts of carried packets that fall at T, in
+ *    carry-list order; the retries of this batch's own packets, in (origin tick, origin slot) order.
+ *  - A carried packet's first attempt inside this batch is made unconditionally, its later ones iff all earlier ones in this batch
+ *    were made and deferred.  Sensing is exactly E8's, and so is the one-frame-per-radio-per-tick rule: the first in list order
+ *    wins.  Two carried packets of one node are allowed.
+ *  - carried_out is flat with n_carry entries (device memory in the device form; any pointer may be NULL): status, tick (relative
+ *    to this batch) and pkt as E8; attempts is the TOTAL, the attempts made before this batch included; flags and energy_dbm are
+ *    those of the last attempt made in this batch.  A carried packet with tick >= n_ticks has no slot: RM_CSMA_PENDING, attempts =
+ *    attempt, tick unchanged, pkt -1, flags 0, energy NaN.
+ *  - With n_carry = 0 the call IS rm_batch_run_sources_csma*, bit for bit (those entry points are this call).
+ * Refused before anything is launched, window unchanged: everything E8 refuses, with its codes (the 8192 limit of an overlapping
+ * tick applies to n_exp[T], carried slots included; RM_ERR_CAPACITY for more than 2^27 packets and carried packets together);
+ * RM_ERR_INVALID for n_carry < 0, n_carry > 0 with carry NULL, a node outside 0 .. n_nodes-1, an attempt outside 1 .. max_backoffs,
+ * tick < 0, origin_slot < 0.
+ * rm_csma_carry_collect* make the next batch's carry list from a batch's results: the RM_CSMA_PENDING carried packets in carry-in
+ * order, then the RM_CSMA_PENDING own packets in flat order, each with tick - n_ticks and attempt = attempts (only status, attempts
+ * and tick are read).  That order is part of the contract: it is what makes the next batch's expanded lists those of the unsplit batch.
+ * THE PROMISE: a CSMA-CA batch over ticks 0 .. N-1 and any split of it into consecutive carry batches, each fed the collected
+ * carry-out of the one before, sense the same attempts with the same result, put the same frames on the air in the same ticks,
+ * give the same heard links (dst, verdict, rssi, sinr, bit for bit, in the same order), leave the same on-air window, and give
+ * every packet the same final status, attempts, absolute tick, flags and energy bits -- a packet's final entry being that of the
+ * part in which it stopped being pending, with flags and energy of the last part in which it made an attempt.
+ * PACKET NUMBERS are the one difference.  E8 schedules every attempt of every packet, made or not: the whole batch keeps a padding
+ * slot (nothing sensed, an empty segment in pkt_offset) for each later attempt of a packet that was sent already.  A carry holds
+ * pending packets only, so in the part after a cut those dead slots of packets from before the cut do not exist: n_exp[T] of the
+ * part is the whole's minus its dead slots of T, and pkt, the links' pkt column and pkt_offset count positions among the
+ * surviving slots, whose order is the whole's. */
+typedef struct rm_csma_carry {  /* 24 bytes; always a HOST array, in both forms */
+    int64_t origin_cca_time_us; /* cca_time_us of the packet's ORIGIN tick (what its backoff hash h1 is made of) */
+    int32_t origin_slot;        /* its position k in the origin tick's own list (>= 0) */
+    int32_t node;               /* 0 .. n_nodes-1 */
+    int32_t tick;               /* tick of its next attempt, relative to THIS batch; >= 0, may be >= n_ticks */
+    int32_t attempt;            /* number of that attempt: 1 .. max_backoffs (= attempts made so far) */
+} rm_csma_carry;
+/* pure host function: rm_csma_schedule plus the carried packets; in origin[] a carried slot is n_pkt + its carry index */
+int rm_csma_schedule_carry(const rm_csma_params *p, int32_t n_ticks, const int32_t *n_src, const int64_t *cca_time_us,
+                           const rm_csma_carry *carry, int32_t n_carry, int32_t *n_exp, int32_t *origin, uint8_t *attempt, int64_t cap,
+                           int64_t *total);
+/* as rm_batch_run_sources_csma_device; dev_carried_out's pointers device memory, n_carry entries each */
+int rm_batch_run_sources_csma_carry_device(rm_context *ctx, int32_t n_ticks, const int64_t *t_begin_us, const int64_t *t_end_us,
+                                           const int32_t *const *dev_src, const int32_t *n_src, const int64_t *start_us,
+                                           const int64_t *air_us, const int64_t *cca_time_us, double cca_threshold_dbm,
+                                           const rm_csma_params *p, const rm_csma_result *dev_out, int32_t *n_exp,
+                                           const rm_csma_carry *carry, int32_t n_carry, const rm_csma_result *dev_carried_out);
+/* as rm_batch_run_sources_csma; carried_out's pointers host arrays */
+int rm_batch_run_sources_csma_carry(rm_context *ctx, int32_t n_ticks, const int64_t *t_begin_us, const int64_t *t_end_us,
+                                    const int32_t *const *src, const int32_t *n_src, const int64_t *start_us, const int64_t *air_us,
+                                    const int64_t *cca_time_us, double cca_threshold_dbm, const rm_csma_params *p,
+                                    const rm_csma_result *out, int32_t *n_exp, const rm_csma_carry *carry, int32_t n_carry,
+                                    const rm_csma_result *carried_out);
+/* host results and host lists, no device needed.  carry_out: cap entries; *count = the entries the carry-out holds, also when cap is
+ * too small (then RM_ERR_CAPACITY, carry_out unspecified).  out / carried_out: status, attempts and tick have to be there unless the
+ * table is empty. */
+int rm_csma_carry_collect(int32_t n_ticks, const int32_t *const *src, const int32_t *n_src, const int64_t *cca_time_us,
+                          const rm_csma_carry *carry, int32_t n_carry, const rm_csma_result *out, const rm_csma_result *carried_out,
+                          rm_csma_carry *carry_out, int64_t cap, int64_t *count);
+/* device results (as the device form wrote them) and device lists; carry and carry_out are host arrays.  Ordered on the context's
+ * stream after the batch; synchronises once. */
+int rm_csma_carry_collect_device(rm_context *ctx, int32_t n_ticks, const int32_t *const *dev_src, const int32_t *n_src,
+                                 const int64_t *cca_time_us, const rm_csma_carry *carry, int32_t n_carry, const rm_csma_result *dev_out,
+                                 const rm_csma_result *dev_carried_out, rm_csma_carry *carry_out, int64_t cap, int64_t *count);
 
 /* ---- several devices behind one caller --------------------------------------------------------------
  * The reference host is ONE process (Main.java:65-73): a group drives n contexts from one host thread, one

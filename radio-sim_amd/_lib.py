@@ -38,6 +38,12 @@ class CsmaResult(C.Structure):
                 ("energy_dbm", C.c_void_p)]
 
 
+class CsmaCarry(C.Structure):
+    """rm_csma_carry: a pending packet on its way into the next CSMA-CA gated batch (24 bytes)"""
+    _fields_ = [("origin_cca_time_us", C.c_int64), ("origin_slot", C.c_int32), ("node", C.c_int32), ("tick", C.c_int32),
+                ("attempt", C.c_int32)]
+
+
 class ModelParams(C.Structure):
     _fields_ = [("kind", C.c_int32), ("flags", C.c_int32),
                 ("udgm_success_ratio_tx", C.c_double), ("udgm_success_ratio_rx", C.c_double),
@@ -252,6 +258,18 @@ SIGNATURES = {
                                                    C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rm_batch_run_sources_csma": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_csma_schedule_carry": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "rm_batch_run_sources_csma_carry_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_int32, C.c_void_p]),
+    "rm_batch_run_sources_csma_carry": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                  C.c_void_p]),
+    "rm_csma_carry_collect": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "rm_csma_carry_collect_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "rm_det_math": (C.c_double, [C.c_int32, C.c_double]),
     "rm_link_hash": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
     "rm_evq_init": (None, [C.c_void_p]),

@@ -1,4 +1,4 @@
-// rm_csma.hip -- the gate of a CSMA-CA gated BATCH (rm_batch_run_sources_csma*)
+// rm_csma.hip -- the gate of a CSMA-CA gated BATCH (rm_batch_run_sources_csma*, _carry*)
 // (part of libradiomedium_hip.so; gfx950 only, -ffp-contract=off, no fast-math)
 //
 // A candidate that finds the channel busy draws a backoff and senses again in a later tick of the batch.  The draw is a hash of the
@@ -15,6 +15,11 @@
 //                    is tentative (one frame per radio per tick: the first in list order wins); kept bit, gated entry, the packet's
 //                    state and outputs.  Tentative bits are read and kept bits written in separate arrays.
 // The descriptors' copy and the counts' scan are the gated batch's own kernels (launch_ccab_begin, launch_ccab_scan).
+// A CARRIED packet (E9) is packet n_pkt + c of the same arrays: its node comes from its carry record, its outputs go to the carried
+// table, the first slot of its chain in this batch is marked (kCsFirst) as an own packet's attempt 0 is; one without a slot gets its
+// entry before tick 0.
+//   k_csma_collect   the carry-out: a stable compaction of the RM_CSMA_PENDING entries, carried table first -- a count per workgroup
+//                    (wave ballots), one workgroup's prefix over the counts, then every pending entry's record at its rank.
 #include "rm_device.hpp"
 
 namespace rm {
@@ -22,6 +27,8 @@ namespace rm {
 constexpr int kCsResolve = 1024;       // threads of the one workgroup that resolves
 constexpr uint8_t kCsTrying = 0xFF;    // CsmaDev::state: attempts so far were made and deferred, another one is scheduled
 constexpr uint8_t kCsMade = 0x40;      // CsmaDev::slot_flags: the slot's attempt was made
+constexpr int kCsCollect = 256;        // threads of a workgroup of the collect passes: an entry each
+constexpr int kCsScan = 1024;          // threads of the one workgroup that scans their counts
 
 template <bool GRID>
 __global__ void __launch_bounds__(256) k_csma_index(const NodesDev nd, const ModelDev m, const CsmaDev cs)
@@ -46,13 +53,18 @@ __global__ void __launch_bounds__(256) k_csma_index(const NodesDev nd, const Mod
         }
         tk = lo;
         const int o = cs.origin[s];
-        lo = 0, hi = cb.n_ticks - 1; // the origin tick: the last one whose first packet is <= o
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (cs.own_first[mid] <= o) lo = mid;
-            else hi = mid - 1;
+        int j;
+        if (o >= cs.n_pkt) { // a carried packet: (the host has checked its node)
+            j = cs.carry[o - cs.n_pkt].node;
+        } else {
+            lo = 0, hi = cb.n_ticks - 1; // the origin tick: the last one whose first packet is <= o
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (cs.own_first[mid] <= o) lo = mid;
+                else hi = mid - 1;
+            }
+            j = cb.ticks[lo].src[o - cs.own_first[lo]];
         }
-        const int j = cb.ticks[lo].src[o - cs.own_first[lo]];
         r = make_tx_record(nd, j, cb.ticks[tk].start_us, cb.ticks[tk].air_us); // (an entry outside 0 .. n-1: a padding record)
         cb.scr[s] = r;
         cb.cand[s] = r.src;
@@ -170,10 +182,31 @@ __global__ void __launch_bounds__(256) k_csma_pairs(const NodesDev nd, const Mod
     cb.pair_fill[i] = min(s_np[wave], cap);
 }
 
+// a carried packet whose next attempt is behind the batch has no slot: still pending, nothing sensed
+RM_D void cs_slotless(const CsmaDev &cs, int c, int n_ticks)
+{
+    const rm_csma_carry r = cs.carry[c];
+    if (r.tick < n_ticks) return;
+    cs.state[cs.n_pkt + c] = uint8_t(RM_CSMA_PENDING);
+    if (cs.carried.status) cs.carried.status[c] = uint8_t(RM_CSMA_PENDING);
+    if (cs.carried.attempts) cs.carried.attempts[c] = uint8_t(r.attempt);
+    if (cs.carried.tick) cs.carried.tick[c] = r.tick;
+    if (cs.carried.pkt) cs.carried.pkt[c] = -1;
+    if (cs.carried.flags) cs.carried.flags[c] = 0;
+    if (cs.carried.energy_dbm) cs.carried.energy_dbm[c] = __builtin_nan("");
+}
+
+__global__ void __launch_bounds__(256) k_csma_slotless(const CsmaDev cs, int n_ticks)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < cs.n_carry) cs_slotless(cs, c, n_ticks);
+}
+
 // ONE workgroup, the ticks in order: what a slot of tick T needs of ticks 0 .. T-1 is their kept bits and its packet's state
 __global__ void __launch_bounds__(kCsResolve) k_csma_resolve(const CsmaDev cs, double noise_lin, double cca_threshold, int32_t *gated)
 {
     const CcaBatchDev &cb = cs.cb;
+    for (int c = threadIdx.x; c < cs.n_carry; c += kCsResolve) cs_slotless(cs, c, cb.n_ticks); // (entries no slot writes)
     for (int T = 0; T < cb.n_ticks; ++T) { // block-uniform
         const int first = cb.ticks[T].first, n = cb.ticks[T].n;
         // phase 1: every made slot's flags, before the first-wins rule
@@ -181,7 +214,7 @@ __global__ void __launch_bounds__(kCsResolve) k_csma_resolve(const CsmaDev cs, d
             const int i = first + k;
             const int j = cb.cand[i];
             const int o = cs.origin[i];
-            const bool made = j >= 0 && (cs.attempt[i] == 0 || cs.state[o] == kCsTrying);
+            const bool made = j >= 0 && ((cs.attempt[i] & kCsFirst) || cs.state[o] == kCsTrying);
             uint32_t flags = 0u, mark = 0u;
             if (made) {
                 const ulonglong2 b0 = cb.base[i];
@@ -217,7 +250,8 @@ __global__ void __launch_bounds__(kCsResolve) k_csma_resolve(const CsmaDev cs, d
                 }
                 const double energy = 10.0 * det_log10(q80_to_double(sum) + noise_lin);
                 if (energy >= cca_threshold) flags |= uint32_t(RM_ED_BUSY); // (a NaN threshold never sets it)
-                if (cs.out.energy_dbm) cs.out.energy_dbm[o] = energy;       // (a chain's attempts are in different ticks: one writer)
+                double *const o_energy = o >= cs.n_pkt ? cs.carried.energy_dbm : cs.out.energy_dbm;
+                if (o_energy) o_energy[o >= cs.n_pkt ? o - cs.n_pkt : o] = energy; // (a chain's attempts are in different ticks: one writer)
             }
             cs.tentative[i] = (made && flags == 0u) ? 1 : 0;
             cs.slot_flags[i] = uint8_t(flags | mark);
@@ -228,7 +262,8 @@ __global__ void __launch_bounds__(kCsResolve) k_csma_resolve(const CsmaDev cs, d
             const int i = first + k;
             const int j = cb.cand[i];
             const int o = cs.origin[i];
-            const int a = cs.attempt[i];
+            const int a = cs.attempt[i] & ~kCsFirst; // (a carried packet's attempts count on from those made before this batch)
+            const bool chain_first = cs.attempt[i] & kCsFirst;
             const uint32_t sf = cs.slot_flags[i];
             uint32_t flags = sf & uint32_t(RM_ED_TRANSMITTING | RM_ED_BUSY);
             bool keep = cs.tentative[i] != 0;
@@ -246,14 +281,22 @@ __global__ void __launch_bounds__(kCsResolve) k_csma_resolve(const CsmaDev cs, d
                 const int nt = cs.next_tick[i];
                 const uint8_t st = keep ? uint8_t(RM_CSMA_SENT) : nt < 0 ? uint8_t(RM_CSMA_FAILED) : nt >= cb.n_ticks ? uint8_t(RM_CSMA_PENDING) : kCsTrying;
                 cs.state[o] = st;
-                if (cs.out.attempts) cs.out.attempts[o] = uint8_t(a + 1);
-                if (cs.out.flags) cs.out.flags[o] = uint8_t(flags);
+                // the table the packet belongs to
+                const bool car = o >= cs.n_pkt;
+                const int e = car ? o - cs.n_pkt : o;
+                uint8_t *const o_status = car ? cs.carried.status : cs.out.status;
+                uint8_t *const o_attempts = car ? cs.carried.attempts : cs.out.attempts;
+                uint8_t *const o_flags = car ? cs.carried.flags : cs.out.flags;
+                int32_t *const o_tick = car ? cs.carried.tick : cs.out.tick;
+                int32_t *const o_pkt = car ? cs.carried.pkt : cs.out.pkt;
+                if (o_attempts) o_attempts[e] = uint8_t(a + 1);
+                if (o_flags) o_flags[e] = uint8_t(flags);
                 if (st != kCsTrying) {
-                    if (cs.out.status) cs.out.status[o] = st;
-                    if (cs.out.tick) cs.out.tick[o] = keep ? T : st == RM_CSMA_PENDING ? nt : -1;
-                    if (cs.out.pkt) cs.out.pkt[o] = keep ? k : -1;
+                    if (o_status) o_status[e] = st;
+                    if (o_tick) o_tick[e] = keep ? T : st == RM_CSMA_PENDING ? nt : -1;
+                    if (o_pkt) o_pkt[e] = keep ? k : -1;
                 }
-            } else if (a == 0) { // a padding entry: a packet that never attempts
+            } else if (chain_first) { // a padding entry: a packet that never attempts (an own one: a carried packet's node is a node)
                 cs.state[o] = uint8_t(RM_CSMA_NONE);
                 if (cs.out.status) cs.out.status[o] = uint8_t(RM_CSMA_NONE);
                 if (cs.out.attempts) cs.out.attempts[o] = 0;
@@ -265,6 +308,100 @@ __global__ void __launch_bounds__(kCsResolve) k_csma_resolve(const CsmaDev cs, d
         }
         __syncthreads(); // (the tick's kept bits and states, for every later tick)
     }
+}
+
+// ---- the carry-out (E9) ---------------------------------------------------------------------------------------------------------
+// entry e of the two tables as one: the carried packets, then the own ones
+RM_D bool cc_pending(const CsmaCollectDev &cc, int e)
+{
+    if (e >= cc.n_carry + cc.n_pkt) return false;
+    return (e < cc.n_carry ? cc.status[0][e] : cc.status[1][e - cc.n_carry]) == uint8_t(RM_CSMA_PENDING);
+}
+
+// FILL = false: the workgroup's pending entries; FILL = true (after the scan): every pending entry's record at its rank
+template <bool FILL>
+__global__ void __launch_bounds__(kCsCollect) k_csma_collect(const CsmaCollectDev cc)
+{
+    __shared__ uint32_t s_wave[kCsCollect / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = wave_index();
+    const int e = blockIdx.x * kCsCollect + tid;
+    const bool pending = cc_pending(cc, e);
+    const unsigned long long mask = __ballot(pending);
+    if (lane == 0) s_wave[wave] = uint32_t(__popcll(mask));
+    __syncthreads();
+    if (!FILL) {
+        if (tid == 0) {
+            uint32_t sum = 0u;
+            for (int w = 0; w < kCsCollect / 64; ++w) sum += s_wave[w];
+            cc.block_cnt[blockIdx.x] = sum;
+        }
+        return;
+    }
+    if (!pending) return;
+    unsigned long long rank = cc.block_cnt[blockIdx.x];
+    for (int w = 0; w < wave; ++w) rank += s_wave[w];
+    rank += uint32_t(__popcll(mask & ((1ull << lane) - 1ull)));
+    if (rank >= (unsigned long long)cc.cap) return; // (the host reports RM_ERR_CAPACITY with the count)
+    rm_csma_carry r;
+    if (e < cc.n_carry) {
+        r = cc.carry[e];
+        r.tick = cc.tick[0][e] - cc.n_ticks;
+        r.attempt = cc.attempts[0][e];
+    } else {
+        const int o = e - cc.n_carry;
+        int lo = 0, hi = cc.n_ticks - 1; // the origin tick: the last one whose first packet is <= o
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (cc.own_first[mid] <= o) lo = mid;
+            else hi = mid - 1;
+        }
+        r.origin_cca_time_us = cc.cca_us[lo];
+        r.origin_slot = o - cc.own_first[lo];
+        r.node = cc.src[lo][r.origin_slot];
+        r.tick = cc.tick[1][o] - cc.n_ticks;
+        r.attempt = cc.attempts[1][o];
+    }
+    cc.h_out[rank] = r;
+}
+
+// one workgroup: the workgroups' counts -> the entries before each of them; the total for the host
+__global__ void __launch_bounds__(kCsScan) k_csma_collect_scan(const CsmaCollectDev cc, int n_blocks)
+{
+    __shared__ unsigned long long s_sum[kCsScan];
+    const int tid = threadIdx.x;
+    unsigned long long before = 0ull;
+    for (int k0 = 0; k0 < n_blocks; k0 += kCsScan) { // block-uniform
+        const int k = k0 + tid;
+        const unsigned long long own = k < n_blocks ? cc.block_cnt[k] : 0ull;
+        s_sum[tid] = own;
+        __syncthreads();
+        for (int d = 1; d < kCsScan; d <<= 1) {
+            const unsigned long long add = tid >= d ? s_sum[tid - d] : 0ull;
+            __syncthreads();
+            s_sum[tid] += add;
+            __syncthreads();
+        }
+        // (a carry-out of 2^32 entries or more does not exist: at most 2^27 packets)
+        if (k < n_blocks) cc.block_cnt[k] = uint32_t(before + s_sum[tid] - own);
+        before += s_sum[kCsScan - 1];
+        __syncthreads();
+    }
+    if (tid == 0) *cc.h_count = before;
+}
+
+hipError_t launch_csma_collect(hipStream_t s, const CsmaCollectDev &cc)
+{
+    const int n_blocks = cdiv(cc.n_carry + cc.n_pkt, kCsCollect);
+    RM_KLAUNCH((k_csma_collect<false>), dim3(n_blocks), dim3(kCsCollect), 0, s, cc);
+    RM_KLAUNCH(k_csma_collect_scan, dim3(1), dim3(kCsScan), 0, s, cc, n_blocks);
+    RM_KLAUNCH((k_csma_collect<true>), dim3(n_blocks), dim3(kCsCollect), 0, s, cc);
+    return hipGetLastError();
+}
+
+hipError_t launch_csma_slotless(hipStream_t s, const CsmaDev &cs)
+{
+    RM_KLAUNCH(k_csma_slotless, dim3(cdiv(cs.n_carry, 256)), dim3(256), 0, s, cs, cs.cb.n_ticks);
+    return hipGetLastError();
 }
 
 hipError_t launch_csma_count(hipStream_t s, const NodesDev &nd, const ModelDev &m, const CsmaDev &cs, const CcaTick *h_ticks, CcaTick *d_ticks, bool grid)

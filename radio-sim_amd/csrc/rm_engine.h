@@ -285,17 +285,37 @@ constexpr uint32_t kCsOwn = 0x80000000u;     // pair_slot: a frame of the slot's
 constexpr uint32_t kCsSibling = 0x40000000u; // pair_slot: a slot of the same node at a lower position of the SAME tick (first wins)
 constexpr uint32_t kCsSlot = 0x3FFFFFFFu;
 constexpr uint8_t kCsHasSibling = 0x80;      // slot_flags: the slot's segment holds sibling pairs
+constexpr uint8_t kCsFirst = 0x80;           // CsmaDev::attempt: the first slot of its packet's chain in this batch
 struct CsmaDev {
     CcaBatchDev cb;            // n_cand = expanded slots of all ticks
     const int32_t *origin;     // [slots] the slot's packet (flat index over the own lists) ...
-    const uint8_t *attempt;    // ... and attempt number: the pinned block that carries the tick descriptors
+    const uint8_t *attempt;    // ... and attempt number | kCsFirst: the pinned block that carries the tick descriptors
     const int32_t *next_tick;  // [slots] the tick of the packet's next attempt (may be >= n_ticks), -1: this is attempt max_backoffs
     const int32_t *own_first;  // [n_ticks + 1] packets before tick b's own list
     int n_pkt;
-    uint8_t *state;            // [n_pkt] RM_CSMA_* while the ticks are walked; 0xFF: trying
+    const rm_csma_carry *carry; // [n_carry] the carried packets (E9): packet n_pkt + c, from the same pinned block
+    int n_carry;
+    uint8_t *state;            // [n_pkt + n_carry] RM_CSMA_* while the ticks are walked; 0xFF: trying
     uint8_t *tentative;        // [slots] made, flags 0 before the first-wins rule
     uint8_t *slot_flags;       // [slots] the slot's flags before the first-wins rule | kCsHasSibling
     rm_csma_result out;        // per packet, device memory; any pointer may be NULL
+    rm_csma_result carried;    // per carried packet, the same
+};
+
+// The carry-out of a CSMA-CA gated batch (k_csma_collect; E9): a stable compaction of the RM_CSMA_PENDING entries of the carried
+// table, then of the own table, into rm_csma_carry records in a pinned block.
+struct CsmaCollectDev {
+    const int32_t *const *src; // [n_ticks] the batch's own lists (device memory)
+    const int32_t *own_first;  // [n_ticks + 1]
+    const int64_t *cca_us;     // [n_ticks]
+    const rm_csma_carry *carry; // [n_carry] the carry-in
+    int n_ticks, n_pkt, n_carry;
+    const uint8_t *status[2], *attempts[2]; // [0] the carried table, [1] the own table
+    const int32_t *tick[2];
+    uint32_t *block_cnt;       // [workgroups] pending entries of the workgroup, then (k_csma_collect_scan) those before it
+    rm_csma_carry *h_out;      // pinned: the first `cap` entries of the carry-out
+    unsigned long long *h_count; // pinned: entries of the carry-out
+    long long cap;
 };
 
 // A BATCH of SINR ticks whose frames outlive their tick (rm_airbatch.hip; BASELINE configs[4]).  The frames the batch can
@@ -773,6 +793,9 @@ hipError_t launch_ccab_scan(hipStream_t s, const CcaBatchDev &cb);
 // the gate of a CSMA-CA gated batch (rm_csma.hip): the same two parts over the expanded slots
 hipError_t launch_csma_count(hipStream_t s, const NodesDev &nd, const ModelDev &m, const CsmaDev &cs, const CcaTick *h_ticks, CcaTick *d_ticks, bool grid);
 hipError_t launch_csma_resolve(hipStream_t s, const NodesDev &nd, const ModelDev &m, const CsmaDev &cs, bool grid, double cca_threshold, int32_t *gated);
+// a batch without a single slot has carried packets all the same: their entries alone
+hipError_t launch_csma_slotless(hipStream_t s, const CsmaDev &cs);
+hipError_t launch_csma_collect(hipStream_t s, const CsmaCollectDev &cc);
 hipError_t launch_air_expire(hipStream_t s, rm_tx_record *recs, int n, int64_t t_seen); // (the on-air window when the clock goes back)
 hipError_t launch_tick_frames_batch(hipStream_t s, const NodesDev &nd, const ModelDev &m, const TickDev *ticks, int n,
                                     const TickDev *dev_ticks, const LaunchCfg &cfg, int seg_len);

@@ -368,15 +368,25 @@ struct rm_context : TickSlot {
         } cb;
         // what a CSMA-CA gated batch adds to it (rm_api_csma.cpp, rm_csma.hip; rm::CsmaDev): the schedule on the device, the packets'
         // states, the slots' tentative bits; the host form's outputs before they are copied out
+        // (E9: the carried packets' outputs of the host form; the carry-out's inputs on the device, its workgroup counts, and the pinned,
+        // host-mapped block k_csma_collect writes the count and the records to)
         struct Csma {
-            DevBuf<char> sched;
-            DevBuf<uint8_t> state, tentative, slot_flags, o_status, o_attempts, o_flags;
-            DevBuf<int32_t> o_tick, o_pkt;
-            DevBuf<double> o_energy;
+            DevBuf<char> sched, collect_in;
+            DevBuf<uint8_t> state, tentative, slot_flags, o_status, o_attempts, o_flags, c_status, c_attempts, c_flags;
+            DevBuf<int32_t> o_tick, o_pkt, c_tick, c_pkt;
+            DevBuf<double> o_energy, c_energy;
+            DevBuf<uint32_t> collect_cnt;
+            char *h_collect = nullptr; // pinned: the upload's staging ([0, h_collect_in)), the count (64 bytes), the carry-out's records
+            size_t h_collect_in = 0, h_collect_out = 0;
             void release_all()
             {
                 sched.release(); state.release(); tentative.release(); slot_flags.release(); o_status.release(); o_attempts.release();
                 o_flags.release(); o_tick.release(); o_pkt.release(); o_energy.release();
+                collect_in.release(); c_status.release(); c_attempts.release(); c_flags.release(); c_tick.release(); c_pkt.release();
+                c_energy.release(); collect_cnt.release();
+                if (h_collect) (void)hipHostFree(h_collect);
+                h_collect = nullptr;
+                h_collect_in = h_collect_out = 0;
             }
         } cs;
     } ed;

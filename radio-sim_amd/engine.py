@@ -732,6 +732,128 @@ class Engine:
                                                        C.byref(params), C.byref(res) if dev_out is not None else None, n_exp.ctypes.data))
         return n_exp
 
+    # ---- the carry of a CSMA-CA gated batch: pending packets go on in the next batch
+    CSMA_CARRY_DTYPE = np.dtype([("origin_cca_time_us", "<i8"), ("origin_slot", "<i4"), ("node", "<i4"), ("tick", "<i4"), ("attempt", "<i4")])
+
+    @classmethod
+    def _carry(cls, carry):
+        """rm_csma_carry[]: a structured array of CSMA_CARRY_DTYPE (None: an empty list) -> (contiguous array, pointer or None)"""
+        a = np.zeros(0, dtype=cls.CSMA_CARRY_DTYPE) if carry is None else np.ascontiguousarray(carry, dtype=cls.CSMA_CARRY_DTYPE)
+        assert a.ndim == 1 and a.dtype.itemsize == C.sizeof(_lib.CsmaCarry)
+        return a, (a.ctypes.data if len(a) else None)
+
+    @classmethod
+    def csma_schedule_carry(cls, params, n_src, cca_time_us, carry, cap=None):
+        """csma_schedule with a carry list (E9): in origin a carried slot is sum(n_src) + its place in the carry list"""
+        cnt = np.ascontiguousarray(n_src, dtype=np.int32)
+        tc = np.ascontiguousarray(cca_time_us, dtype=np.int64)
+        assert len(cnt) == len(tc)
+        car, car_p = cls._carry(carry)
+        n_exp = np.zeros(len(cnt), dtype=np.int32)
+        total = C.c_int64(-1)
+        L = _lib.lib()
+        if cap is None:
+            check(L.rm_csma_schedule_carry(C.byref(params), len(cnt), cnt.ctypes.data, tc.ctypes.data, car_p, len(car), n_exp.ctypes.data, None,
+                                           None, 0, C.byref(total)))
+            cap = total.value
+        origin = np.zeros(max(int(cap), 1), dtype=np.int32)
+        attempt = np.zeros(max(int(cap), 1), dtype=np.uint8)
+        try:
+            check(L.rm_csma_schedule_carry(C.byref(params), len(cnt), cnt.ctypes.data, tc.ctypes.data, car_p, len(car), n_exp.ctypes.data,
+                                           origin.ctypes.data, attempt.ctypes.data, int(cap), C.byref(total)))
+        except _lib.RadioMediumError as err:
+            err.total = total.value
+            raise
+        return n_exp, origin[:total.value], attempt[:total.value]
+
+    def batch_run_sources_csma_carry(self, t_begin, t_end, src_lists, start_us, air_us, cca_time_us, cca_threshold_dbm, params, carry,
+                                     fields=None, carried_fields=None):
+        """batch_run_sources_csma with carried packets (E9; carry: a structured array of CSMA_CARRY_DTYPE or None).
+        -> ({field: per own packet}, {field: per carried packet}, n_exp per tick)"""
+        lists = [np.ascontiguousarray(s, dtype=np.int32) for s in src_lists]
+        tb, te, st, ai, tc, cnt = self._cca_batch_args(t_begin, t_end, [len(s) for s in lists], start_us, air_us, cca_time_us)
+        assert len(lists) == len(tb)
+        ptrs = np.array([s.ctypes.data if len(s) else 0 for s in lists], dtype=np.uint64)
+        car, car_p = self._carry(carry)
+        total = int(cnt.sum())
+        tables = []
+        for n, names in ((total, fields), (len(car), carried_fields)):
+            want = [f for f, _ in self.CSMA_FIELDS] if names is None else list(names)
+            tables.append({f: np.empty(max(n, 1), dtype=t) for f, t in self.CSMA_FIELDS if f in want})
+        res = [_lib.CsmaResult(**{f: a.ctypes.data for f, a in t.items()}) for t in tables]
+        n_exp = np.zeros(len(lists), dtype=np.int32)
+        check(self._L.rm_batch_run_sources_csma_carry(self._h, len(lists), tb.ctypes.data, te.ctypes.data, ptrs.ctypes.data, cnt.ctypes.data,
+                                                      st.ctypes.data, ai.ctypes.data, tc.ctypes.data, float(cca_threshold_dbm), C.byref(params),
+                                                      C.byref(res[0]), n_exp.ctypes.data, car_p, len(car), C.byref(res[1])))
+        return {f: a[:total] for f, a in tables[0].items()}, {f: a[:len(car)] for f, a in tables[1].items()}, n_exp
+
+    def batch_run_sources_csma_carry_device(self, t_begin, t_end, dev_src_ptrs, n_src, start_us, air_us, cca_time_us, cca_threshold_dbm, params,
+                                            carry, dev_out=None, dev_carried_out=None):
+        """The raw form: device lists; dev_out / dev_carried_out: {field: device pointer} (sum(n_src) / len(carry) entries each); the
+        carry list itself is a host array.  -> n_exp per tick."""
+        tb, te, st, ai, tc, cnt = self._cca_batch_args(t_begin, t_end, n_src, start_us, air_us, cca_time_us)
+        ptrs = np.ascontiguousarray([p or 0 for p in dev_src_ptrs], dtype=np.uint64)
+        assert len(ptrs) == len(tb)
+        car, car_p = self._carry(carry)
+        res, res_c = _lib.CsmaResult(**(dev_out or {})), _lib.CsmaResult(**(dev_carried_out or {}))
+        n_exp = np.zeros(len(ptrs), dtype=np.int32)
+        check(self._L.rm_batch_run_sources_csma_carry_device(self._h, len(ptrs), tb.ctypes.data, te.ctypes.data, ptrs.ctypes.data,
+                                                             cnt.ctypes.data, st.ctypes.data, ai.ctypes.data, tc.ctypes.data,
+                                                             float(cca_threshold_dbm), C.byref(params),
+                                                             C.byref(res) if dev_out is not None else None, n_exp.ctypes.data, car_p, len(car),
+                                                             C.byref(res_c) if dev_carried_out is not None else None))
+        return n_exp
+
+    @classmethod
+    def csma_carry_collect(cls, src_lists, cca_time_us, carry, out, carried_out, cap=None):
+        """The next batch's carry list from a batch's host results (E9; no device needed): the pending carried packets in carry-in order,
+        then the pending own packets in flat order.  out / carried_out: {field: array} with status, attempts and tick.
+        cap: the room offered (default: every packet); too small: RadioMediumError with .count."""
+        lists = [np.ascontiguousarray(s, dtype=np.int32) for s in src_lists]
+        cnt = np.array([len(s) for s in lists], dtype=np.int32)
+        tc = np.ascontiguousarray(cca_time_us, dtype=np.int64)
+        assert len(tc) == len(lists)
+        ptrs = np.array([s.ctypes.data if len(s) else 0 for s in lists], dtype=np.uint64)
+        car, car_p = cls._carry(carry)
+        keep = []
+
+        def table(t, n):
+            t = {f: np.ascontiguousarray(t[f], dtype=dict(cls.CSMA_FIELDS)[f]) for f in ("status", "attempts", "tick")} if n else {}
+            assert all(len(a) == n for a in t.values())
+            keep.append(t)
+            return _lib.CsmaResult(**{f: a.ctypes.data for f, a in t.items()})
+        res, res_c = table(out, int(cnt.sum())), table(carried_out, len(car))
+        cap = int(cnt.sum()) + len(car) if cap is None else int(cap)
+        got = np.zeros(max(cap, 1), dtype=cls.CSMA_CARRY_DTYPE)
+        count = C.c_int64(-1)
+        try:
+            check(_lib.lib().rm_csma_carry_collect(len(lists), ptrs.ctypes.data, cnt.ctypes.data, tc.ctypes.data, car_p, len(car), C.byref(res),
+                                                   C.byref(res_c), got.ctypes.data, cap, C.byref(count)))
+        except _lib.RadioMediumError as err:
+            err.count = count.value
+            raise
+        return got[:count.value]
+
+    def csma_carry_collect_device(self, dev_src_ptrs, n_src, cca_time_us, carry, dev_out, dev_carried_out, cap=None):
+        """The same from the device form's tables and lists ({field: device pointer}, status / attempts / tick): one compaction on the
+        context's stream, one wait.  -> the carry list, a host array."""
+        cnt = np.ascontiguousarray(n_src, dtype=np.int32)
+        tc = np.ascontiguousarray(cca_time_us, dtype=np.int64)
+        ptrs = np.ascontiguousarray([p or 0 for p in dev_src_ptrs], dtype=np.uint64)
+        assert len(ptrs) == len(cnt) == len(tc)
+        car, car_p = self._carry(carry)
+        res, res_c = _lib.CsmaResult(**(dev_out or {})), _lib.CsmaResult(**(dev_carried_out or {}))
+        cap = int(cnt.sum()) + len(car) if cap is None else int(cap)
+        got = np.zeros(max(cap, 1), dtype=self.CSMA_CARRY_DTYPE)
+        count = C.c_int64(-1)
+        try:
+            check(self._L.rm_csma_carry_collect_device(self._h, len(ptrs), ptrs.ctypes.data, cnt.ctypes.data, tc.ctypes.data, car_p, len(car),
+                                                       C.byref(res), C.byref(res_c), got.ctypes.data, cap, C.byref(count)))
+        except _lib.RadioMediumError as err:
+            err.count = count.value
+            raise
+        return got[:count.value]
+
     def sync(self):
         check(self._L.rm_sync(self._h))
 

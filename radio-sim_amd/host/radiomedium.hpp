@@ -850,7 +850,21 @@ public:
                                                const std::vector<int64_t> &start_us, int64_t hex_length, const std::vector<int64_t> &cca_time_us,
                                                double threshold_dbm, const rm_csma_params &p)
     {
+        std::vector<rm_csma_carry> none;
+        return transmitCsmaBatch(senders, t_begin_us, start_us, hex_length, cca_time_us, threshold_dbm, p, {}, none);
+    }
+    // The same with a carry (extension E9): carry_in are the senders an earlier batch left pending (its carry_out), which go on
+    // with their next attempt in this batch; carry_out receives the senders this batch leaves pending, for the next one, whose
+    // tick 0 is the tick after this batch's last.  Consecutive batches chained this way make the calls of one batch over all
+    // their ticks.  carried (may be NULL): one entry per carried sender, attempts counting those of the earlier batches.
+    std::vector<CsmaOutcome> transmitCsmaBatch(const std::vector<std::vector<Node *>> &senders, const std::vector<int64_t> &t_begin_us,
+                                               const std::vector<int64_t> &start_us, int64_t hex_length, const std::vector<int64_t> &cca_time_us,
+                                               double threshold_dbm, const rm_csma_params &p, const std::vector<rm_csma_carry> &carry_in,
+                                               std::vector<rm_csma_carry> &carry_out, std::vector<CsmaOutcome> *carried = nullptr)
+    {
         lastError.clear();
+        carry_out.clear();
+        if (carried) carried->clear();
         Simulator *sim = simulator;
         if (!sim) { lastError = "No simulator"; return {}; }
         const size_t nt = senders.size();
@@ -870,20 +884,40 @@ public:
             n_src[b] = int32_t(src[b].size());
             flat.insert(flat.end(), senders[b].begin(), senders[b].end());
         }
-        const size_t total = flat.size();
-        std::vector<uint8_t> status(total + 1, 0), attempts(total + 1, 0), flags(total + 1, 0);
-        std::vector<int32_t> tick(total + 1, -1), pkt(total + 1, -1);
+        // the carried senders are packets total .. of the same arrays
+        const size_t total = flat.size(), nc = carry_in.size(), all = total + nc;
+        for (const rm_csma_carry &c : carry_in) {
+            if (c.node < 0 || size_t(c.node) >= nodes.size()) { lastError = "a carried sender is not a node"; return {}; }
+            flat.push_back(nodes[size_t(c.node)]);
+        }
+        std::vector<uint8_t> status(all + 2, 0), attempts(all + 2, 0), flags(all + 2, 0);
+        std::vector<int32_t> tick(all + 2, -1), pkt(all + 2, -1);
         const rm_csma_result res = {status.data(), attempts.data(), tick.data(), pkt.data(), flags.data(), nullptr};
-        if (rm_batch_run_sources_csma(ctx_, int32_t(nt), t_begin_us.data(), start_us.data(), lists.data(), n_src.data(), start_us.data(), air.data(),
-                                      cca_time_us.data(), threshold_dbm, &p, &res, n_exp.data()) != RM_OK) {
+        const size_t at = total + 1;
+        const rm_csma_result res_c = {status.data() + at, attempts.data() + at, tick.data() + at, pkt.data() + at, flags.data() + at, nullptr};
+        if (rm_batch_run_sources_csma_carry(ctx_, int32_t(nt), t_begin_us.data(), start_us.data(), lists.data(), n_src.data(), start_us.data(),
+                                            air.data(), cca_time_us.data(), threshold_dbm, &p, &res, n_exp.data(), carry_in.data(), int32_t(nc),
+                                            &res_c) != RM_OK) {
             lastError = rm_last_error();
             return {};
         }
+        carry_out.resize(all + 1);
+        int64_t n_out = 0;
+        if (rm_csma_carry_collect(int32_t(nt), lists.data(), n_src.data(), cca_time_us.data(), carry_in.data(), int32_t(nc), &res, &res_c,
+                                  carry_out.data(), int64_t(all), &n_out) != RM_OK) {
+            lastError = rm_last_error();
+            carry_out.clear();
+            return {};
+        }
+        carry_out.resize(size_t(n_out));
         std::vector<CsmaOutcome> out(total);
         std::vector<std::vector<std::pair<int32_t, size_t>>> sent(nt); // per tick: (position in the expanded list, packet)
-        for (size_t o = 0; o < total; ++o) {
-            out[o] = CsmaOutcome{status[o], attempts[o], flags[o], tick[o], pkt[o]};
-            if (status[o] == RM_CSMA_SENT) sent[size_t(tick[o])].emplace_back(pkt[o], o);
+        for (size_t o = 0; o < all; ++o) {
+            const size_t e = o < total ? o : o + 1;
+            const CsmaOutcome one{status[e], attempts[e], flags[e], tick[e], pkt[e]};
+            if (o < total) out[o] = one;
+            else if (carried) carried->push_back(one);
+            if (one.status == RM_CSMA_SENT) sent[size_t(one.tick)].emplace_back(one.pkt, o);
         }
         if (ccaDst_.empty()) { ccaDst_.resize(1024); ccaVerdict_.resize(1024); ccaRssi_.resize(1024); }
         const std::string data(size_t(hex_length), '0');

@@ -10,6 +10,12 @@ window back to the same steady state (8000 frames live when the next tick begins
   gated_batch         (c) rm_batch_run_sources_cca_device over the original lists; (a) - (c) is the price of the retries
   kernels_us          dispatch intervals (rm_profile_kernels) of the gate's kernels in (a), per batch of 64 ticks
   expanded_slots, deferred_share   of the CSMA batch: slots of all expanded lists; made attempts that deferred
+  carry_n0            (d) rm_batch_run_sources_csma_carry_device with an empty carry list: the no-regression check against
+                      (a) of the parent commit's library, measured in the same session by running this tool with --e8-only and
+                      RM_LIBRARY=<the parent's build>, which prints series (a) alone
+  carry_2x32_collect  (e) the same 64 ticks as two carry batches of 32, each followed by rm_csma_carry_collect_device, the second fed
+                      the first one's carry-out; carried_into_second_half: its length
+  collect_kernels_us  dispatch intervals of k_csma_collect<false>, k_csma_collect_scan, k_csma_collect<true> in (e), per collect
 
 Medians of `reps` with min and max, all series in one process.  Prints one JSON line.  Run on the GPU box:
 python tools/csma_batch_latency.py [reps]
@@ -44,7 +50,13 @@ def mix64(z):
 
 
 def main():
-    reps = max(20, int(sys.argv[1]) if len(sys.argv) > 1 else 20)
+    e8_only = "--e8-only" in sys.argv
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    if e8_only:                                  # a library of before E9 has none of its entry points
+        from radio_sim_amd import _lib
+        for name in [k for k in _lib.SIGNATURES if "carry" in k]:
+            del _lib.SIGNATURES[name]
+    reps = max(20, int(args[0]) if args else 20)
     cfg = W.CONFIGS["c5"]
     n, t = cfg["n"], W.tx_count(cfg)
     nodes = W.make_nodes(n, cfg["index"])
@@ -85,6 +97,28 @@ def main():
         last["n_exp"] = eng.batch_run_sources_csma_device(tb, te, [dev[(first + b) % pool].ptr.value for b in range(BATCH)], [t] * BATCH, ts,
                                                           [W.AIR_US] * BATCH, tc, THRESHOLD, params,
                                                           {"status": d_st.ptr.value, "attempts": d_at.ptr.value, "flags": d_f.ptr.value})
+
+    d_tk = DeviceArray(nbytes=4 * BATCH * t)
+    d_cst, d_cat, d_ctk = DeviceArray(nbytes=BATCH * t), DeviceArray(nbytes=BATCH * t), DeviceArray(nbytes=4 * BATCH * t)
+
+    def carry_n0():
+        first, tb, te, tc, ts = span(BATCH)
+        eng.batch_run_sources_csma_carry_device(tb, te, [dev[(first + b) % pool].ptr.value for b in range(BATCH)], [t] * BATCH, ts,
+                                                [W.AIR_US] * BATCH, tc, THRESHOLD, params, None,
+                                                {"status": d_st.ptr.value, "attempts": d_at.ptr.value, "flags": d_f.ptr.value}, None)
+
+    def carry_halves():
+        first, tb, te, tc, ts = span(BATCH)
+        own = {"status": d_st.ptr.value, "attempts": d_at.ptr.value, "tick": d_tk.ptr.value}
+        car = {"status": d_cst.ptr.value, "attempts": d_cat.ptr.value, "tick": d_ctk.ptr.value}
+        carry, h = None, BATCH // 2
+        for lo in (0, h):
+            ptrs = [dev[(first + b) % pool].ptr.value for b in range(lo, lo + h)]
+            eng.batch_run_sources_csma_carry_device(tb[lo:lo + h], te[lo:lo + h], ptrs, [t] * h, ts[lo:lo + h], [W.AIR_US] * h, tc[lo:lo + h],
+                                                    THRESHOLD, params, carry, own, car)
+            carry = eng.csma_carry_collect_device(ptrs, [t] * h, tc[lo:lo + h], carry, own, car)
+            if lo == 0:
+                last["carried"] = len(carry)
 
     def host_loop():
         first, tb, te, tc, ts = span(BATCH)
@@ -130,6 +164,10 @@ def main():
     out = {"nodes": n, "candidates_per_tick": t, "ticks_per_batch": BATCH, "air_us": W.AIR_US, "frames_live_when_the_batch_begins": 8 * t,
            "threshold_dbm": THRESHOLD, "csma": [MAX_BACKOFFS, MIN_BE, MAX_BE, SEED], "unit": "us per tick"}
     out["csma_batch"] = timed(csma_batch)
+    if e8_only:
+        out["csma_batch_again"] = timed(csma_batch)
+        print(json.dumps(out))
+        return
     status = DeviceArray.read(d_st.ptr.value, np.uint8, BATCH * t)
     attempts = DeviceArray.read(d_at.ptr.value, np.uint8, BATCH * t).astype(np.int64)
     out["expanded_slots"] = int(np.sum(last["n_exp"]))
@@ -138,6 +176,20 @@ def main():
     out["host_loop"] = timed(host_loop)
     out["gated_batch"] = timed(gated_batch)
     out["csma_batch_again"] = timed(csma_batch)
+    out["carry_n0"] = timed(carry_n0)
+    out["carry_2x32_collect"] = timed(carry_halves)
+    out["carried_into_second_half"] = last["carried"]
+    col = {}
+    for rep in range(reps):
+        refill()
+        eng.profile_enable(1)
+        carry_halves()
+        eng.sync()
+        for name, v in eng.profile_kernels().items():
+            if name.startswith("k_csma_collect"):
+                col.setdefault(name, []).append(v[1] * 1e3 / max(v[0], 1))
+        eng.profile_enable(0)
+    out["collect_kernels_us"] = {name: stats(v) for name, v in col.items()}
     per = {}
     for rep in range(reps):
         refill()
@@ -151,7 +203,7 @@ def main():
     out["kernels_us"] = {name: stats(v) for name, v in per.items()}
     out["kernels_us_sum_of_medians"] = float(sum(s["median_us"] for s in out["kernels_us"].values()))
     print(json.dumps(out))
-    for d in dev + [d_f, d_e, d_st, d_at]:
+    for d in dev + [d_f, d_e, d_st, d_at, d_tk, d_cst, d_cat, d_ctk]:
         d.free()
     eng.close()
 
