@@ -664,6 +664,43 @@ int rm_csma_carry_collect_device(rm_context *ctx, int32_t n_ticks, const int32_t
                                  const int64_t *cca_time_us, const rm_csma_carry *carry, int32_t n_carry, const rm_csma_result *dev_out,
                                  const rm_csma_result *dev_carried_out, rm_csma_carry *carry_out, int64_t cap, int64_t *count);
 
+/* ---- frame error model: delivery decided from SINR and frame length -----------------------------------------------
+ * (not reference behaviour.)  Opt-in, on the RM_LD_SINR medium only.  Without it a heard
+ * link is delivered iff sinr >= ld_capture_db, whatever the frame's length; with RM_EM_OQPSK_250K a link that is RM_DELIVERED
+ * under everything else (Tx failure, capture, half duplex, the rxProbability draw) becomes RM_INTERFERED iff !(u < psr):
+ *   psr  = (1 - ber)^(air_us / us_per_bit), ber = 8/15 * 1/16 * sum_{k=2..16} (-1)^k C(16,k) exp(20 s (1/k - 1)), s = 10^(sinr/10),
+ *          in the operations and the order of E-math that DESIGN.md E10 writes down (rm_error_model_psr is that, on the host);
+ *          ber is clamped to [0, 0.5]; a NaN sinr gives a NaN psr, which never delivers;
+ *   u    = the uniform deviate of mix64(mix64(mix64(seed + 0x9E3779B97F4A7C15) ^ start_us) ^ (src << 32 | dst)): a function of the
+ *          frame (source node, start time), the receiver and the seed alone (rm_error_model_draw) -- not of packet numbers,
+ *          ticks, slots or ranks, and no java.util.Random draw is consumed.
+ * Nothing else of a result changes: sinr, rssi, dst, pkt_offset, pkt_interference, the on-air window, the energy query and the
+ * gates (they read no verdict).  ld_capture_db keeps working as a floor; -inf leaves the curve alone.  The verdict of a frame at a
+ * receiver does not depend on whether a lone tick, a batch, a gated batch or any split of a CSMA-CA run into carry batches
+ * evaluated it: E9's promise holds with the model on.
+ * The pass (one launch over the finished result; a batch: one launch over all of its slots) runs inside the evaluating call,
+ * before anything reads verdicts: rm_transmit, rm_tick_begin .. rm_tick_flush / _view / rm_tick_run, rm_tick_run_sources_device,
+ * rm_tick_run_records_device, rm_batch_run_sources_device (both kinds), rm_batch_run_device, the gated forms (E6 - E9), and the
+ * reception stage behind all of them.  A lone tick with the model on writes its compact arrays at once (one more launch).
+ * rm_set_error_model: RM_ERR_STATE unless the model is RM_MODEL_LOGDIST with RM_LD_SINR, and on a context made under RM_GRAPH=1
+ * (the pass is not part of the captured sequence); RM_ERR_INVALID for an unknown kind, reserved != 0, or us_per_bit not finite
+ * and > 0.  rm_set_model switches the error model off (RM_EM_NONE).  While a model is on, an evaluating call on a context with
+ * a receiver partition (rm_set_partition*) and the gathered / rm_dist_* / rm_group_* forms are refused with RM_ERR_STATE before
+ * anything is launched, the window unchanged.  With RM_EM_NONE (the default) nothing is launched and nothing changes. */
+enum rm_error_model_kind { RM_EM_NONE = 0, RM_EM_OQPSK_250K = 1 };
+typedef struct rm_error_model {
+    int32_t kind;      /* enum rm_error_model_kind */
+    int32_t reserved;  /* 0 */
+    double us_per_bit; /* 4.0: 250 kbit/s */
+    uint64_t seed;
+} rm_error_model;
+void rm_error_model_defaults(rm_error_model *e, int32_t kind); /* us_per_bit 4.0, seed 0 */
+int rm_set_error_model(rm_context *ctx, const rm_error_model *e);
+int rm_get_error_model(const rm_context *ctx, rm_error_model *out);
+/* pure host functions, no device (built from csrc/rm_math.hpp by the host compiler, like rm_det_math); RM_EM_NONE: psr 1 */
+double rm_error_model_psr(const rm_error_model *e, double sinr_db, int64_t air_us);
+double rm_error_model_draw(const rm_error_model *e, int32_t src, int64_t start_us, int32_t dst);
+
 /* ---- several devices behind one caller --------------------------------------------------------------
  * The reference host is ONE process (Main.java:65-73): a group drives n contexts from one host thread, one
  * per device (an ordinal may repeat: several partitions on one GPU).  Receivers are partitioned over the

@@ -44,6 +44,14 @@ class CsmaCarry(C.Structure):
                 ("attempt", C.c_int32)]
 
 
+class ErrorModel(C.Structure):
+    """rm_error_model: the frame error model of the SINR medium (24 bytes)"""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("us_per_bit", C.c_double), ("seed", C.c_uint64)]
+
+
+EM_NONE, EM_OQPSK_250K = 0, 1
+
+
 class ModelParams(C.Structure):
     _fields_ = [("kind", C.c_int32), ("flags", C.c_int32),
                 ("udgm_success_ratio_tx", C.c_double), ("udgm_success_ratio_rx", C.c_double),
@@ -270,6 +278,11 @@ SIGNATURES = {
                                         C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "rm_csma_carry_collect_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "rm_error_model_defaults": (None, [C.c_void_p, C.c_int32]),
+    "rm_set_error_model": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rm_get_error_model": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rm_error_model_psr": (C.c_double, [C.c_void_p, C.c_double, C.c_int64]),
+    "rm_error_model_draw": (C.c_double, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32]),
     "rm_det_math": (C.c_double, [C.c_int32, C.c_double]),
     "rm_link_hash": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
     "rm_evq_init": (None, [C.c_void_p]),

@@ -264,6 +264,13 @@ int rmh::launch_batch(rm_context *c, TickSlot *const *slots, const TickPlan *pla
         RM_TRY(stage(RM_STAGE_SINR));
         RM_TRY(after_sweep(c, after_arg));
     }
+    if (em_on(c) && is_sinr(c)) {
+        // the frame error model (E10): every verdict of the batch is final here (the draws, the interference stages of a batch of
+        // overlapping ticks); ONE launch over all slots, ahead of everything that reads them (result copies, the packing launch of
+        // rm_batch_result_view, rm_events_process_batch)
+        RM_TRY(stage(RM_STAGE_SINR));
+        RM_HIP(rm::launch_errmodel_batch(s, em_dev(c), n, dev_ticks));
+    }
     for (int b = 0; b < n; ++b) {
         slots[b]->have_result = true;
         slots[b]->compact_pending = false;
@@ -285,6 +292,7 @@ int rmh::batch_run(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us, co
         (!dev_src && !dev_new && !any_gathered) || ((dev_src || gathered_idx) && (!start_us || !air_us)) ||
         (any_gathered && (gather_world < 1 || gather_slots < 1)))
         return fail(RM_ERR_INVALID, "bad arguments");
+    RM_TRY(em_check(c, any_gathered)); // (the frame error model: refused before anything is planned or the window moves)
     static thread_local std::vector<int32_t> n_gath;
     if (any_gathered) {
         n_gath.assign(size_t(n_ticks), gather_world * gather_slots);
@@ -434,7 +442,25 @@ int rmh::batch_run(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us, co
     // configurations the batched kernels do not cover (fp64 frame, unsorted table, very many frames,
     // empty ticks): the same ticks, one launch sequence each
     parity.dismiss();
-    for (int b = 0; b < n_ticks; ++b) RM_TRY(launch_tick(c, *slots[b], plans[b]));
+    for (int b = 0; b < n_ticks; ++b) RM_TRY(launch_tick(c, *slots[b], plans[b], false));
+    if (em_on(c) && sinr) {
+        // the frame error model over the ticks that were launched one by one: their compact arrays, then one pass over all of them
+        static thread_local std::vector<rm::TickDev> em_ticks;
+        em_ticks.clear();
+        for (int b = 0; b < n_ticks; ++b) {
+            if (plans[b].empty) continue;
+            if (slots[b]->draws_pending) return fail(RM_ERR_STATE, "internal: the frame error model's pass cannot run before the ranks' draws are finished");
+            RM_TRY(materialize(c, *slots[b]));
+            em_ticks.push_back(slots[b]->last);
+        }
+        if (!em_ticks.empty()) {
+            ProbeScope probe(c);
+            sample_stage(probe.smp, RM_STAGE_SINR);
+            RM_HIP(c->d_ticks.ensure(RM_MAX_BATCH));
+            RM_HIP(rm::launch_store_ticks(c->stream, em_ticks.data(), int(em_ticks.size()), c->d_ticks.p));
+            RM_HIP(rm::launch_errmodel_batch(c->stream, em_dev(c), int(em_ticks.size()), c->d_ticks.p));
+        }
+    }
     return RM_OK;
 }
 

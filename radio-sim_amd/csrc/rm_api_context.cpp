@@ -394,6 +394,7 @@ int rm_set_model(rm_context *c, const rm_model_params *p)
     ev_touch(c);
     const bool was_geo = is_geometric(c);
     c->params = *p;
+    c->em = rm_error_model{}; // (a new medium starts without a frame error model: rm_set_error_model comes after rm_set_model)
     if (was_geo != is_geometric(c)) c->rx_dirty = true;
     c->prefilter_dirty = true;
     RM_HIP(hipSetDevice(c->device));

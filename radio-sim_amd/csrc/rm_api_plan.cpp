@@ -387,7 +387,7 @@ int prepare_tick(rm_context *c, TickSlot &ts, TickPlan &plan, bool want_wg, cons
 }
 
 // the launch sequence of one prepared tick
-int launch_tick(rm_context *c, TickSlot &ts, const TickPlan &plan)
+int launch_tick(rm_context *c, TickSlot &ts, const TickPlan &plan, bool em_pass)
 {
     if (plan.empty) return RM_OK;
     const rm::TickDev &t = plan.t;
@@ -549,6 +549,15 @@ int launch_tick(rm_context *c, TickSlot &ts, const TickPlan &plan)
     ts.last_model = m;
     ts.last_cfg = cfg;
     ts.have_result = true;
+    if (em_pass && sinr && em_on(c)) {
+        if (ts.draws_pending) return fail(RM_ERR_STATE, "internal: the frame error model's pass cannot run before the ranks' draws are finished");
+        // the frame error model (E10): the tick's compact arrays at once, then the pass over them -- on the stream before the hand-over
+        // to the reception stage (run_tick), before any pack launch and any copy, which all read out_verdict from here on
+        RM_TRY(stage(RM_STAGE_REORDER));
+        RM_TRY(materialize(c, ts));
+        RM_TRY(stage(RM_STAGE_SINR));
+        RM_HIP(rm::launch_errmodel(s, em_dev(c), ts.last));
+    }
     return RM_OK;
 }
 

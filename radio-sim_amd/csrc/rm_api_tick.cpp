@@ -598,6 +598,7 @@ int air_window_reserve(rm_context *c, size_t n_more)
 int air_tick_device(rm_context *c, int64_t t_begin_us, const int32_t *dev_src, const rm_tx_record *dev_new, int32_t n, int64_t start_us,
                     int64_t air_us, int64_t latest_end_us, bool new_on_host)
 {
+    RM_TRY(em_check(c, false)); // (the frame error model refuses partitions before the window moves)
     RM_TRY(air_window_expire(c, t_begin_us));
     RM_TRY(air_window_reserve(c, size_t(n)));
     const size_t live = c->air_tail - c->air_head;

@@ -505,6 +505,12 @@ struct TickDev {
     NbrCacheDev nc;         // the source candidate cache (batches of source indices over a whole sorted table; state == nullptr: none)
 };
 
+// The frame error model (rm_errmodel.hip): what the pass over a finished result reads of rm_error_model
+struct EmDev {
+    double us_per_bit;
+    uint64_t seed;
+};
+
 // rm_transmit's result block in host-mapped (pinned) memory, written by k_pack_result
 constexpr int kTransmitMax = 2048;
 struct TransmitResult {
@@ -832,6 +838,10 @@ hipError_t launch_dense_layout(hipStream_t s, const ModelDev &m, const TickDev &
 hipError_t launch_dense_write(hipStream_t s, const ModelDev &m, const TickDev &t, const uint32_t *cell_cnt, const uint32_t *cell_off,
                               const unsigned long long *cell_mask, int rx_first, int chunks);
 
+// (rm_errmodel.hip) the frame error model's pass over one finished result slot / over the n slots of a batch in one launch
+hipError_t launch_errmodel(hipStream_t s, const EmDev &em, const TickDev &t);
+hipError_t launch_errmodel_batch(hipStream_t s, const EmDev &em, int n, const TickDev *dev_ticks);
+
 // reception stage (rm_events.hip)
 hipError_t launch_ev_append(hipStream_t s, const EvDev &e, const EvLinkSrc &ls, const rm_tx_record *tx, int n_new, int64_t now,
                             int immediate, const uint32_t *dropped_flag);
@@ -852,6 +862,8 @@ double host_det_pow10(double y);
 double host_det_math(int fn, double x);                                  // rm_det_math (test hook)
 uint64_t host_link_hash(uint64_t seed, uint32_t a, uint32_t b, double *u); // rm_link_hash (test hook)
 uint64_t host_mix64(uint64_t z);
+double host_em_psr(int kind, double us_per_bit, double sinr_db, int64_t air_us);    // rm_error_model_psr (rm_errmodel.hip)
+double host_em_draw(uint64_t seed, int32_t src, int64_t start_us, int32_t dst);     // rm_error_model_draw
 void host_lcg_jump_map(uint64_t steps, uint64_t *A, uint64_t *C);
 
 } // namespace rm

@@ -145,6 +145,7 @@ struct rm_context : TickSlot {
     bool own_stream = false;
 
     rm_model_params params{};
+    rm_error_model em{};       // the frame error model (E10); kind RM_EM_NONE: off
     double base_rssi = -100.0; // AbstractRadioMedium.java:38
 
     // host mirror of the node table (Simulator.getNodes() snapshot)
@@ -556,7 +557,9 @@ bool air_lists_current(const rm_context *c, int64_t t_begin, uint32_t oldest);
 int prepare_tick(rm_context *c, TickSlot &ts, TickPlan &plan, bool want_wg, const rm_tx_record *tx, int n_active,
                  int first_new, const int32_t *src_list = nullptr, int64_t src_start_us = 0, int64_t src_air_us = 0,
                  int air_mode = kAirNone, uint32_t air_oldest = 0, const rm::PlanKnobs *knobs_in = nullptr);
-int launch_tick(rm_context *c, TickSlot &ts, const TickPlan &plan);
+// em_pass: with the frame error model on, the tick ends with its compact arrays and the model's pass over them (a batch that
+// launches its ticks one by one runs ONE pass over all of them afterwards instead)
+int launch_tick(rm_context *c, TickSlot &ts, const TickPlan &plan, bool em_pass = true);
 int materialize(rm_context *c, TickSlot &ts);
 int dense_layout(rm_context *c, TickSlot &ts); // (the cells' offsets and totals of a dense tick that ended with its cells)
 int run_tick(rm_context *c, const rm_tx_record *tx, int n_active, int first_new, const int32_t *src_list = nullptr,
@@ -632,6 +635,12 @@ int cca_desc_block(rm_context *c, size_t extra, rm::CcaTick **h_ticks, uint32_t 
 int cca_batch_dev(rm_context *c, size_t n_cand, int32_t n_ticks, const int32_t *const *src, const int32_t *n_per, const int64_t *start_us,
                   const int64_t *air_us, const int64_t *cca_time_us, size_t extra, rm::CcaBatchDev *out, bool *use_grid, rm::CcaTick **h_ticks_out,
                   const int32_t **gated_v, char **h_extra);
+
+// ---- rm_api_errmodel.cpp: the frame error model (E10)
+inline bool em_on(const rm_context *c) { return c->em.kind != RM_EM_NONE; }
+rm::EmDev em_dev(const rm_context *c);
+// what an evaluating call refuses while a model is on, before anything is launched (gathered: a gathered / rm_dist_* form)
+int em_check(const rm_context *c, bool gathered);
 
 // ---- rm_api_comm.cpp
 int comm_all_gather(rm_context *c, const void *mine, void *all, size_t bytes);

@@ -117,6 +117,47 @@ RM_HD double shadow_gauss(uint64_t seed_mixed, double clip, uint32_t a, uint32_t
     return g;
 }
 
+// ---- frame error model (extension spec E10): packet success ratio of an 802.15.4 O-QPSK frame and the link's draw ----
+// ber = 8/15 * 1/16 * sum_{k=2..16} (-1)^k C(16,k) exp(20 s (1/k - 1)), s the linear SINR; psr = (1 - ber)^bits.
+// Every operation is one IEEE rounding in the order DESIGN.md section 6 (E10) writes them; the loop is unrolled, so the
+// binomials and the 1/k - 1 are literals of the instruction stream (folded by the compiler with IEEE rounding), not loads.
+RM_HD double em_ber_oqpsk(double s)
+{
+    const double binom[17] = {1.0, 16.0, 120.0, 560.0, 1820.0, 4368.0, 8008.0, 11440.0, 12870.0,
+                              11440.0, 8008.0, 4368.0, 1820.0, 560.0, 120.0, 16.0, 1.0};
+    const double s20 = 20.0 * s;
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 2; k <= 16; ++k) {
+        const double ck = 1.0 / double(k) - 1.0;
+        const double yk = (s20 * ck) * 1.4426950408889634;
+        const double tk = binom[k] * det_exp2(yk);
+        acc = (k & 1) ? acc - tk : acc + tk;
+    }
+    double ber = acc / 30.0;
+    if (ber < 0.0) ber = 0.0;
+    if (0.5 < ber) ber = 0.5;
+    return ber; // (a NaN passes both comparisons and stays NaN)
+}
+
+RM_HD double em_psr_oqpsk(double us_per_bit, double sinr_db, int64_t air_us)
+{
+    const double s = det_pow10(sinr_db / 10.0);
+    const double ber = em_ber_oqpsk(s);
+    if (ber != ber) return ber; // (det_log2 reads a NaN's bits as a number: the NaN is handed through here, and never delivers)
+    const double n = double(air_us) / us_per_bit;
+    return det_exp2(n * det_log2(1.0 - ber));
+}
+
+// the link's uniform deviate: a hash of (seed, the frame's start, its source node, the receiver) and of nothing else -- not of
+// packet numbers, ticks, slots or ranks, so a frame's verdict at a receiver is the same however the frame was evaluated
+RM_HD double em_draw(uint64_t seed, int32_t src, int64_t start_us, int32_t dst)
+{
+    const uint64_t h1 = mix64(mix64(seed + 0x9E3779B97F4A7C15ull) ^ uint64_t(start_us));
+    const uint64_t h = mix64(h1 ^ ((uint64_t(uint32_t(src)) << 32) | uint64_t(uint32_t(dst))));
+    return (double(h >> 12) + 0.5) * 0x1.0p-52;
+}
+
 // Position.getDistance, Position.java:56-64: this = transmitter, p2 = receiver;
 // (dx*dx + dy*dy) + dz*dz, then a correctly rounded square root.
 RM_HD double ref_distance(double ax, double ay, double az, double bx, double by, double bz)

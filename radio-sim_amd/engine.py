@@ -121,6 +121,38 @@ class Engine:
         assert m.ndim == 2 and m.shape[0] == m.shape[1]
         check(self._L.rm_set_n2n_matrix(self._h, m.shape[0], m.ctypes.data))
 
+    # -- frame error model of the SINR medium
+    @staticmethod
+    def error_model(kind=_lib.EM_OQPSK_250K, us_per_bit=4.0, seed=0, reserved=0):
+        """rm_error_model: the library's defaults with the given fields"""
+        e = _lib.ErrorModel()
+        _lib.lib().rm_error_model_defaults(C.byref(e), kind)
+        e.us_per_bit, e.seed, e.reserved = us_per_bit, seed, reserved
+        return e
+
+    def set_error_model(self, kind, us_per_bit=4.0, seed=0, reserved=0):
+        """rm_set_error_model: EM_NONE switches it off (and so does set_model)"""
+        e = self.error_model(kind, us_per_bit, seed, reserved)
+        check(self._L.rm_set_error_model(self._h, C.byref(e)))
+        return e
+
+    def get_error_model(self):
+        e = _lib.ErrorModel()
+        check(self._L.rm_get_error_model(self._h, C.byref(e)))
+        return e
+
+    @staticmethod
+    def error_model_psr(sinr_db, air_us, kind=_lib.EM_OQPSK_250K, us_per_bit=4.0):
+        """rm_error_model_psr: the packet success ratio, on the host alone"""
+        e = Engine.error_model(kind, us_per_bit)
+        return _lib.lib().rm_error_model_psr(C.byref(e), sinr_db, air_us)
+
+    @staticmethod
+    def error_model_draw(src, start_us, dst, seed=0):
+        """rm_error_model_draw: the link's uniform deviate, on the host alone"""
+        e = Engine.error_model(seed=seed)
+        return _lib.lib().rm_error_model_draw(C.byref(e), src, start_us, dst)
+
     # -- java.util.Random
     def seed(self, seed):
         check(self._L.rm_seed(self._h, seed))

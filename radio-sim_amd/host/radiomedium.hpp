@@ -674,11 +674,43 @@ class LogDistanceRadioMedium : public GpuRadioMedium {
 public:
     explicit LogDistanceRadioMedium(int device = 0) : GpuRadioMedium(RM_MODEL_LOGDIST, device) {}
     rm_model_params &params() { return params_; } // change, then apply()
-    using GpuRadioMedium::apply;
     void setSinr(bool on)
     {
         params_.flags = on ? (params_.flags | RM_LD_SINR) : (params_.flags & ~RM_LD_SINR);
         apply();
+    }
+    // (rm_set_model switches the frame error model off: a medium that has one sets it again after every change of its parameters --
+    // and loses it, as the engine would refuse it, when the change takes the SINR extension away)
+    void apply()
+    {
+        GpuRadioMedium::apply();
+        if (errorModel_.kind != RM_EM_NONE && rm_set_error_model(ctx_, &errorModel_) != RM_OK) {
+            errorModel_ = rm_error_model{};
+            lastError = rm_last_error();
+        }
+    }
+    // The frame error model (extension E10; needs setSinr(true)): with RM_EM_OQPSK_250K a delivered link survives with the packet
+    // success ratio of its SINR and its air time.  The verdicts come out of the engine, so transmit(), transmitIfClear(), the tick
+    // mode and transmitCsmaBatch() deliver and interfere accordingly and their generateReceptionEvents calls carry the new verdict.
+    // false and lastError on a refusal (the model the medium had stays).
+    bool setErrorModel(int32_t kind, double us_per_bit = 4.0, uint64_t seed = 0)
+    {
+        rm_error_model e;
+        rm_error_model_defaults(&e, kind);
+        e.us_per_bit = us_per_bit;
+        e.seed = seed;
+        if (rm_set_error_model(ctx_, &e) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        errorModel_ = e;
+        return true;
+    }
+    rm_error_model getErrorModel() const
+    {
+        rm_error_model e;
+        if (rm_get_error_model(ctx_, &e) != RM_OK) rm_error_model_defaults(&e, RM_EM_NONE);
+        return e;
     }
     // Clear-channel assessment / energy detection over the frames on the air (extension E5; needs setSinr(true)): the power in
     // dBm that `node` sees on its own channel at time_us -- the noise level when nothing counts; NaN and lastError on a refusal.
@@ -944,6 +976,7 @@ public:
     }
 
 private:
+    rm_error_model errorModel_{}; // what setErrorModel set last (RM_EM_NONE: none), kept across apply()
     std::vector<std::unique_ptr<RadioPacket>> ccaSent_;
     std::vector<int32_t> ccaDst_;
     std::vector<uint8_t> ccaVerdict_;
