@@ -701,6 +701,56 @@ int rm_get_error_model(const rm_context *ctx, rm_error_model *out);
 double rm_error_model_psr(const rm_error_model *e, double sinr_db, int64_t air_us);
 double rm_error_model_draw(const rm_error_model *e, int32_t src, int64_t start_us, int32_t dst);
 
+/* ---- per-node traffic counters accumulated on the device -----------------------------------------------------------
+ * (not reference behaviour.)  Opt-in, on every medium.  With statistics on, every evaluating
+ * call ends with one more launch on the context's stream that adds the call's results to a table of one rm_node_stats per node
+ * index -- behind the frame error model's pass, so it counts the verdicts every result reader sees.  For every evaluated tick,
+ * with its new frames q (record tx[q]: src, air_us) and its heard links i (packet q_i, receiver dst_i, final verdict v_i):
+ *   a frame counts on the transmitter side iff 0 <= src_q < n_nodes (padding, deferred candidates of the gates and CSMA-CA slots
+ *   not made are -1 and count nothing); then tx_frames[src_q] += 1, tx_air_us[src_q] += air_us_q, tx_failed[src_q] += pkt_interference[q];
+ *   a heard link adds 1, air_us_{q_i} and [v_i == RM_DELIVERED] to rx_heard, rx_air_us and rx_delivered of dst_i, and, if its frame
+ *   counts, 1 and [v_i == RM_DELIVERED] to tx_links_heard and tx_links_delivered of src_{q_i}.
+ * rx_air_us is a sum per heard frame, not the union of their spans: frames that overlap at a receiver count twice.  Frames of
+ * earlier ticks that are still on the air get no verdicts in a later tick and are never counted twice.  A tick whose result
+ * overflowed the link capacity or was dropped counts nothing and adds 1 to ticks_skipped; every other non-empty tick adds 1 to
+ * ticks_counted; an empty tick changes nothing.  All sums are integers: the table after any sequence of calls is the sum over
+ * its ticks, whether they ran as lone ticks, a batch, a gated batch, a CSMA-CA batch or any split of a CSMA-CA run into carry
+ * batches (nothing here is indexed by packet number).
+ * Accepted on a whole-table context by rm_transmit, rm_tick_flush / _view / rm_tick_run, rm_tick_run_device,
+ * rm_tick_run_sources_device, rm_tick_run_records_device, rm_batch_run_sources_device (both SINR kinds), rm_batch_run_device and
+ * the gated forms (E6 - E9).  While statistics are on, an evaluating call on a context with a receiver partition
+ * (rm_set_partition*) and the gathered / rm_dist_* / rm_group_* forms are refused with RM_ERR_STATE before anything is launched,
+ * the on-air window unchanged; rm_stats_enable(ctx, 1) is RM_ERR_STATE on a context made under RM_GRAPH=1 (the pass is not part
+ * of the captured sequence).  With statistics on, rm_transmit on a reference medium does not take its one-launch shortcut (whose
+ * links never become a slot's result) but the general tick path: the links it returns are the same.  A lone tick with statistics
+ * on writes its compact arrays at once (a dense tick: its records from the lane masks).
+ * The counters do not depend on the medium: rm_set_model, rm_set_error_model, rm_seed, rm_node_update and rm_nodes_move keep them
+ * and counting goes on.  rm_nodes_upload with the same node count keeps them; another node count resizes the table and zeroes it
+ * and the totals (pointers handed out by rm_stats_device are stale then).  With statistics off (the default) nothing is launched
+ * and nothing allocated. */
+typedef struct rm_node_stats {
+    uint64_t tx_frames;          /* frames this node put on the air */
+    uint64_t tx_failed;          /* of those, frames whose per-packet Tx-failure flag (pkt_interference) is set */
+    uint64_t tx_air_us;          /* sum of air_us of those frames */
+    uint64_t tx_links_heard;     /* heard links of those frames */
+    uint64_t tx_links_delivered; /* of those, links whose final verdict is RM_DELIVERED */
+    uint64_t rx_heard;           /* heard links with this node as receiver */
+    uint64_t rx_delivered;       /* of those, RM_DELIVERED */
+    uint64_t rx_air_us;          /* sum of air_us of the frames of those heard links (per heard frame: overlapping frames count twice) */
+} rm_node_stats;                 /* 64 bytes */
+typedef struct rm_stats_totals { uint64_t ticks_counted, ticks_skipped; } rm_stats_totals;
+/* on = 1: allocate the table (zeroed) if need be and count from the next evaluating call; 0: stop counting, the table is kept */
+int rm_stats_enable(rm_context *ctx, int32_t on);
+int rm_stats_enabled(const rm_context *ctx);
+/* zero the table and the totals, on the context's stream.  RM_ERR_STATE before the first rm_stats_enable(ctx, 1), as the next two. */
+int rm_stats_reset(rm_context *ctx);
+/* the listed nodes' records in list order (nodes == NULL: all, in node order; n has to be the node count then), and the totals
+ * (or NULL).  Synchronises the context's stream once.  RM_ERR_INVALID: an index outside 0 .. n_nodes - 1. */
+int rm_stats_read(rm_context *ctx, const int32_t *nodes, int32_t n, rm_node_stats *out, rm_stats_totals *totals);
+/* the table ([n_nodes], by node index) and the totals in device memory: valid until statistics are enabled with another node
+ * count (or rm_nodes_upload changes it) or the context is destroyed; the caller's reads are ordered by the context's stream */
+int rm_stats_device(rm_context *ctx, const rm_node_stats **dev_table, const rm_stats_totals **dev_totals);
+
 /* ---- several devices behind one caller --------------------------------------------------------------
  * The reference host is ONE process (Main.java:65-73): a group drives n contexts from one host thread, one
  * per device (an ordinal may repeat: several partitions on one GPU).  Receivers are partitioned over the

@@ -14,5 +14,6 @@ There is no CPU fallback anywhere in this package.
 from . import _lib  # noqa: F401
 from ._lib import (MODEL_NULL, MODEL_UDGM, MODEL_UDGM_CONST, MODEL_N2N, MODEL_LOGDIST,  # noqa: F401
                    UNHEARD, INTERFERED, DELIVERED, LD_SINR, MAX_BATCH, RadioMediumError, ModelParams, TxRecord,
-                   TX_RECORD_DTYPE, build_library, library_path, ErrorModel, EM_NONE, EM_OQPSK_250K)
+                   TX_RECORD_DTYPE, build_library, library_path, ErrorModel, EM_NONE, EM_OQPSK_250K,
+                   NodeStats, StatsTotals, NODE_STATS_DTYPE)
 from .engine import Engine, Group  # noqa: F401

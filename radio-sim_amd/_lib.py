@@ -52,6 +52,21 @@ class ErrorModel(C.Structure):
 EM_NONE, EM_OQPSK_250K = 0, 1
 
 
+class NodeStats(C.Structure):
+    """rm_node_stats: one node's traffic counters (64 bytes)"""
+    _fields_ = [("tx_frames", C.c_uint64), ("tx_failed", C.c_uint64), ("tx_air_us", C.c_uint64), ("tx_links_heard", C.c_uint64),
+                ("tx_links_delivered", C.c_uint64), ("rx_heard", C.c_uint64), ("rx_delivered", C.c_uint64), ("rx_air_us", C.c_uint64)]
+
+
+class StatsTotals(C.Structure):
+    """rm_stats_totals"""
+    _fields_ = [("ticks_counted", C.c_uint64), ("ticks_skipped", C.c_uint64)]
+
+
+NODE_STATS_DTYPE = np.dtype([(name, "<u8") for name, _ in NodeStats._fields_])
+assert NODE_STATS_DTYPE.itemsize == C.sizeof(NodeStats) == 64
+
+
 class ModelParams(C.Structure):
     _fields_ = [("kind", C.c_int32), ("flags", C.c_int32),
                 ("udgm_success_ratio_tx", C.c_double), ("udgm_success_ratio_rx", C.c_double),
@@ -283,6 +298,11 @@ SIGNATURES = {
     "rm_get_error_model": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rm_error_model_psr": (C.c_double, [C.c_void_p, C.c_double, C.c_int64]),
     "rm_error_model_draw": (C.c_double, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32]),
+    "rm_stats_enable": (C.c_int, [C.c_void_p, C.c_int32]),
+    "rm_stats_enabled": (C.c_int, [C.c_void_p]),
+    "rm_stats_reset": (C.c_int, [C.c_void_p]),
+    "rm_stats_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(StatsTotals)]),
+    "rm_stats_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "rm_det_math": (C.c_double, [C.c_int32, C.c_double]),
     "rm_link_hash": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
     "rm_evq_init": (None, [C.c_void_p]),

@@ -323,6 +323,9 @@ void rm_destroy(rm_context *c)
         if (o.h_flag) (void)hipHostFree(o.h_flag);
     }
     c->ed.cnt.release(); c->ed.tx_mark.release(); c->ed.bucket_f.release(); c->ed.every_f.release(); c->ed.bucket_m.release(); c->ed.every_m.release(); c->ed.gated.release();
+    c->st.table.release(); c->st.totals.release();
+    if (c->st.h_block) (void)hipHostFree(c->st.h_block);
+    c->st.h_block = nullptr;
     if (c->ed.h_block) (void)hipHostFree(c->ed.h_block);
     c->ed.h_block = nullptr;
     c->ed.cb.release_all();

@@ -429,6 +429,13 @@ int launch_tick(rm_context *c, TickSlot &ts, const TickPlan &plan, bool em_pass)
         ts.last_model = m;
         ts.last_cfg = cfg;
         ts.have_result = true;
+        if (em_pass && stats_on(c)) {
+            // the traffic counters (E11) over a dense tick: its records from the lane masks, then the pass (rm_result_dense keeps
+            // answering: the masks stay where they are)
+            RM_TRY(stage(RM_STAGE_REORDER));
+            RM_TRY(materialize(c, ts));
+            RM_HIP(rm::launch_stats(s, stats_dev(c), ts.last));
+        }
         return RM_OK;
     }
     const int seg_len = (t.n_active - t.first_new <= frame_tick_max()) ? rm::frame_tick_segment(t, cfg, m) : 0;
@@ -557,6 +564,13 @@ int launch_tick(rm_context *c, TickSlot &ts, const TickPlan &plan, bool em_pass)
         RM_TRY(materialize(c, ts));
         RM_TRY(stage(RM_STAGE_SINR));
         RM_HIP(rm::launch_errmodel(s, em_dev(c), ts.last));
+    }
+    if (em_pass && stats_on(c)) {
+        if (ts.draws_pending) return fail(RM_ERR_STATE, "internal: the traffic counters' pass cannot run before the ranks' draws are finished");
+        // the traffic counters (E11), behind the frame error model's pass: the tick's compact arrays at once, then one pass over them
+        RM_TRY(stage(RM_STAGE_REORDER));
+        RM_TRY(materialize(c, ts));
+        RM_HIP(rm::launch_stats(s, stats_dev(c), ts.last));
     }
     return RM_OK;
 }

@@ -511,6 +511,13 @@ struct EmDev {
     uint64_t seed;
 };
 
+// Per-node traffic counters (rm_stats.hip): the table the pass over a finished result adds to
+struct StatsDev {
+    rm_node_stats *table;    // [n_nodes], by node index
+    rm_stats_totals *totals; // [1]
+    int n_nodes;
+};
+
 // rm_transmit's result block in host-mapped (pinned) memory, written by k_pack_result
 constexpr int kTransmitMax = 2048;
 struct TransmitResult {
@@ -841,6 +848,12 @@ hipError_t launch_dense_write(hipStream_t s, const ModelDev &m, const TickDev &t
 // (rm_errmodel.hip) the frame error model's pass over one finished result slot / over the n slots of a batch in one launch
 hipError_t launch_errmodel(hipStream_t s, const EmDev &em, const TickDev &t);
 hipError_t launch_errmodel_batch(hipStream_t s, const EmDev &em, int n, const TickDev *dev_ticks);
+
+// (rm_stats.hip) the traffic counters' pass over one finished result slot / over the n slots of a batch in one launch, and the
+// gather of listed nodes' records (and the totals) into a host-mapped block
+hipError_t launch_stats(hipStream_t s, const StatsDev &sd, const TickDev &t);
+hipError_t launch_stats_batch(hipStream_t s, const StatsDev &sd, int n, const TickDev *dev_ticks);
+hipError_t launch_stats_gather(hipStream_t s, const StatsDev &sd, const int32_t *nodes, int n, rm_node_stats *out, rm_stats_totals *totals_out);
 
 // reception stage (rm_events.hip)
 hipError_t launch_ev_append(hipStream_t s, const EvDev &e, const EvLinkSrc &ls, const rm_tx_record *tx, int n_new, int64_t now,

@@ -146,6 +146,16 @@ struct rm_context : TickSlot {
 
     rm_model_params params{};
     rm_error_model em{};       // the frame error model (E10); kind RM_EM_NONE: off
+    // per-node traffic counters (E11; rm_api_stats.cpp, rm_stats.hip): the table by node index, the totals, and the pinned,
+    // host-mapped block a list read is staged through (node list in; records and totals out)
+    struct Stats {
+        bool on = false;
+        int32_t n = -1; // the node count the table was made (and zeroed) for; -1: never enabled
+        DevBuf<rm_node_stats> table;
+        DevBuf<rm_stats_totals> totals;
+        char *h_block = nullptr;
+        size_t h_cap = 0; // nodes the block has room for
+    } st;
     double base_rssi = -100.0; // AbstractRadioMedium.java:38
 
     // host mirror of the node table (Simulator.getNodes() snapshot)
@@ -558,7 +568,7 @@ int prepare_tick(rm_context *c, TickSlot &ts, TickPlan &plan, bool want_wg, cons
                  int first_new, const int32_t *src_list = nullptr, int64_t src_start_us = 0, int64_t src_air_us = 0,
                  int air_mode = kAirNone, uint32_t air_oldest = 0, const rm::PlanKnobs *knobs_in = nullptr);
 // em_pass: with the frame error model on, the tick ends with its compact arrays and the model's pass over them (a batch that
-// launches its ticks one by one runs ONE pass over all of them afterwards instead)
+// launches its ticks one by one runs ONE pass over all of them afterwards instead); the same holds for the traffic counters' pass
 int launch_tick(rm_context *c, TickSlot &ts, const TickPlan &plan, bool em_pass = true);
 int materialize(rm_context *c, TickSlot &ts);
 int dense_layout(rm_context *c, TickSlot &ts); // (the cells' offsets and totals of a dense tick that ended with its cells)
@@ -641,6 +651,14 @@ inline bool em_on(const rm_context *c) { return c->em.kind != RM_EM_NONE; }
 rm::EmDev em_dev(const rm_context *c);
 // what an evaluating call refuses while a model is on, before anything is launched (gathered: a gathered / rm_dist_* form)
 int em_check(const rm_context *c, bool gathered);
+
+// ---- rm_api_stats.cpp: per-node traffic counters (E11)
+inline bool stats_on(const rm_context *c) { return c->st.on; }
+rm::StatsDev stats_dev(const rm_context *c);
+// what an evaluating call refuses while statistics are on, before anything is launched (the shape of em_check)
+int stats_check(const rm_context *c, bool gathered);
+// rm_nodes_upload: another node count resizes the table and zeroes it
+int stats_nodes_changed(rm_context *c);
 
 // ---- rm_api_comm.cpp
 int comm_all_gather(rm_context *c, const void *mine, void *all, size_t bytes);

@@ -153,6 +153,36 @@ class Engine:
         e = Engine.error_model(seed=seed)
         return _lib.lib().rm_error_model_draw(C.byref(e), src, start_us, dst)
 
+    # -- per-node traffic counters accumulated on the device
+    def stats_enable(self, on=True):
+        """rm_stats_enable: count from the next evaluating call (False: stop counting, the table is kept)"""
+        check(self._L.rm_stats_enable(self._h, 1 if on else 0))
+
+    def stats_enabled(self):
+        return bool(self._L.rm_stats_enabled(self._h))
+
+    def stats_reset(self):
+        check(self._L.rm_stats_reset(self._h))
+
+    def stats_read(self, nodes=None):
+        """rm_stats_read: (structured array of NODE_STATS_DTYPE -- the listed nodes in list order, or all in node order --,
+        {"ticks_counted": .., "ticks_skipped": ..})"""
+        tot = _lib.StatsTotals()
+        if nodes is None:
+            out = np.zeros(max(int(self._L.rm_node_count(self._h)), 0), dtype=_lib.NODE_STATS_DTYPE)
+            check(self._L.rm_stats_read(self._h, None, out.shape[0], out.ctypes.data, C.byref(tot)))
+        else:
+            idx = np.ascontiguousarray(nodes, dtype=np.int32)
+            out = np.zeros(idx.shape[0], dtype=_lib.NODE_STATS_DTYPE)
+            check(self._L.rm_stats_read(self._h, idx.ctypes.data, idx.shape[0], out.ctypes.data, C.byref(tot)))
+        return out, {"ticks_counted": int(tot.ticks_counted), "ticks_skipped": int(tot.ticks_skipped)}
+
+    def stats_device(self):
+        """rm_stats_device: (device pointer of the table [n_nodes] of 64-byte records, device pointer of the totals)"""
+        tbl, tot = C.c_void_p(), C.c_void_p()
+        check(self._L.rm_stats_device(self._h, C.byref(tbl), C.byref(tot)))
+        return tbl.value, tot.value
+
     # -- java.util.Random
     def seed(self, seed):
         check(self._L.rm_seed(self._h, seed))

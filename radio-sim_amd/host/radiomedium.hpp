@@ -558,6 +558,52 @@ public:
             else sim->generateReceptionEvents(packet, node, rssi_[i], verdict_[i] == RM_DELIVERED);
         }
     }
+    // Per-node traffic counters accumulated on the device (extension E11): with statistics on, every evaluating call of the medium
+    // (transmit(), the tick mode, transmitIfClear(), transmitCsmaBatch()) adds its frames and heard links to one rm_node_stats per
+    // node of Simulator.getNodes() -- frames sent and failed, links heard and delivered on both sides, air time sent and received.
+    // The setting survives apply(); a node table of another size starts a zeroed table.  false and lastError on a refusal.
+    bool setStatistics(bool on)
+    {
+        if (rm_stats_enable(ctx_, on ? 1 : 0) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        statistics_ = on;
+        return true;
+    }
+    bool getStatisticsEnabled() const { return rm_stats_enabled(ctx_) != 0; }
+    bool resetStatistics()
+    {
+        if (rm_stats_reset(ctx_) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        return true;
+    }
+    // one node's counters (all zero and lastError on a refusal) / every node's, in the order of Simulator.getNodes() (empty and
+    // lastError on a refusal); `totals`: the ticks counted and skipped
+    rm_node_stats getStatistics(const Node &node, rm_stats_totals *totals = nullptr)
+    {
+        rm_node_stats out{};
+        const int32_t i = node.index;
+        if (!syncNodes()) return out; // the device mirrors the node table first: the table has its size
+        if (rm_stats_read(ctx_, &i, 1, &out, totals) != RM_OK) {
+            lastError = rm_last_error();
+            out = rm_node_stats{};
+        }
+        return out;
+    }
+    std::vector<rm_node_stats> getStatistics(rm_stats_totals *totals = nullptr)
+    {
+        std::vector<rm_node_stats> out;
+        if (!syncNodes()) return out;
+        out.resize(simulator ? simulator->getNodes().size() : size_t(rm_node_count(ctx_)));
+        if (rm_stats_read(ctx_, nullptr, int32_t(out.size()), out.data(), totals) != RM_OK) {
+            lastError = rm_last_error();
+            out.clear();
+        }
+        return out;
+    }
     std::string lastError;
     bool lastInterference = false;
 
@@ -566,7 +612,13 @@ protected:
     void apply()
     {
         if (rm_set_model(ctx_, &params_) != RM_OK) throw std::invalid_argument(rm_last_error());
+        // (the traffic counters are the context's, not the medium's: a setting the medium made stays made)
+        if (statistics_ && !rm_stats_enabled(ctx_) && rm_stats_enable(ctx_, 1) != RM_OK) {
+            statistics_ = false;
+            lastError = rm_last_error();
+        }
     }
+    bool statistics_ = false; // what setStatistics set last, kept across apply()
     rm_context *ctx_ = nullptr;
     bool syncNodes() { return !simulator || sync(simulator, simulator->getNodes()); } // the device mirrors the node table first
 
