@@ -404,7 +404,9 @@ int rm_profile_kernels(rm_context *ctx, rm_kernel_time *out, int32_t cap, int32_
 /* number of Tx->Rx link evaluations resolved by the last tick ( T * (N_loc) minus self links ) */
 int64_t rm_last_link_evaluations(const rm_context *ctx);
 /* observability (synchronises): the candidate links the sweep's conservative filter handed to the exact stage for the
- * tick of result slot `slot` (0 on the one-launch tick path, which keeps no candidate list) and its heard links */
+ * tick of result slot `slot` (0 on the one-launch tick path, which keeps no candidate list) and its heard links.  A frame
+ * that a draw-free batch served from its source's cached records (the heard form) was neither swept nor
+ * evaluated: the candidate count holds the SWEPT frames' candidates only, the heard count every frame's links */
 int rm_slot_stats(rm_context *ctx, int32_t slot, uint64_t *candidates, uint64_t *heard);
 /* the SINR extension's on-air lists (build-defined, DESIGN.md "Extension spec" E4): how many ticks added only their new
  * frames to the per-receiver interferer lists kept on the device, and how many rebuilt the lists from every frame on the

@@ -48,8 +48,9 @@ void nbr_cache_report(rm_context *c)
     if (!g_clock.on || !c->nc.ctr.p) return;
     unsigned long long v[3] = {0, 0, 0};
     if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(v, c->nc.ctr.p, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return;
-    std::fprintf(stderr, "rm source candidate cache: %llu frames served from a list, %llu swept (%.1f %% hits); %llu arena entries of %zu handed out in "
-                         "the last epoch (%u epochs)\n",
+    std::fprintf(stderr, "rm source cache (launch sequences: %llu heard form, %llu candidates form; the last one: %s): %llu frames served from a list, "
+                         "%llu swept (%.1f %% hits); %llu arena entries of %zu handed out in the last epoch (%u epochs)\n",
+                 c->nc.batches[1], c->nc.batches[0], c->nc.form == 1 ? "heard" : "candidates",
                  v[1], v[2], (v[1] + v[2]) ? 100.0 * double(v[1]) / double(v[1] + v[2]) : 0.0, v[0], c->nc.arena.n, c->nc.epoch);
 }
 
@@ -57,6 +58,7 @@ void nbr_cache_report(rm_context *c)
 // by source indices (records built from the node table) over the WHOLE sorted table of a geometric medium without the SINR
 // extension; partitions, gathered batches, caller-supplied records and everything that is not the plain four-stage sequence keep
 // the sweep as it is.
+// The form (rm::NbrCacheDev): heard -- finished records per source -- where no draw can happen in the batch, candidates otherwise.
 static int plan_nbr_cache(rm_context *c, rm::TickDev *ticks, const TickPlan *plans, int n)
 {
     const rm::LaunchCfg &cfg = plans[0].cfg;
@@ -74,6 +76,7 @@ static int plan_nbr_cache(rm_context *c, rm::TickDev *ticks, const TickPlan *pla
     const size_t nodes = size_t(c->n);
     // the arena: 96 entries per node (the bench shape keeps some 50 per source), half a gigabyte at most
     const size_t arena = std::min<size_t>(nodes * 96, size_t(1) << 27);
+    const int form = cfg.stochastic ? 0 : 1;
     if (nc.nodes != c->n || !nc.state.p) {
         RM_HIP(nc.state.ensure(nodes));
         RM_HIP(nc.off.ensure(nodes));
@@ -87,8 +90,13 @@ static int plan_nbr_cache(rm_context *c, rm::TickDev *ticks, const TickPlan *pla
         nc.epoch = 0x7FFFFFFFu; // (the state words are zeroed below)
         nc.seen = 0;
     }
-    if (nc.seen != nc.change) { // a new epoch: every list is stale
+    if (form == 1) { // 13 bytes per entry instead of 4
+        RM_HIP(nc.arena_rssi.ensure(arena));
+        RM_HIP(nc.arena_verdict.ensure(arena));
+    }
+    if (nc.seen != nc.change || nc.form != form) { // a new epoch: every list is stale (another form reads the arena differently)
         nc.seen = nc.change;
+        nc.form = form;
         if (nc.epoch >= 0x7FFFFFFEu) {
             RM_HIP(hipMemsetAsync(nc.state.p, 0, nc.state.n * sizeof(uint32_t), s));
             nc.epoch = 0;
@@ -102,12 +110,15 @@ static int plan_nbr_cache(rm_context *c, rm::TickDev *ticks, const TickPlan *pla
     RM_HIP(nc.fill.ensure(size_t(n) * per));
     RM_HIP(nc.cur.ensure(size_t(n) * per));
     RM_HIP(hipMemsetAsync(nc.tick_cnt.p, 0, size_t(n) * 4 * sizeof(uint32_t), s));
+    nc.batches[form]++;
     for (int b = 0; b < n; ++b) {
         rm::NbrCacheDev &d = ticks[b].nc;
         d.state = nc.state.p;
         d.off = nc.off.p;
         d.len = nc.len.p;
         d.arena = nc.arena.p;
+        d.arena_rssi = form == 1 ? nc.arena_rssi.p : nullptr;
+        d.arena_verdict = form == 1 ? nc.arena_verdict.p : nullptr;
         d.ctr = nc.ctr.p;
         d.arena_len = uint32_t(arena);
         d.word = (nc.epoch << 1) | 1u;
@@ -242,7 +253,7 @@ int rmh::launch_batch(rm_context *c, TickSlot *const *slots, const TickPlan *pla
     RM_TRY(stage(RM_STAGE_FILTER));
     RM_HIP(rm::launch_batch_stage(s, 0, nd, m, ticks, n, dev_ticks, cfg));
     c->last_tile_reuse = rm::filter_ticks_per_wg(ticks[0], n);
-    if (use_nc) RM_HIP(rm::launch_nbr_cache_batch(s, ticks, n, dev_ticks));
+    if (use_nc) RM_HIP(rm::launch_nbr_cache_batch(s, ticks, n, dev_ticks, false));
     RM_TRY(stage(RM_STAGE_EXACT));
     RM_HIP(rm::launch_batch_stage(s, 1, nd, m, ticks, n, dev_ticks, cfg));
     if (plans[0].sinr && ticks[0].acc_lo == nullptr) { // (the per-receiver lists: SELF entries, then the walks; sums per receiver need neither)
@@ -256,6 +267,7 @@ int rmh::launch_batch(rm_context *c, TickSlot *const *slots, const TickPlan *pla
     }
     RM_TRY(stage(RM_STAGE_REORDER));
     RM_HIP(rm::launch_batch_stage(s, 2, nd, m, ticks, n, dev_ticks, cfg));
+    if (use_nc) RM_HIP(rm::launch_nbr_cache_batch(s, ticks, n, dev_ticks, true)); // (the heard form fills its lists from the ordered records)
     if (cfg.stochastic) {
         // the shared generator is walked tick by tick, in slot order, inside one launch
         RM_TRY(stage(RM_STAGE_DRAWS));

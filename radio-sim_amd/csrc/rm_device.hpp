@@ -450,6 +450,21 @@ RM_D uint32_t wave_inclusive_scan(uint32_t v, int lane)
     return v;
 }
 
+// the lanes' runs laid end to end (inc: wave_inclusive_scan of their lengths): the lane whose run holds entry j -- the first one
+// whose running count is above j (63 for a j at or beyond the total)
+RM_D int wave_run_of(const uint32_t inc, const uint32_t j)
+{
+    int lo = 0, hi = 63;
+#pragma unroll
+    for (int step = 0; step < 6; ++step) {
+        const int mid = (lo + hi) >> 1;
+        const bool above = uint32_t(__shfl(int(inc), mid)) > j;
+        hi = above ? mid : hi;
+        lo = above ? lo : mid + 1;
+    }
+    return min(lo, 63);
+}
+
 // exclusive scan of one value per thread over a 1024-thread block; returns the block total in `total`
 RM_D uint32_t block_exclusive_scan_1024(uint32_t v, uint32_t *s_wave /*[16]*/, uint32_t &total)
 {

@@ -371,25 +371,35 @@ struct OvDev {
     uint32_t *pair_tail;        // [kShards * kShardStride]
     uint32_t pair_seg;
 };
-// The source candidate cache of the batched sweep.  What the sweep finds for a frame -- the receivers that pass
-// the fp32 distance test and the shadowed medium's table test -- depends on the frame through its SOURCE NODE only, so a
-// context keeps every source's candidates (engine positions) from one launch sequence to the next: the pre-pass takes a
-// frame whose source has a valid list out of the sweep, k_nc_expand_batch copies the list into the tick's shards instead.
+// The source cache of the batched sweep.  What a frame's evaluation finds depends on the frame through its
+// SOURCE NODE only, so a context keeps a list per source from one launch sequence to the next: the pre-pass (k_tick_prep_batch)
+// takes a frame whose source has a valid list out of the sweep and notes the list's place in hit[]; the frames that were swept
+// claim and fill lists for their sources (k_nc_claim_batch, k_nc_fill_batch).
 // A list is valid in one EPOCH of the context: the host moves on to a new epoch whenever the receiver table or the
 // pre-filter is rebuilt (any change of a node, the medium, the partition or the engine order).
-constexpr uint32_t kNcListCap = 1024; // candidates per list at most: a source with more stays uncached
+// What a list holds is the cache's FORM, chosen per launch sequence by the host (a change of form begins a new epoch):
+//  candidates: a list holds the engine positions that passed the sweep; the exact and reorder stages evaluate and rank them as
+//      if the sweep had appended them.  Links that draw need this form: their verdicts are pending, their records carry a_prob.
+//  heard (arena_rssi != nullptr): where no draw can happen, a frame's FINISHED records -- receiver node index, rssi, verdict, in
+//      node order -- depend on the frame through its source node only as well (kFlagTxDead comes from the source's txprob, neither
+//      start_us nor air_us enters).  A list holds those records in three parallel columns; a hit frame skips the exact stage and
+//      the ranking altogether: k_nc_expand_batch puts its list's length into cursor[], k_reorder_served_batch copies the columns
+//      to the frame's place in the ordered records, and the lists are filled from the ordered records behind the reorder stage.
+constexpr uint32_t kNcListCap = 1024; // entries per list at most: a source with more stays uncached
 struct NbrCacheDev {
     uint32_t *state;           // [n] per node: (epoch << 1) | 1 the list is valid in `epoch`; (epoch << 1) claimed in `epoch`, no list
     uint32_t *off, *len;       // [n] the node's list in the arena
-    int32_t *arena;            // engine positions, handed out by a bump allocator
+    int32_t *arena;            // engine positions (candidates) / receiver node indices (heard), handed out by a bump allocator
+    double *arena_rssi;        // heard form: the records' rssi ... (nullptr: the candidates form)
+    uint8_t *arena_verdict;    // ... and verdict, by the same index
     unsigned long long *ctr;   // [0] arena entries handed out, [1] frames served from a list, [2] frames swept (since the context was made)
     uint32_t arena_len;
     uint32_t word;             // (epoch << 1) | 1 of the running launch sequence
     // per tick of the running launch sequence
     uint32_t *tick_cnt;        // [0] frames left to the sweep, [1] lists claimed for filling, [2] frames served from a list
     uint2 *hit;                // [n_cnt] per frame: (length + 1 of its source's list, 0: swept; the list's offset)
-    int32_t *fill;             // [n_cnt] per frame: offset of the list its candidates are copied to, -1: none
-    uint32_t *cur;             // [n_cnt] per frame: candidates copied so far
+    int32_t *fill;             // [n_cnt] per frame: offset of the list its candidates / records are copied to, -1: none
+    uint32_t *cur;             // [n_cnt] per frame: candidates copied so far (candidates form)
 };
 
 constexpr int kNearSb = 16;   // filter workgroups (of 1024 receivers) per block of the near-frame lists
@@ -769,9 +779,11 @@ hipError_t launch_rank_frames(hipStream_t s, const NodesDev &nd, const ModelDev 
 constexpr int kGatherTrailer = RM_GATHER_TRAILER; // words behind a rank's source indices in its block of a sharded batch
 hipError_t launch_stage_block(hipStream_t s, const int32_t *src, int n, uint64_t digest, int32_t *dst);
 int filter_ticks_per_wg(const TickDev &t0, int n);
-// the source candidate cache, between the sweep and the exact stage of a batch: claim lists for the swept frames' sources,
-// copy their candidates there, then append the cached candidates of the frames the sweep left out
-hipError_t launch_nbr_cache_batch(hipStream_t s, const TickDev *ticks, int n, const TickDev *dev_ticks);
+// the source candidate cache, called twice per batch: between the sweep and the exact stage, and behind the reorder stage.
+// Candidates form, first call: claim lists for the swept frames' sources, copy their candidates there, then append the cached
+// candidates of the frames the sweep left out.  Heard form, first call: the served frames' list lengths join cursor[]; second
+// call: claim lists for the swept frames' sources and copy their ordered records there.
+hipError_t launch_nbr_cache_batch(hipStream_t s, const TickDev *ticks, int n, const TickDev *dev_ticks, bool behind_reorder);
 hipError_t launch_exact_batch(hipStream_t s, const NodesDev &nd, const ModelDev &m, const TickDev *ticks, int n,
                               const TickDev *dev_ticks, const LaunchCfg &cfg);
 hipError_t launch_sinr_acc_batch(hipStream_t s, const ModelDev &m, int n, const TickDev *dev_ticks, int max_links, int share);

@@ -1379,10 +1379,14 @@ k_filter_wg_group(const NodesDev nd, const ModelDev m, const TickDev *__restrict
     }
 }
 
-// ============================================================================ the source candidate cache (NbrCacheDev)
-// Three launches between the sweep and the exact stage of a batch.  The sweep has appended the candidates of the frames the
-// pre-pass left to it; a list written here is read by LATER launch sequences only (the pre-pass of this one has run), so the
-// order of the stream is all the ordering there is.
+// ============================================================================ the source cache (NbrCacheDev)
+// Three kernels, in both forms of the cache: claim (a swept frame's source gets a list), fill (the list's entries), expand (a
+// frame the pre-pass took out of the sweep gets what its source's list holds).  A list written here is read by LATER launch
+// sequences only (the pre-pass of this one has run), so the order of the stream is all the ordering there is.
+// Heard form (t.nc.arena_rssi != nullptr, block-uniform in every kernel below): expand alone runs before the exact stage and
+// only hands the hit frames' list lengths to the reorder stage's scan; claim and fill run BEHIND the reorder stage (and
+// k_reorder_served_batch, rm_reorder.hip) and take the swept frames' finished records from the ordered arrays.
+// Candidates form: all three run between the sweep and the exact stage, over the candidates the sweep has appended.
 
 // one thread per frame: a swept frame whose source has no list in this epoch claims one (compare-and-swap on the state word: a
 // node that transmits in two ticks of the batch is filled once) and takes its room from the arena.  A source with more
@@ -1398,16 +1402,19 @@ __global__ void __launch_bounds__(256) k_nc_claim_batch(const TickDev *__restric
         atomicAdd(&t.nc.ctr[2], (unsigned long long)t.nc.tick_cnt[0]);
     }
     const int lane = threadIdx.x & 63;
-    // (a tick whose shards overflowed has gaps where runs were dropped: none of its frames leaves a list)
+    // (a tick whose shards overflowed has gaps where runs were dropped: none of its frames leaves a list; in the heard form
+    // neither does a tick whose heard links exceed the link capacity: its ordered records stop at `cap`)
+    const bool heard = t.nc.arena_rssi != nullptr;
+    const bool dropped = t.stage_count[1] != 0u || (heard && t.out_count[1] != 0u);
     bool mine = false;
     int s = -1;
     uint32_t cnt = 0;
-    if (e < n_eval && t.nc.hit[e].x == 0u && t.stage_count[1] == 0u) {
+    if (e < n_eval && t.nc.hit[e].x == 0u && !dropped) {
         s = t.p_src[e];
         if (s >= 0) {
             const uint32_t st = t.nc.state[s];
             if ((st >> 1) != (t.nc.word >> 1) && atomicCAS(&t.nc.state[s], st, t.nc.word & ~1u) == st) {
-                cnt = t.cand_tot[e - t.cnt_base];
+                cnt = heard ? t.cursor[e - t.cnt_base] : t.cand_tot[e - t.cnt_base]; // (heard: the frame's final heard count)
                 mine = cnt <= kNcListCap;
             }
         }
@@ -1436,12 +1443,47 @@ __global__ void __launch_bounds__(256) k_nc_claim_batch(const TickDev *__restric
     if (fm && int(threadIdx.x & 63) == __ffsll((long long)fm) - 1) atomicAdd(&t.nc.tick_cnt[1], uint32_t(__popcll(fm)));
 }
 
-// one workgroup per shard of a tick that claimed lists: the shard's entries (the sweep's: the cached ones are appended
-// afterwards) whose frame fills a list go there, one atomic per run of entries of one frame
+// the entries of the lists claimed in this launch sequence (nothing to do for a tick that claimed none)
+// Heard form: one wave per 64 frames.  A claimed frame's records are contiguous and already in node order at its place in the
+// ordered arrays; all of the wave's lists are copied to the arena's columns with full lanes (no atomics).
+// Candidates form: one workgroup per shard: the shard's entries (the sweep's: the cached ones are appended afterwards) whose
+// frame fills a list go there, one atomic per run of entries of one frame.
 __global__ void __launch_bounds__(256) k_nc_fill_batch(const TickDev *__restrict__ ticks)
 {
     const TickDev &t = ticks[blockIdx.z];
     if (t.nc.state == nullptr || uniform_u(t.nc.tick_cnt[1]) == 0u) return;
+    if (t.nc.arena_rssi != nullptr) { // (block-uniform; grid: frames / kBlock in x)
+        const int lane = threadIdx.x & 63;
+        const int e0 = int(blockIdx.x) * kBlock + wave_index() * 64;
+        const int e = e0 + lane;
+        int32_t fo = -1;
+        if (e < t.n_active - t.first_eval) fo = t.nc.fill[e];
+        uint32_t cnt = 0, src = 0;
+        if (fo >= 0) { // (claimed: the tick was not dropped, so every record of the frame lies below `cap`)
+            cnt = t.cursor[e - t.cnt_base];
+            src = t.slot_off[e - t.cnt_base];
+        }
+        const uint32_t inc = wave_inclusive_scan(cnt, lane);
+        const uint32_t total = uniform_u(uint32_t(__shfl(int(inc), 63)));
+        for (uint32_t j0 = 0; j0 < total; j0 += 64u) { // wave-uniform
+            const uint32_t j = j0 + uint32_t(lane);
+            const int f = wave_run_of(inc, j);
+            const uint32_t f_inc = uint32_t(__shfl(int(inc), f)), f_cnt = uint32_t(__shfl(int(cnt), f)), f_src = uint32_t(__shfl(int(src), f));
+            const uint32_t f_dst = uint32_t(__shfl(fo, f));
+            if (j < total) {
+                const uint32_t k = j - (f_inc - f_cnt);
+                const uint32_t a = f_dst + k, o = f_src + k;
+                // (the claim has made sure of both -- the list ends inside the arena, the tick was not dropped; like the
+                // candidates form's fill below, the store is guarded all the same: it is a write into memory shared by every tick)
+                if (a < t.nc.arena_len && o < t.cap) {
+                    t.nc.arena[a] = t.out_dst[o];
+                    t.nc.arena_rssi[a] = t.out_rssi[o];
+                    t.nc.arena_verdict[a] = t.out_verdict[o];
+                }
+            }
+        }
+        return;
+    }
     const uint32_t shard = blockIdx.y;
     if (shard > t.shard_mask || t.stage_count[1] != 0u) return;
     const uint32_t n = uniform_u(min(t.shard_count[shard * kShardStride], t.seg_cap));
@@ -1465,10 +1507,12 @@ __global__ void __launch_bounds__(256) k_nc_fill_batch(const TickDev *__restrict
     }
 }
 
-// one wave per 64 frames: the list of each one the pre-pass took out of the sweep goes into one of the tick's shards as a run
-// of (frame, engine position) entries, all of the wave's lists copied with full lanes (an entry finds its frame by bisection over the lanes' running
-// counts), and every list's length into its frame's candidate count -- what the sweep would have appended (the order inside
-// a shard never mattered: the reorder stage ranks by node index)
+// what the frames that the pre-pass took out of the sweep get from their sources' lists
+// Heard form: one thread per frame: the list's length goes into cursor[] -- the frame's heard count for the reorder stage's scan.
+// Candidates form: one wave per 64 frames: the list of each hit frame goes into one of the tick's shards as a run of (frame,
+// engine position) entries, all of the wave's lists copied with full lanes (an entry finds its frame by bisection over the lanes'
+// running counts, wave_run_of), and every list's length into its frame's candidate count -- what the sweep would have appended
+// (the order inside a shard never mattered: the reorder stage ranks by node index)
 __global__ void __launch_bounds__(256) k_nc_expand_batch(const TickDev *__restrict__ ticks)
 {
     const TickDev &t = ticks[blockIdx.z];
@@ -1479,6 +1523,13 @@ __global__ void __launch_bounds__(256) k_nc_expand_batch(const TickDev *__restri
     uint2 h = make_uint2(0u, 0u);
     if (e < t.n_active - t.first_eval) h = t.nc.hit[e];
     uint32_t cnt = h.x > 1u ? h.x - 1u : 0u; // (0: swept, or an empty list)
+    if (t.nc.arena_rssi != nullptr) {
+        // heard form (block-uniform): the list IS the frame's heard links.  Its length joins the reorder stage's scan of cursor[]
+        // (the pre-pass zeroed it; the exact stage adds to swept frames' words only); nothing goes to the shards, the frame's
+        // candidate count stays 0 and the exact stage never sees it.
+        if (cnt) t.cursor[e - t.cnt_base] = cnt;
+        return;
+    }
     // a list is one run in one shard (the sweep's runs are no longer: a shard has room for cap / shards entries)
     uint32_t dst = 0;
     if (cnt) {
@@ -1495,15 +1546,7 @@ __global__ void __launch_bounds__(256) k_nc_expand_batch(const TickDev *__restri
     const uint32_t total = uniform_u(uint32_t(__shfl(int(inc), 63)));
     for (uint32_t j0 = 0; j0 < total; j0 += 64u) { // wave-uniform
         const uint32_t j = j0 + uint32_t(lane);
-        int lo = 0, hi = 63; // the first lane whose running count is above j
-#pragma unroll
-        for (int step = 0; step < 6; ++step) {
-            const int mid = (lo + hi) >> 1;
-            const bool above = uint32_t(__shfl(int(inc), mid)) > j;
-            hi = above ? mid : hi;
-            lo = above ? lo : mid + 1;
-        }
-        const int f = min(lo, 63);
+        const int f = wave_run_of(inc, j);
         const uint32_t f_inc = uint32_t(__shfl(int(inc), f)), f_cnt = uint32_t(__shfl(int(cnt), f)), f_off = uint32_t(__shfl(int(h.y), f));
         const uint32_t f_dst = uint32_t(__shfl(int(dst), f));
         if (j < total) {
@@ -1516,7 +1559,7 @@ __global__ void __launch_bounds__(256) k_nc_expand_batch(const TickDev *__restri
 
 // ============================================================================ launchers
 
-hipError_t launch_nbr_cache_batch(hipStream_t s, const TickDev *ticks, int n, const TickDev *b)
+hipError_t launch_nbr_cache_batch(hipStream_t s, const TickDev *ticks, int n, const TickDev *b, bool behind_reorder)
 {
     int max_eval = 0;
     uint32_t shards = 1;
@@ -1525,9 +1568,17 @@ hipError_t launch_nbr_cache_batch(hipStream_t s, const TickDev *ticks, int n, co
         shards = max(shards, ticks[i].shard_mask + 1u);
     }
     if (max_eval <= 0) return hipSuccess;
-    RM_KLAUNCH(k_nc_claim_batch, dim3(cdiv(max_eval, 256), 1, n), dim3(256), 0, s, b);
-    RM_KLAUNCH(k_nc_fill_batch, dim3(1, shards, n), dim3(256), 0, s, b);
-    RM_KLAUNCH(k_nc_expand_batch, dim3(cdiv(max_eval, kBlock), 1, n), dim3(kBlock), 0, s, b);
+    const bool heard = ticks[0].nc.arena_rssi != nullptr;
+    if (heard && !behind_reorder) {
+        RM_KLAUNCH(k_nc_expand_batch, dim3(cdiv(max_eval, kBlock), 1, n), dim3(kBlock), 0, s, b);
+    } else if (heard) {
+        RM_KLAUNCH(k_nc_claim_batch, dim3(cdiv(max_eval, 256), 1, n), dim3(256), 0, s, b);
+        RM_KLAUNCH(k_nc_fill_batch, dim3(cdiv(max_eval, kBlock), 1, n), dim3(kBlock), 0, s, b);
+    } else if (!behind_reorder) {
+        RM_KLAUNCH(k_nc_claim_batch, dim3(cdiv(max_eval, 256), 1, n), dim3(256), 0, s, b);
+        RM_KLAUNCH(k_nc_fill_batch, dim3(1, shards, n), dim3(256), 0, s, b);
+        RM_KLAUNCH(k_nc_expand_batch, dim3(cdiv(max_eval, kBlock), 1, n), dim3(kBlock), 0, s, b);
+    }
     return hipGetLastError();
 }
 

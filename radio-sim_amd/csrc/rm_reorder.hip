@@ -17,9 +17,14 @@ namespace rm {
 // lanes take a frame each (three links per frame, thousands of frames), neighbouring lanes with neighbouring frames read
 // neighbouring segments and write neighbouring records: 64 frames G apart were 64 lines per load and per store instruction
 // (configs[3]: 888 MB of counter traffic per 128 ticks for 45 MB of records).
-template <bool STOCH, bool SINR, int MODE>
+// NC (batches without draws and without SINR only: lone ticks keep their code): the source cache's heard form may be on
+// (t.nc.arena_rssi, block-uniform).  The scan of cursor[] then includes the frames served from a list -- slot_off, out_count and
+// the packets' offsets come from it -- but the walk leaves them out: k_reorder_served_batch writes their records.
+template <bool STOCH, bool SINR, int MODE, bool NC = false>
 RM_D void reorder_body(const ModelDev &m, const TickDev &t, const int cwl)
 {
+    static_assert(!NC || MODE == 1 || MODE == 3 || MODE == 4, "served frames are told apart where the counts sit in LDS");
+    const bool nc_heard = NC && t.nc.arena_rssi != nullptr;
     __shared__ uint32_t s_off[scan_lds(MODE)];
     __shared__ uint32_t s_wave[4];
     const bool publisher = blockIdx.x == 0;
@@ -43,6 +48,7 @@ RM_D void reorder_body(const ModelDev &m, const TickDev &t, const int cwl)
     if (q0 < n_new) {
         src0 = uniform_u(t.seg_off[int(q0) + t.shift]);
         len = uniform_u(t.cursor[int(q0) + t.shift]);
+        if (NC && nc_heard && uniform_u(t.nc.hit[int(q0)].x) != 0u) len = 0u; // (served: cursor is its list's length, it has no segment)
         if (uint32_t(lane) < len) {
             const uint32_t o = src0 + lane;
             mine = t.a_dst[o];
@@ -89,6 +95,7 @@ RM_D void reorder_body(const ModelDev &m, const TickDev &t, const int cwl)
             if (qi < n_new) {
                 const int sl = int(qi) + t.shift;
                 my_len = s_off[sl + 1] - s_off[sl];
+                if (NC && nc_heard && t.nc.hit[int(qi)].x != 0u) my_len = 0u; // served from its source's list
                 if (my_len) my_src = t.seg_off[sl];
             }
             // A frame with a handful of heard links (sixteen channels: three per frame) is its LANE's own business: the lane ranks its
@@ -206,7 +213,60 @@ __global__ void __launch_bounds__(256) k_reorder(ModelDev m, TickDev t)
 template <bool STOCH, int SCAN, bool SINR = false>
 __global__ void __launch_bounds__(256) k_reorder_batch(const ModelDev m, const TickDev *__restrict__ ticks, const int cwl)
 {
-    reorder_body<STOCH, SINR, SCAN>(m, ticks[blockIdx.z], cwl);
+    reorder_body<STOCH, SINR, SCAN, !STOCH && !SINR>(m, ticks[blockIdx.z], cwl);
+}
+
+// The source cache's heard form (NbrCacheDev): the ordered records of the frames that were served from a list.  One wave per
+// 64 consecutive frames; every hit frame's list is copied with full lanes from the arena's columns to the frame's place
+// slot_off[slot] (an entry finds its frame by bisection over the lanes' running counts).  Consecutive frames have adjacent
+// output ranges, so the wave's stores coalesce.  Launched right behind k_reorder_batch, whose publisher wrote slot_off.
+__global__ void __launch_bounds__(256) k_reorder_served_batch(const TickDev *__restrict__ ticks)
+{
+    const TickDev &t = ticks[blockIdx.z];
+    if (t.nc.arena_rssi == nullptr || uniform_u(t.nc.tick_cnt[2]) == 0u) return;
+    const int lane = threadIdx.x & 63;
+    const int e0 = int(blockIdx.x) * kBlock + wave_index() * 64;
+    const int e = e0 + lane;
+    uint2 h = make_uint2(0u, 0u);
+    if (e < t.n_active - t.first_new) h = t.nc.hit[e]; // (the cache serves ticks with first_eval == first_new == 0: frame == packet)
+    const uint32_t cnt = h.x > 1u ? h.x - 1u : 0u; // (0: swept, or an empty list)
+    const uint32_t dst = cnt ? t.slot_off[e + t.shift] : 0u;
+    const uint32_t inc = wave_inclusive_scan(cnt, lane);
+    const uint32_t total = uniform_u(uint32_t(__shfl(int(inc), 63)));
+    // four rounds of 64 entries at a time: all their loads are requested before the first store (the arena and the records may
+    // alias as far as the compiler knows, so it would wait for every round's loads on its own)
+    constexpr int kRounds = 4;
+    for (uint32_t j0 = 0; j0 < total; j0 += 64u * kRounds) { // wave-uniform
+        uint32_t d[kRounds];
+        bool ok[kRounds];
+        int pkt[kRounds], v_dst[kRounds];
+        double v_rssi[kRounds];
+        uint8_t v_verdict[kRounds];
+#pragma unroll
+        for (int u = 0; u < kRounds; ++u) {
+            const uint32_t j = j0 + uint32_t(u * 64 + lane);
+            const int f = wave_run_of(inc, j);
+            const uint32_t f_inc = uint32_t(__shfl(int(inc), f)), f_cnt = uint32_t(__shfl(int(cnt), f)), f_off = uint32_t(__shfl(int(h.y), f));
+            const uint32_t f_dst = uint32_t(__shfl(int(dst), f));
+            const uint32_t k = j - (f_inc - f_cnt);
+            const uint32_t a = f_off + k;
+            d[u] = f_dst + k;
+            pkt[u] = e0 + f;
+            ok[u] = j < total && d[u] < t.cap && a < t.nc.arena_len; // (a: the claim kept every list inside the arena; guarded like every read of it)
+            v_dst[u] = ok[u] ? t.nc.arena[a] : 0;
+            v_rssi[u] = ok[u] ? t.nc.arena_rssi[a] : 0.0;
+            v_verdict[u] = ok[u] ? t.nc.arena_verdict[a] : uint8_t(0);
+        }
+#pragma unroll
+        for (int u = 0; u < kRounds; ++u) {
+            if (ok[u]) {
+                t.out_pkt[d[u]] = pkt[u];
+                t.out_dst[d[u]] = v_dst[u];
+                t.out_rssi[d[u]] = v_rssi[u];
+                t.out_verdict[d[u]] = v_verdict[u];
+            }
+        }
+    }
 }
 
 // ============================================================================ Java-RNG draws
@@ -651,6 +711,8 @@ hipError_t launch_reorder_batch(hipStream_t s, const NodesDev &nd, const ModelDe
     const int scan = batch_scan_variant(ticks, n);
     int max_new = 0;
     for (int i = 0; i < n; ++i) max_new = max(max_new, ticks[i].n_active - ticks[i].first_new);
+    // (the source cache's heard form: the walk tells served frames apart where the counts sit in LDS -- every variant a batch takes)
+    if (ticks[0].nc.arena_rssi != nullptr && scan != 1 && scan != 3 && scan != 4) return hipErrorInvalidValue;
     // two frames per wave (every workgroup redoes the scan of the per-frame counts first: fewer, longer
     // workgroups); a receiver partition hears 1/share of a frame's links, so its waves take more
     // ... and every workgroup redoes the scan over all frames of its tick: with thousands of frames per tick
@@ -692,6 +754,8 @@ hipError_t launch_reorder_batch(hipStream_t s, const NodesDev &nd, const ModelDe
         else if (scan == 4) RM_KLAUNCH((k_reorder_batch<false, 4>), grid, block, 0, s, m, b, cwl);
         else RM_KLAUNCH((k_reorder_batch<false, 1>), grid, block, 0, s, m, b, cwl);
     }
+    if (ticks[0].nc.arena_rssi != nullptr && max_new > 0)
+        RM_KLAUNCH(k_reorder_served_batch, dim3(cdiv(max_new, kBlock), 1, n), dim3(kBlock), 0, s, b);
     return hipGetLastError();
 }
 
