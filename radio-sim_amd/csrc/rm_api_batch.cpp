@@ -225,11 +225,9 @@ int rmh::launch_batch(rm_context *c, TickSlot *const *slots, const TickPlan *pla
         // the ticks' frame lists: the descriptors' frame counts are the device's from here on (the medium itself, not the
         // sweep's override: the SINR medium's candidate level is its interference floor)
         RM_TRY(stage(RM_STAGE_FILTER));
-        int max_frames = 1;
-        for (int b = 0; b < n; ++b) max_frames = std::max(max_frames, ticks[b].n_pub);
         rm::RankFramesArgs rf = *rank_frames;
         rf.sweep_level = m.ld_level;
-        RM_HIP(rm::launch_rank_frames(s, nd, model_dev(c), dev_ticks, n, max_frames, rf));
+        RM_HIP(rm::launch_rank_frames(s, nd, model_dev(c), dev_ticks, n, rf));
     }
     // (RM_BATCH_FRAMES; not over a rank's frame list: k_tick_frames_batch writes no offsets by global packet number, which the result readers
     // of such a slot take)

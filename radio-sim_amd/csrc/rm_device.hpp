@@ -204,6 +204,93 @@ RM_D RunInfo run_prefix(int key, bool pred, int lane)
 // test uses the very same expression (monotone in each |d|)
 RM_D float dist2_f32(float dx, float dy, float dz) { return fmaf(dz, dz, fmaf(dy, dy, dx * dx)); }
 
+// THE box test of every cull level (receiver group, filter workgroup, block of workgroups, partition): the frame's pre-filter
+// record f (position, squared cut-off in w) against a box (x0, y0, x1, y1) / (z0, z1) -- clamped, squared, compared with f.w
+RM_D bool box_near(const float4 &qb, const float2 &qz, const float4 &f)
+{
+    const float dx = fmaxf(fmaxf(qb.x - f.x, f.x - qb.z), 0.f);
+    const float dy = fmaxf(fmaxf(qb.y - f.y, f.y - qb.w), 0.f);
+    const float dz = fmaxf(fmaxf(qz.x - f.z, f.z - qz.y), 0.f);
+    return dist2_f32(dx, dy, dz) <= f.w;
+}
+
+// A union of boxes and of the channel masks that go with them (receiver groups -> filter workgroup -> block of workgroups ->
+// partition); every level's box contains the boxes below it, so box_near against it is conservative for them.
+struct BoxUnion {
+    float4 xy; // (x0, y0, x1, y1)
+    float2 z;  // (z0, z1)
+    uint32_t chmask;
+};
+RM_D BoxUnion box_union_empty()
+{
+    const float inf_ = __builtin_inff();
+    BoxUnion u;
+    u.xy = make_float4(inf_, inf_, -inf_, -inf_);
+    u.z = make_float2(inf_, -inf_);
+    u.chmask = 0u;
+    return u;
+}
+RM_D void box_union_add(BoxUnion &u, const float4 &q, const float2 &qz, const uint32_t chmask)
+{
+    u.xy.x = fminf(u.xy.x, q.x);
+    u.xy.y = fminf(u.xy.y, q.y);
+    u.xy.z = fmaxf(u.xy.z, q.z);
+    u.xy.w = fmaxf(u.xy.w, q.w);
+    u.z.x = fminf(u.z.x, qz.x);
+    u.z.y = fmaxf(u.z.y, qz.y);
+    u.chmask |= chmask;
+}
+// ... over the lanes of a wave: a butterfly at distances d0, d0 / 2, .. 1 (32: the whole wave, 8: every 16 lanes)
+RM_D void box_union_lanes(BoxUnion &u, const int d0)
+{
+#pragma unroll
+    for (int d = d0; d >= 1; d >>= 1)
+        box_union_add(u, make_float4(__shfl_xor(u.xy.x, d), __shfl_xor(u.xy.y, d), __shfl_xor(u.xy.z, d), __shfl_xor(u.xy.w, d)),
+                      make_float2(__shfl_xor(u.z.x, d), __shfl_xor(u.z.y, d)), uint32_t(__shfl_xor(int(u.chmask), d)));
+}
+// Second level of the sweep on the shadowed medium: with this link's shadowing deviate, can it still reach the level?
+// tbl: the conservative table of the largest link hash that can, per bin of rho = s2 / thr (inv: bins / thr of the frame,
+// 0: the table is not usable for it -- bin 0 always passes); the hash is of the ordered (source, receiver) pair.
+RM_D bool shadow_pass(const ModelDev &m, const uint32_t *tbl, const float s2, const float inv, const int src, const int orig)
+{
+    const int bin = min(kShadowBins - 1, int(s2 * inv));
+    const uint32_t a = uint32_t(src), b = uint32_t(orig);
+    const uint64_t key = (uint64_t(a < b ? a : b) << 32) | uint64_t(a < b ? b : a);
+    return uint32_t(mix64(m.ld_seed_mixed ^ key) >> 32) <= tbl[bin];
+}
+// bins / thr of a frame for that table.  It is indexed by rho = s2 / thr: usable if the fp32 frame error is small against
+// the distances where it decides anything (d > 0.15 cut), else 0
+RM_D float prefilter_inv(const ModelDev &m, const float4 &f)
+{
+    float inv = 0.f;
+    if (m.shadow_tbl && f.w > 0.f && f.w < __builtin_inff()) {
+        const double cut = sqrt(double(f.w));
+        if (2.0 * m.f32_slack / (0.15 * cut) + 1e-5 <= kShadowPad) inv = float(kShadowBins) / f.w;
+    }
+    return inv;
+}
+
+// What a tick's pre-pass zeroes for the kernels behind it -- the next tick's counters (other parity: nothing touches them
+// during this tick), the words later kernels of this tick (cursor) or the next tick's filter (candidate totals) add to, a
+// batch's per-receiver link lists or sums -- shared by `stride` threads, this one the `first`-th of them.
+RM_D void tick_zero_duties(const TickDev &t, const int first, const int stride)
+{
+    if (first < 8) t.next_counters[first] = 0u;
+    for (int i = first; i < kShards; i += stride) t.next_shard_count[i * kShardStride] = 0u;
+    if (!t.use_matrix)
+        for (int i = first; i < t.zero_len; i += stride) {
+            t.cursor[i] = 0u;
+            t.cand_tot_next[i] = 0u;
+        }
+    if (t.reset_heads) // SINR tick of a batch: every receiver's link list starts empty
+        for (int i = first; i < t.n_rx; i += stride) t.head[i] = -1;
+    if (t.acc_lo) // ... or, summed per receiver (TickDev::acc_lo): every receiver's sum starts at zero, nobody is on the air yet
+        for (int i = first; i < t.n_rx; i += stride) {
+            t.acc_lo[i] = 0ull;
+            t.acc_hi[i] = 0ull;
+        }
+}
+
 // The sweep's conservative tests for one (node, frame) pair, shared by the query (k_energy_sum), the gate (k_cca_gate) and the gated batch (rm_ccabatch.hip): same
 // channel, not the node's own frame (RM_ED_TRANSMITTING says that it is sending), fp32 distance against the squared cut-off (which
 // carries the fp32 frame's slack), the shadowed medium's link-hash table (tbl: its kShadowBins words, staged in LDS).  A node
@@ -220,10 +307,7 @@ RM_D bool ed_candidate(const ModelDev &m, const uint32_t *tbl, const EdNode &nv,
     const float s2 = dist2_f32(nv.px - f.x, nv.py - f.y, nv.pz - f.z);
     if (!(s2 <= f.w)) return false;
     if (!nv.shadow) return true;
-    const int bin = min(kShadowBins - 1, int(s2 * __int_as_float(fm.w)));
-    const uint32_t a = uint32_t(fm.z), b = uint32_t(nv.j);
-    const uint64_t key = (uint64_t(a < b ? a : b) << 32) | uint64_t(a < b ? b : a);
-    return uint32_t(mix64(m.ld_seed_mixed ^ key) >> 32) <= tbl[bin];
+    return shadow_pass(m, tbl, s2, __int_as_float(fm.w), fm.z, nv.j);
 }
 
 // a 64-bit sum over the lanes of a wave (the gates add 128-bit Q80 sums limb by limb: integer adds, the order cannot matter)

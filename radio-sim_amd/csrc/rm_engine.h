@@ -19,7 +19,8 @@
 // Reference paths: /root/reference/radio-medium/java/se/sics/emul8/radiomedium/.
 //
 // Files: rm_math.hpp (exact arithmetic: E-math, link hash, Q80, java.util.Random), rm_device.hpp
-// (shared device code: wave helpers, pre-filter records, eval_link, fused scans), rm_filter.hip,
+// (shared device code: wave helpers, pre-filter records, the box test and box unions, eval_link, fused scans), rm_nodes.hip
+// (node table, Tx packing), rm_filter.hip (the sweeps), rm_rankframes.hip, rm_nbrcache.hip,
 // rm_exact.hip, rm_reorder.hip, rm_transmit.hip, rm_tick.hip, rm_events.hip (kernels + their launchers),
 // rm_evorder.hpp (the reference event queue's pop order as a sort key), rm_api_*.cpp (C ABI, by concern).
 #pragma once
@@ -714,7 +715,7 @@ struct LaunchCfg {
     bool shadow;      // second-level shadowing filter (table lookup on the link hash)
 };
 
-// kernels' host launchers (rm_filter.hip, rm_exact.hip, rm_reorder.hip, rm_transmit.hip)
+// kernels' host launchers (rm_nodes.hip, rm_filter.hip, rm_exact.hip, rm_reorder.hip, rm_transmit.hip)
 hipError_t launch_prep_rx(hipStream_t s, const NodesDev &nd, const ModelDev &m);
 hipError_t launch_patch_nodes(hipStream_t s, const NodesDev &nd, const NodePatch *dev_list, int n, const NodePatch &one);
 hipError_t launch_pack_tx(hipStream_t s, const NodesDev &nd, const int32_t *dev_src, int n, int64_t start_us,
@@ -747,7 +748,7 @@ bool batch_eligible(const TickDev &t, const LaunchCfg &cfg, const ModelDev &m);
 hipError_t launch_store_ticks(hipStream_t s, const TickDev *ticks, int n, TickDev *dev_ticks);
 hipError_t launch_filter_batch(hipStream_t s, const NodesDev &nd, const ModelDev &m, const TickDev *ticks, int n,
                                const TickDev *dev_ticks, const LaunchCfg &cfg);
-// (rm_filter.hip) the rank-level frame lists of a batch of gathered ticks: which of all ranks' frames can matter to THIS partition's
+// (rm_rankframes.hip) the rank-level frame lists of a batch of gathered ticks: which of all ranks' frames can matter to THIS partition's
 // receivers (m: the medium whose candidate level bounds the reach -- the SINR medium's interference floor where it has one);
 // margin: metres added around the partition's boxes (frames that stay on the air: a receiver may move while they do);
 // digests: the ranks' node-table digests as the all-gather left them (gather_base + r * gather_block + digest_off, two words
@@ -775,7 +776,7 @@ struct RankFramesArgs {
     int64_t t_first, batch_end; // the batch's first t_begin, the end of its last frame
 };
 hipError_t launch_cull_check(hipStream_t s, const NodesDev &nd, const CullEntry *ring, int64_t t_begin, uint32_t *flag_word);
-hipError_t launch_rank_frames(hipStream_t s, const NodesDev &nd, const ModelDev &m, TickDev *dev_ticks, int n, int max_frames, const RankFramesArgs &a);
+hipError_t launch_rank_frames(hipStream_t s, const NodesDev &nd, const ModelDev &m, TickDev *dev_ticks, int n, const RankFramesArgs &a);
 constexpr int kGatherTrailer = RM_GATHER_TRAILER; // words behind a rank's source indices in its block of a sharded batch
 hipError_t launch_stage_block(hipStream_t s, const int32_t *src, int n, uint64_t digest, int32_t *dst);
 int filter_ticks_per_wg(const TickDev &t0, int n);

@@ -51,14 +51,6 @@ constexpr int kFrCand = kFrRound * kGroup;
     } while (0)
 #endif
 
-RM_D bool box_near(const float4 &qb, const float2 &qz, const float4 &f)
-{
-    const float dx = fmaxf(fmaxf(qb.x - f.x, f.x - qb.z), 0.f);
-    const float dy = fmaxf(fmaxf(qb.y - f.y, f.y - qb.w), 0.f);
-    const float dz = fmaxf(fmaxf(qz.x - f.z, f.z - qz.y), 0.f);
-    return dist2_f32(dx, dy, dz) <= f.w;
-}
-
 // Which frame does workgroup b take?  The hardware deals workgroups to the eight XCDs in turn (b % 8), each with its own L2.  With
 // xcd_map the frames of a tick are dealt in EIGHTHS instead -- XCD x takes the x-th eighth of the slots -- so that, where the
 // caller's frame order is a spatial order (node ids assigned along a space-filling curve), the frames that share receiver groups

@@ -224,12 +224,7 @@ __global__ void __launch_bounds__(1024) k_transmit_one(const NodesDev nd, const 
     } else if (f.w >= 0.f) {
         // level 1: boxes of 16 groups
         for (int b = tid; b < n_boxes; b += blockDim.x) {
-            const float4 q = nd.wg_box_xy[b];
-            const float2 qz = nd.wg_box_z[b];
-            const float dx = fmaxf(fmaxf(q.x - f.x, f.x - q.z), 0.f);
-            const float dy = fmaxf(fmaxf(q.y - f.y, f.y - q.w), 0.f);
-            const float dz = fmaxf(fmaxf(qz.x - f.z, f.z - qz.y), 0.f);
-            if (dist2_f32(dx, dy, dz) <= f.w) {
+            if (box_near(nd.wg_box_xy[b], nd.wg_box_z[b], f)) {
                 const uint32_t k = atomicAdd(&s_n1, 1u);
                 if (k < uint32_t(kOneL1)) s_l1[k] = b; else s_over = 1u;
             }
@@ -242,12 +237,7 @@ __global__ void __launch_bounds__(1024) k_transmit_one(const NodesDev nd, const 
         for (int i = tid; i < n1 * 16; i += blockDim.x) {
             const int g = s_l1[i >> 4] * 16 + (i & 15);
             if (g >= n_groups) continue;
-            const float4 q = nd.bbox_xy[g];
-            const float2 qz = nd.bbox_z[g];
-            const float dx = fmaxf(fmaxf(q.x - f.x, f.x - q.z), 0.f);
-            const float dy = fmaxf(fmaxf(q.y - f.y, f.y - q.w), 0.f);
-            const float dz = fmaxf(fmaxf(qz.x - f.z, f.z - qz.y), 0.f);
-            if (dist2_f32(dx, dy, dz) <= f.w) {
+            if (box_near(nd.bbox_xy[g], nd.bbox_z[g], f)) {
                 const uint32_t k = atomicAdd(&s_n2, 1u);
                 if (k < uint32_t(kOneL2)) s_l2[k] = g; else s_over = 1u;
             }
