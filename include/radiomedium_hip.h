@@ -753,6 +753,48 @@ int rm_stats_read(rm_context *ctx, const int32_t *nodes, int32_t n, rm_node_stat
  * count (or rm_nodes_upload changes it) or the context is destroyed; the caller's reads are ordered by the context's stream */
 int rm_stats_device(rm_context *ctx, const rm_node_stats **dev_table, const rm_stats_totals **dev_totals);
 
+/* ---- unicast outcome query: did a frame reach its destination -------------------------------------------------------
+ * (not reference behaviour.)  The medium is broadcast: a result lists every receiver that
+ * heard a frame.  The query answers, on the device and over the FINISHED results of the last evaluating call, what became of a
+ * frame at the one node it was addressed to.  A query entry names a result slot b (tick b of the last batch; slot 0 is also the
+ * last lone tick, as rm_result_* reads it), a packet number p in that slot and a wanted node w.  With n_new(b) the slot's new
+ * frames, rec = tx[first_new + p] the frame's record and [lo, hi) = [pkt_offset[p], pkt_offset[p + 1]) its segment of heard links
+ * (dst ascends inside it), the FIRST rule that applies gives the entry's status:
+ *   RM_UC_NONE        w < 0, b < 0, b >= slots of the last call, p < 0 or p >= n_new(b): nothing asked, or no such packet (a CSMA-CA
+ *                     packet that was not sent has tick / pkt -1);
+ *   RM_UC_LOST        the slot overflowed its link capacity or was dropped (what the traffic counters skip);
+ *   RM_UC_NOT_SENT    rec.src outside 0 .. n_nodes-1 (padding, a candidate a gate deferred, a CSMA-CA slot not made);
+ *   RM_UC_UNHEARD     no link i in [lo, hi) with dst[i] == w (so for w == rec.src, and for w >= n_nodes in a device list);
+ *   RM_UC_INTERFERED  that link exists and its final verdict is not RM_DELIVERED;
+ *   RM_UC_DELIVERED   that link exists and its final verdict is RM_DELIVERED.
+ * Final: after the draws, the SINR stages and the frame error model's pass -- what every result reader sees.  Outputs per entry
+ * (rm_unicast_out; any pointer may be NULL): status; link = i, the link's index into the slot's arrays, for the last two and -1
+ * otherwise; rssi and sinr bit for bit what rm_result_copy / rm_batch_result_copy give at that index, NaN without a link, sinr NaN
+ * on media without the SINR column; reply_src = w where the frame was delivered and -1 otherwise -- the list has the shape of a
+ * source list and can be handed to rm_tick_run_sources_device as it lies in device memory (the acknowledgement tick).  It names a
+ * node twice when two packets were delivered to the same destination: that is the caller's business.
+ * status, rssi bits and sinr bits of a frame at its wanted receiver do not depend on whether a lone tick, a batch, a gated batch, a
+ * CSMA-CA batch or any split of a CSMA-CA run into carry batches evaluated it; link is a position and may differ.
+ * The query only reads: results, the on-air window and the generator are never touched, and nothing is launched before a refusal.
+ * RM_ERR_STATE: no evaluated result yet; a context with a receiver partition (links of other ranks are not there); after a gathered
+ * / rm_dist_* / rm_group_* call; a context made under RM_GRAPH=1.  RM_ERR_INVALID: NULL arguments, negative counts, n_slots outside
+ * 1 .. slots of the last call, n_pkt[b] < 0, a want >= n_nodes in a HOST list.  RM_ERR_CAPACITY: more than 2^27 entries.
+ * The device forms enqueue on the context's stream and do not wait: the outputs are valid when the stream reaches them.  The host
+ * forms synchronise the stream once.  The slots are read as they are until the next evaluating call. */
+enum rm_unicast_status { RM_UC_NONE = 0, RM_UC_NOT_SENT = 1, RM_UC_UNHEARD = 2, RM_UC_INTERFERED = 3, RM_UC_DELIVERED = 4, RM_UC_LOST = 5 };
+typedef struct rm_unicast_out { uint8_t *status; int32_t *link; double *rssi; double *sinr; int32_t *reply_src; } rm_unicast_out; /* any may be NULL */
+/* packets 0 .. n_pkt[b]-1 of slots 0 .. n_slots-1, flat in slot order; n_pkt is a host array (entries past a slot's packets: RM_UC_NONE) */
+int rm_unicast_query_device(rm_context *ctx, int32_t n_slots, const int32_t *n_pkt, const int32_t *dev_want, const rm_unicast_out *dev_out);
+int rm_unicast_query(rm_context *ctx, int32_t n_slots, const int32_t *n_pkt, const int32_t *want, const rm_unicast_out *out);
+/* entry e names (slot[e], pkt[e]): exactly the tick / pkt columns of rm_csma_result (own or carried packets) */
+int rm_unicast_query_at_device(rm_context *ctx, int64_t n, const int32_t *dev_slot, const int32_t *dev_pkt, const int32_t *dev_want,
+                               const rm_unicast_out *dev_out);
+int rm_unicast_query_at(rm_context *ctx, int64_t n, const int32_t *slot, const int32_t *pkt, const int32_t *want, const rm_unicast_out *out);
+/* pure host function, no device (like rm_csma_carry_collect): the same answer from one tick's host result, packets 0 .. r->n_packets-1.
+ * src[n_packets] may be NULL (every packet sent); reads pkt_offset, dst, verdict, rssi or pkt_rssi, sinr (NULL: NaN); r->count /
+ * capacity problems are the caller's (no RM_UC_LOST).  RM_ERR_INVALID: NULL r / want / out, n_nodes < 0, a want >= n_nodes. */
+int rm_unicast_from_result(const rm_host_result *r, const int32_t *src, int32_t n_nodes, const int32_t *want, const rm_unicast_out *out);
+
 /* ---- several devices behind one caller --------------------------------------------------------------
  * The reference host is ONE process (Main.java:65-73): a group drives n contexts from one host thread, one
  * per device (an ordinal may repeat: several partitions on one GPU).  Receivers are partitioned over the

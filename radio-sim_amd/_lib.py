@@ -63,6 +63,14 @@ class StatsTotals(C.Structure):
     _fields_ = [("ticks_counted", C.c_uint64), ("ticks_skipped", C.c_uint64)]
 
 
+class UnicastOut(C.Structure):
+    """rm_unicast_out: the output arrays of the unicast outcome query; any may be NULL"""
+    _fields_ = [("status", C.c_void_p), ("link", C.c_void_p), ("rssi", C.c_void_p), ("sinr", C.c_void_p), ("reply_src", C.c_void_p)]
+
+
+UC_NONE, UC_NOT_SENT, UC_UNHEARD, UC_INTERFERED, UC_DELIVERED, UC_LOST = 0, 1, 2, 3, 4, 5
+UNICAST_FIELDS = (("status", np.uint8), ("link", np.int32), ("rssi", np.float64), ("sinr", np.float64), ("reply_src", np.int32))
+
 NODE_STATS_DTYPE = np.dtype([(name, "<u8") for name, _ in NodeStats._fields_])
 assert NODE_STATS_DTYPE.itemsize == C.sizeof(NodeStats) == 64
 
@@ -303,6 +311,11 @@ SIGNATURES = {
     "rm_stats_reset": (C.c_int, [C.c_void_p]),
     "rm_stats_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(StatsTotals)]),
     "rm_stats_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "rm_unicast_query_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_unicast_query": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_unicast_query_at_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_unicast_query_at": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_unicast_from_result": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "rm_det_math": (C.c_double, [C.c_int32, C.c_double]),
     "rm_link_hash": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
     "rm_evq_init": (None, [C.c_void_p]),

@@ -262,6 +262,7 @@ int rm_dist_tick_run_sources_device(rm_context *c, int64_t t_begin_us, int64_t t
     RM_HIP(rm::launch_pack_tx(c->stream, nodes_dev(c), all, slots * world, start_us, air_us, c->d_dist_all.p));
     // (the SINR medium keeps the frames on the air: the packed frames all end at start + air)
     RM_TRY(rm_tick_run_records_device(c, t_begin_us, t_end_us, c->d_dist_all.p, slots * world, start_us + air_us));
+    uc_ran(c, 1, true); // (a gathered tick: the unicast query refuses it)
     return comm_finish_draws(c);
 }
 

@@ -136,6 +136,7 @@ void ev_batch_ran(rm_context *c, int rc, int n_ticks, bool eligible)
     v.batch_n = (rc == RM_OK && v.on) ? n_ticks : 0;
     v.batch_ok = eligible;
     v.batch_gen = v.gen;
+    if (rc == RM_OK) uc_ran(c, n_ticks, !eligible); // (the unicast query, E12: the batch's slots; not eligible = a gathered / rm_dist_* form)
 }
 
 } // namespace rmh

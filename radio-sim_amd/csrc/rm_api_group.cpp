@@ -319,8 +319,10 @@ int rm_group_tick_run_sources_device(rm_group *g, int64_t t_begin_us, int64_t t_
         }
     }
     // every member sweeps the gathered frames against its receivers; all launches are enqueued before anything is waited for
-    for (rm_context *c : g->m)
+    for (rm_context *c : g->m) {
         RM_TRY(rm_tick_run_records_device(c, t_begin_us, t_end_us, c->d_dist_all.p, slots * world, start_us + air_us));
+        uc_ran(c, 1, true); // (a gathered tick: the unicast query refuses it)
+    }
     g->n_new = slots * world;
     return group_finish_draws(g, g->n_new);
 }
@@ -343,7 +345,10 @@ int rm_group_tick_flush(rm_group *g, int32_t *pkt, int32_t *dst, uint8_t *verdic
     g->in_tick = false;
     const int n_new = g->n_new;
     // every member's launches are enqueued before anything is waited for
-    for (rm_context *c : g->m) RM_TRY(tick_run_host(c));
+    for (rm_context *c : g->m) {
+        RM_TRY(tick_run_host(c));
+        uc_ran(c, 1, true); // (a group's tick: the unicast query refuses it)
+    }
     RM_TRY(group_finish_draws(g, n_new));
     return group_merge(g, n_new, pkt, dst, verdict, rssi, sinr, cap, count, pkt_interference, pkt_offset);
 }

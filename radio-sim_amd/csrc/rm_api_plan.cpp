@@ -605,6 +605,7 @@ int run_tick(rm_context *c, const rm_tx_record *tx, int n_active, int first_new,
     TickPlan plan;
     RM_TRY(prepare_tick(c, *c, plan, false, tx, n_active, first_new, src_list, src_start_us, src_air_us, air_mode, air_oldest));
     RM_TRY(launch_tick(c, *c, plan));
+    uc_ran(c, 1, false); // (the unicast query reads slot 0 as the last lone tick)
     if (c->ev.on && !c->draws_pending) {
         if (plan.empty && c->last_n_new > 0) {
             // a tick without receivers on this rank: its packets exist all the same (slot_off of an empty tick is not written)

@@ -529,6 +529,20 @@ struct StatsDev {
     int n_nodes;
 };
 
+// The unicast outcome query (rm_unicast.hip): what the query reads of one finished result slot --
+// the compact packet-major arrays every result reader gets, the records of the tick's new frames, the slot's counters
+struct UcSlot {
+    const rm_tx_record *recs;    // [n_new] the tick's new frames (tx + first_new)
+    const uint32_t *pkt_offset;  // [n_new + 1] first link of every packet (nullptr: no packet has a link)
+    const int32_t *dst;          // ascending inside a packet's segment
+    const uint8_t *verdict;
+    const double *rssi, *sinr;   // sinr: nullptr on media without the column
+    const uint32_t *out_count;   // [0] links stored, [1] dropped flag, [2] links total (TickDev::out_count)
+    const uint32_t *stage_count; // [1] dropped for capacity (TickDev::stage_count; may be nullptr)
+    int n_new;
+    int pad;
+};
+
 // rm_transmit's result block in host-mapped (pinned) memory, written by k_pack_result
 constexpr int kTransmitMax = 2048;
 struct TransmitResult {
@@ -867,6 +881,14 @@ hipError_t launch_errmodel_batch(hipStream_t s, const EmDev &em, int n, const Ti
 hipError_t launch_stats(hipStream_t s, const StatsDev &sd, const TickDev &t);
 hipError_t launch_stats_batch(hipStream_t s, const StatsDev &sd, int n, const TickDev *dev_ticks);
 hipError_t launch_stats_gather(hipStream_t s, const StatsDev &sd, const int32_t *nodes, int n, rm_node_stats *out, rm_stats_totals *totals_out);
+
+// (rm_unicast.hip) the unicast outcome query, one launch: a lane per entry.  n_slots result slots described by dev_slots -- or, with
+// dev_slots == nullptr, the one slot `lone`.  Slots form (dev_prefix: [n_slots + 1] exclusive prefix of the entries per slot; nullptr
+// with one slot): entry e is packet e - prefix[b] of slot b.  At form: entry e names (dev_slot[e], dev_pkt[e]).
+hipError_t launch_unicast_slots(hipStream_t s, const UcSlot *dev_slots, const UcSlot &lone, int n_slots, const uint32_t *dev_prefix, int64_t n,
+                                int n_nodes, const int32_t *want, const rm_unicast_out &out);
+hipError_t launch_unicast_at(hipStream_t s, const UcSlot *dev_slots, const UcSlot &lone, int n_slots, int64_t n, int n_nodes,
+                             const int32_t *slot, const int32_t *pkt, const int32_t *want, const rm_unicast_out &out);
 
 // reception stage (rm_events.hip)
 hipError_t launch_ev_append(hipStream_t s, const EvDev &e, const EvLinkSrc &ls, const rm_tx_record *tx, int n_new, int64_t now,

@@ -156,6 +156,18 @@ struct rm_context : TickSlot {
         char *h_block = nullptr;
         size_t h_cap = 0; // nodes the block has room for
     } st;
+    // the unicast outcome query (E12; rm_api_unicast.cpp, rm_unicast.hip): what the last evaluating call left -- how many result slots,
+    // and whether it was a gathered / rm_dist_* / rm_group_* form -- the slots' descriptors in device memory (rm::UcSlot per slot,
+    // then the prefix of a slots-form query), their pinned staging (two blocks, each rewritten only after its copy has completed), and
+    // the host forms' device scratch (lists in, outputs out)
+    struct Unicast {
+        int slots = 0; // 0: no evaluating call yet
+        bool gathered = false;
+        DevBuf<char> d_desc, d_io;
+        char *h_desc[2] = {nullptr, nullptr};
+        hipEvent_t h_ev[2] = {nullptr, nullptr};
+        int gen = 0;
+    } uc;
     double base_rssi = -100.0; // AbstractRadioMedium.java:38
 
     // host mirror of the node table (Simulator.getNodes() snapshot)
@@ -664,6 +676,14 @@ rm::StatsDev stats_dev(const rm_context *c);
 int stats_check(const rm_context *c, bool gathered);
 // rm_nodes_upload: another node count resizes the table and zeroes it
 int stats_nodes_changed(rm_context *c);
+
+// ---- rm_api_unicast.cpp: the unicast outcome query (E12)
+// an evaluating call has left its results in `slots` result slots (gathered: a gathered / rm_dist_* / rm_group_* form)
+inline void uc_ran(rm_context *c, int slots, bool gathered)
+{
+    c->uc.slots = slots;
+    c->uc.gathered = gathered;
+}
 
 // ---- rm_api_comm.cpp
 int comm_all_gather(rm_context *c, const void *mine, void *all, size_t bytes);

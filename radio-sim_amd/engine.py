@@ -183,6 +183,82 @@ class Engine:
         check(self._L.rm_stats_device(self._h, C.byref(tbl), C.byref(tot)))
         return tbl.value, tot.value
 
+    # -- unicast outcome query: did a frame reach its destination
+    UC_NONE, UC_NOT_SENT, UC_UNHEARD, UC_INTERFERED = _lib.UC_NONE, _lib.UC_NOT_SENT, _lib.UC_UNHEARD, _lib.UC_INTERFERED
+    UC_DELIVERED, UC_LOST = _lib.UC_DELIVERED, _lib.UC_LOST
+
+    @staticmethod
+    def _unicast_host_out(n, fields):
+        """host arrays for n entries -> (rm_unicast_out, {name: array}); fields: the outputs asked for (None: all five)"""
+        arrs = {name: np.empty(n, dtype=dt) for name, dt in _lib.UNICAST_FIELDS if fields is None or name in fields}
+        return _lib.UnicastOut(**{name: a.ctypes.data for name, a in arrs.items()}), arrs
+
+    @staticmethod
+    def _unicast_dev_out(dev_out):
+        if isinstance(dev_out, _lib.UnicastOut):
+            return dev_out
+        return _lib.UnicastOut(**{name: (int(p) if p else None) for name, p in dev_out.items()})
+
+    def unicast_query(self, want_lists, fields=None):
+        """rm_unicast_query: want_lists[b][p] is the wanted node of packet p of result slot b (-1: not asked) -> dict of flat
+        numpy arrays status / link / rssi / sinr / reply_src, in slot order"""
+        lists = [np.ascontiguousarray(w, dtype=np.int32).reshape(-1) for w in want_lists]
+        n_pkt = np.array([len(w) for w in lists], dtype=np.int32)
+        want = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0), dtype=np.int32)
+        out, arrs = self._unicast_host_out(len(want), fields)
+        check(self._L.rm_unicast_query(self._h, len(lists), n_pkt.ctypes.data, want.ctypes.data, C.byref(out)))
+        return arrs
+
+    def unicast_query_device(self, n_pkt, dev_want_ptr, dev_out):
+        """rm_unicast_query_device: n_pkt[b] entries per slot (host), the wanted nodes and the outputs in device memory
+        (dev_out: a dict name -> device pointer, or a _lib.UnicastOut); enqueued on the context's stream, not waited for"""
+        n_pkt = np.ascontiguousarray(n_pkt, dtype=np.int32)
+        out = self._unicast_dev_out(dev_out)
+        check(self._L.rm_unicast_query_device(self._h, len(n_pkt), n_pkt.ctypes.data, dev_want_ptr, C.byref(out)))
+
+    def unicast_query_at(self, slot, pkt, want, fields=None):
+        """rm_unicast_query_at: entry e names (slot[e], pkt[e]) -- the tick / pkt columns of a CSMA-CA result -- and want[e]"""
+        slot, pkt, want = (np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (slot, pkt, want))
+        assert len(slot) == len(pkt) == len(want)
+        out, arrs = self._unicast_host_out(len(want), fields)
+        check(self._L.rm_unicast_query_at(self._h, len(want), slot.ctypes.data, pkt.ctypes.data, want.ctypes.data, C.byref(out)))
+        return arrs
+
+    def unicast_query_at_device(self, n, dev_slot_ptr, dev_pkt_ptr, dev_want_ptr, dev_out):
+        out = self._unicast_dev_out(dev_out)
+        check(self._L.rm_unicast_query_at_device(self._h, n, dev_slot_ptr, dev_pkt_ptr, dev_want_ptr, C.byref(out)))
+
+    @staticmethod
+    def unicast_from_result(result, src, n_nodes, want, fields=None):
+        """rm_unicast_from_result (pure host function): the same answer from one tick's host result -- a _lib.HostResult, or
+        anything with pkt_offset, dst, verdict and rssi or pkt_rssi (sinr optional), e.g. what tick_flush_view returns;
+        src: the packets' sources (None: every packet sent)"""
+        keep = []
+        if isinstance(result, HostResult):
+            r = result
+        else:
+            def col(name, dt):
+                a = getattr(result, name, None)
+                if a is None:
+                    return None
+                a = np.ascontiguousarray(a, dtype=dt)
+                keep.append(a)
+                return a.ctypes.data
+            off = np.ascontiguousarray(result.pkt_offset, dtype=np.uint32)
+            keep.append(off)
+            rssi = col("rssi", np.float64)
+            r = HostResult(count=int(result.count), n_packets=len(off) - 1, pkt_offset=off.ctypes.data, dst=col("dst", np.int32),
+                           verdict=col("verdict", np.uint8), rssi=rssi, sinr=col("sinr", np.float64),
+                           pkt_rssi=None if rssi is not None else col("pkt_rssi", np.float64))
+        want = np.ascontiguousarray(want, dtype=np.int32).reshape(-1)
+        assert len(want) == r.n_packets
+        if src is not None:
+            src = np.ascontiguousarray(src, dtype=np.int32).reshape(-1)
+            assert len(src) == r.n_packets
+        out, arrs = Engine._unicast_host_out(len(want), fields)
+        check(_lib.lib().rm_unicast_from_result(C.byref(r), _ptr(src), n_nodes, want.ctypes.data, C.byref(out)))
+        return arrs
+
     # -- java.util.Random
     def seed(self, seed):
         check(self._L.rm_seed(self._h, seed))

@@ -604,6 +604,34 @@ public:
         }
         return out;
     }
+    // Did a frame reach the node it was addressed to (extension E12)?  One entry per packet of the LAST evaluated tick -- the tick
+    // mode's flush, or transmitIfClear() -- in packet order: destinations[k] is packet k's intended receiver (nullptr: not asked).
+    // status is RM_UC_*; link the index of the heard link in the tick's result (-1 without one); rssi and sinr as the result has
+    // them (NaN without a link, sinr NaN on media without the SINR column).  Empty and lastError on a refusal.
+    struct UnicastOutcome {
+        int status;
+        int link;
+        double rssi, sinr;
+    };
+    std::vector<UnicastOutcome> unicastOutcomes(const std::vector<Node *> &destinations)
+    {
+        lastError.clear();
+        const size_t n = destinations.size();
+        std::vector<int32_t> want(n);
+        for (size_t k = 0; k < n; ++k) want[k] = destinations[k] ? destinations[k]->index : -1;
+        std::vector<uint8_t> status(n + 1);
+        std::vector<int32_t> link(n + 1);
+        std::vector<double> rssi(n + 1), sinr(n + 1);
+        const rm_unicast_out out = {status.data(), link.data(), rssi.data(), sinr.data(), nullptr};
+        const int32_t n_pkt = int32_t(n);
+        if (rm_unicast_query(ctx_, 1, &n_pkt, want.data(), &out) != RM_OK) {
+            lastError = rm_last_error();
+            return {};
+        }
+        std::vector<UnicastOutcome> res(n);
+        for (size_t k = 0; k < n; ++k) res[k] = UnicastOutcome{int(status[k]), int(link[k]), rssi[k], sinr[k]};
+        return res;
+    }
     std::string lastError;
     bool lastInterference = false;
 
@@ -1025,6 +1053,34 @@ public:
             }
         }
         return out;
+    }
+
+    // The same after transmitCsmaBatch() (extension E12): entry k asks for the packet of outcomes[k] -- the tick it was sent in and
+    // its position there -- at destinations[k]; a packet that was not sent (failed, pending, padding) gives RM_UC_NONE.  Ask before
+    // the next evaluating call of the medium.
+    using GpuRadioMedium::unicastOutcomes;
+    std::vector<UnicastOutcome> unicastOutcomes(const std::vector<CsmaOutcome> &outcomes, const std::vector<Node *> &destinations)
+    {
+        lastError.clear();
+        const size_t n = outcomes.size();
+        if (destinations.size() != n) { lastError = "one destination per outcome"; return {}; }
+        std::vector<int32_t> slot(n + 1), pkt(n + 1), want(n + 1), link(n + 1);
+        for (size_t k = 0; k < n; ++k) {
+            const bool sent = outcomes[k].status == RM_CSMA_SENT;
+            slot[k] = sent ? outcomes[k].tick : -1;
+            pkt[k] = sent ? outcomes[k].pkt : -1;
+            want[k] = destinations[k] ? destinations[k]->index : -1;
+        }
+        std::vector<uint8_t> status(n + 1);
+        std::vector<double> rssi(n + 1), sinr(n + 1);
+        const rm_unicast_out out = {status.data(), link.data(), rssi.data(), sinr.data(), nullptr};
+        if (rm_unicast_query_at(ctx_, int64_t(n), slot.data(), pkt.data(), want.data(), &out) != RM_OK) {
+            lastError = rm_last_error();
+            return {};
+        }
+        std::vector<UnicastOutcome> res(n);
+        for (size_t k = 0; k < n; ++k) res[k] = UnicastOutcome{int(status[k]), int(link[k]), rssi[k], sinr[k]};
+        return res;
     }
 
 private:
