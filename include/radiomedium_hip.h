@@ -795,6 +795,53 @@ int rm_unicast_query_at(rm_context *ctx, int64_t n, const int32_t *slot, const i
  * capacity problems are the caller's (no RM_UC_LOST).  RM_ERR_INVALID: NULL r / want / out, n_nodes < 0, a want >= n_nodes. */
 int rm_unicast_from_result(const rm_host_result *r, const int32_t *src, int32_t n_nodes, const int32_t *want, const rm_unicast_out *out);
 
+/* ---- receiver listening schedules: duty-cycled radios on the device ------------------------------------------------
+ * (not reference behaviour.)  Opt-in, on every medium.  One rm_listen_schedule per node
+ * index, a table of the context (like the traffic counters').  period_us = 0: the radio always listens (the default of every
+ * node; on_us and phase_us have to be 0 then).  period_us > 0: 0 <= on_us <= period_us and 0 <= phase_us < period_us.
+ * listening(s, t): 1 when s.period_us == 0; otherwise d = int64(uint64(t) - uint64(s.phase_us)) (a wrapping subtraction),
+ * r = d % s.period_us in C semantics, if (r < 0) r += s.period_us, and listening = r < s.on_us -- so on_us = 0 never listens and
+ * on_us = period_us always does.
+ * With schedules on, every evaluating call ends with one more pass over its finished result, behind the frame error model's pass
+ * and ahead of the traffic counters': a link whose verdict is RM_DELIVERED under everything else (Tx failure, capture, half
+ * duplex, the rxProbability draw, the error model) becomes RM_INTERFERED iff !listening(sched[dst], rec.start_us), rec =
+ * tx[first_new + pkt] the frame's own record -- the radio is sampled at the frame's first microsecond -- and missed[dst] += 1
+ * (uint64 per node: links that everything else had delivered and that sleep alone lost).  Nothing else changes: dst, rssi, sinr,
+ * pkt_offset, pkt_interference, the on-air window and java.util.Random are as with the feature off (a link at a sleeping receiver
+ * still consumes its draw; this is NOT setEnabled(false), which takes the receiver out of the sweep); the energy query and the
+ * gates (E5 - E9) ignore schedules (a CCA sample switches the radio on; the transmitter's own schedule plays no part).  A slot
+ * that overflowed its link capacity or was dropped is left as it is and counts nothing.  The traffic counters and the unicast
+ * query see the verdict after this pass.  A frame's verdict at a receiver and the missed table do not depend on whether a lone
+ * tick, a batch, a gated batch, a CSMA-CA batch or any split of a CSMA-CA run into carry batches evaluated it; with every
+ * period 0 the results are bit for bit those with the feature off.
+ * Accepted by every evaluating call the traffic counters accept, on a whole-table context.  With schedules on, rm_transmit on a
+ * reference medium takes the general tick path (same links), a lone tick writes its compact arrays at once, and a dense tick ends
+ * with its records: rm_result_dense is RM_ERR_STATE for it (one verdict per packet cannot express the pass).  Refused with
+ * RM_ERR_STATE before anything is launched, window, generator and tables untouched: contexts with a receiver partition, the
+ * gathered / rm_dist_* / rm_group_* forms; rm_listen_set on a context made under RM_GRAPH=1.
+ * rm_set_model, rm_seed, rm_node_update, rm_nodes_move and rm_nodes_upload with the same node count keep both tables;
+ * rm_nodes_upload with another node count clears the feature as rm_listen_clear does.  Off (the default): nothing is launched. */
+typedef struct rm_listen_schedule { int64_t period_us; int64_t on_us; int64_t phase_us; } rm_listen_schedule; /* 24 bytes */
+/* nodes == NULL: sched[n] for all nodes in node order, n has to be the node count; otherwise sched[k] for node nodes[k], applied in
+ * list order (the last entry of a node wins).  The whole list is validated before anything changes (RM_ERR_INVALID: a bad record, an
+ * index outside 0 .. n_nodes - 1, NULL arguments, a negative count).  Switches the feature on; ordered on the context's stream:
+ * it applies to calls evaluated after it. */
+int rm_listen_set(rm_context *ctx, const int32_t *nodes, int32_t n, const rm_listen_schedule *sched);
+/* the schedules of the listed nodes (the same list convention).  RM_ERR_STATE before the first rm_listen_set, as the calls below. */
+int rm_listen_get(rm_context *ctx, const int32_t *nodes, int32_t n, rm_listen_schedule *out);
+/* switches the feature off: every node always listens, missed is zeroed, nothing is launched afterwards */
+int rm_listen_clear(rm_context *ctx);
+int rm_listen_enabled(const rm_context *ctx);
+/* missed of the listed nodes in list order (nodes == NULL: all, n has to be the node count).  Synchronises the stream once. */
+int rm_listen_missed_read(rm_context *ctx, const int32_t *nodes, int32_t n, uint64_t *out);
+/* zeroes missed, on the context's stream */
+int rm_listen_missed_reset(rm_context *ctx);
+/* both tables ([n_nodes], by node index) in device memory: valid until rm_listen_clear, another node count or rm_destroy; the
+ * caller's reads are ordered by the context's stream */
+int rm_listen_device(rm_context *ctx, const rm_listen_schedule **dev_sched, const uint64_t **dev_missed);
+/* the listening rule itself, a pure host function without a device: 1, 0, or RM_ERR_INVALID for a NULL or bad record */
+int rm_listen_at(const rm_listen_schedule *s, int64_t t_us);
+
 /* ---- several devices behind one caller --------------------------------------------------------------
  * The reference host is ONE process (Main.java:65-73): a group drives n contexts from one host thread, one
  * per device (an ordinal may repeat: several partitions on one GPU).  Receivers are partitioned over the

@@ -75,6 +75,15 @@ NODE_STATS_DTYPE = np.dtype([(name, "<u8") for name, _ in NodeStats._fields_])
 assert NODE_STATS_DTYPE.itemsize == C.sizeof(NodeStats) == 64
 
 
+class ListenSchedule(C.Structure):
+    """rm_listen_schedule: one receiver's listening schedule (24 bytes)"""
+    _fields_ = [("period_us", C.c_int64), ("on_us", C.c_int64), ("phase_us", C.c_int64)]
+
+
+LISTEN_SCHEDULE_DTYPE = np.dtype([(name, "<i8") for name, _ in ListenSchedule._fields_])
+assert LISTEN_SCHEDULE_DTYPE.itemsize == C.sizeof(ListenSchedule) == 24
+
+
 class ModelParams(C.Structure):
     _fields_ = [("kind", C.c_int32), ("flags", C.c_int32),
                 ("udgm_success_ratio_tx", C.c_double), ("udgm_success_ratio_rx", C.c_double),
@@ -316,6 +325,14 @@ SIGNATURES = {
     "rm_unicast_query_at_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rm_unicast_query_at": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rm_unicast_from_result": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rm_listen_set": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "rm_listen_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "rm_listen_clear": (C.c_int, [C.c_void_p]),
+    "rm_listen_enabled": (C.c_int, [C.c_void_p]),
+    "rm_listen_missed_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "rm_listen_missed_reset": (C.c_int, [C.c_void_p]),
+    "rm_listen_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "rm_listen_at": (C.c_int, [C.c_void_p, C.c_int64]),
     "rm_det_math": (C.c_double, [C.c_int32, C.c_double]),
     "rm_link_hash": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
     "rm_evq_init": (None, [C.c_void_p]),

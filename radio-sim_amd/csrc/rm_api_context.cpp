@@ -324,6 +324,9 @@ void rm_destroy(rm_context *c)
     }
     c->ed.cnt.release(); c->ed.tx_mark.release(); c->ed.bucket_f.release(); c->ed.every_f.release(); c->ed.bucket_m.release(); c->ed.every_m.release(); c->ed.gated.release();
     c->st.table.release(); c->st.totals.release();
+    c->ls.sched.release(); c->ls.missed.release();
+    if (c->ls.h_block) (void)hipHostFree(c->ls.h_block);
+    c->ls.h_block = nullptr;
     c->uc.d_desc.release(); c->uc.d_io.release();
     for (int g = 0; g < 2; ++g) {
         if (c->uc.h_ev[g]) (void)hipEventDestroy(c->uc.h_ev[g]);

@@ -1,0 +1,212 @@
+// rm_api_listen.cpp -- C ABI: receiver listening schedules, duty-cycled radios on the device (the pass is
+// rm_listen.hip).
+//
+// The tables belong to the context, not to a medium or a tick slot: one rm_listen_schedule and one missed count per node index.
+// The evaluating calls run the pass (launch_tick, launch_batch, batch_run's fallback); everything here sets, clears and reads.
+#include "rm_host.hpp"
+
+using namespace rmh;
+
+namespace rmh {
+
+rm::ListenDev listen_dev(const rm_context *c)
+{
+    rm::ListenDev d{};
+    d.sched = c->ls.sched.p;
+    d.missed = c->ls.missed.p;
+    d.n_nodes = c->ls.n;
+    return d;
+}
+
+int listen_check(const rm_context *c, bool gathered)
+{
+    if (!listen_on(c)) return RM_OK;
+    if (gathered)
+        return fail(RM_ERR_STATE, "listening schedules are on: the gathered, rm_dist_* and rm_group_* forms do not run their pass "
+                                  "(rm_listen_clear switches them off)");
+    if (part_spatial(c) || part_count(c) != c->n)
+        return fail(RM_ERR_STATE, "listening schedules are on: a context with a receiver partition does not run their pass");
+    return RM_OK;
+}
+
+// off: every node always listens, the tables forgotten (the buffers stay for the next rm_listen_set)
+static int listen_off(rm_context *c)
+{
+    rm_context::Listen &ls = c->ls;
+    if (ls.n >= 0) RM_HIP(hipStreamSynchronize(c->stream)); // (a pass in flight still reads the tables; pointers handed out end here)
+    ls.on = false;
+    ls.n = -1;
+    ls.host.clear();
+    return RM_OK;
+}
+
+int listen_nodes_changed(rm_context *c)
+{
+    if (c->ls.n < 0 || c->ls.n == c->n) return RM_OK; // never set, or the same node count: both tables stay
+    return listen_off(c);
+}
+
+// the tables for c->n nodes: every period 0, missed 0
+static int listen_make(rm_context *c)
+{
+    rm_context::Listen &ls = c->ls;
+    if (ls.n == c->n && ls.sched.p && ls.missed.p) return RM_OK;
+    RM_HIP(hipStreamSynchronize(c->stream));
+    RM_HIP(ls.sched.ensure(size_t(std::max(c->n, 1))));
+    RM_HIP(ls.missed.ensure(size_t(std::max(c->n, 1))));
+    RM_HIP(hipMemsetAsync(ls.sched.p, 0, size_t(std::max(c->n, 1)) * sizeof(rm_listen_schedule), c->stream));
+    RM_HIP(hipMemsetAsync(ls.missed.p, 0, size_t(std::max(c->n, 1)) * sizeof(uint64_t), c->stream));
+    ls.host.assign(size_t(c->n), rm_listen_schedule{0, 0, 0});
+    ls.n = c->n;
+    return RM_OK;
+}
+
+// the pinned, host-mapped block of a list call: n records (a list update's schedules in, or a list read's counts out), then the list.
+// The stream is idle when this returns: the caller may overwrite the block
+static int listen_host_block(rm_context *c, int32_t n, char **h_recs, int32_t **h_nodes)
+{
+    rm_context::Listen &ls = c->ls;
+    if (ls.h_cap < size_t(n) || !ls.h_block) {
+        RM_HIP(hipStreamSynchronize(c->stream));
+        if (ls.h_block) RM_HIP(hipHostFree(ls.h_block));
+        ls.h_block = nullptr;
+        ls.h_cap = 0;
+        const size_t want = std::max<size_t>(size_t(n) + size_t(n) / 2, 256);
+        RM_HIP(hipHostMalloc(reinterpret_cast<void **>(&ls.h_block), pad64(want * sizeof(rm_listen_schedule)) + pad64(want * 4), hipHostMallocMapped));
+        ls.h_cap = want;
+    }
+    else
+        RM_HIP(hipStreamSynchronize(c->stream)); // (an earlier list call's launch -- a set's scatter, a read's gather -- may still read the block)
+    *h_recs = ls.h_block;
+    *h_nodes = reinterpret_cast<int32_t *>(ls.h_block + pad64(ls.h_cap * sizeof(rm_listen_schedule)));
+    return RM_OK;
+}
+
+static int listen_have(const rm_context *c)
+{
+    if (c->ls.n < 0) return fail(RM_ERR_STATE, "no listening schedules: rm_listen_set comes first");
+    return RM_OK;
+}
+
+static int listen_check_list(const int32_t *nodes, int32_t n, int32_t n_nodes)
+{
+    if (!nodes && n != n_nodes) return fail(RM_ERR_INVALID, "without a list n has to be the node count");
+    if (nodes)
+        for (int32_t k = 0; k < n; ++k)
+            if (nodes[k] < 0 || nodes[k] >= n_nodes) return fail(RM_ERR_INVALID, "node index out of range");
+    return RM_OK;
+}
+
+} // namespace rmh
+
+extern "C" {
+
+int rm_listen_set(rm_context *c, const int32_t *nodes, int32_t n, const rm_listen_schedule *sched)
+{
+    if (!c || n < 0 || (n > 0 && !sched)) return fail(RM_ERR_INVALID, "bad arguments");
+    if (c->use_graphs)
+        return fail(RM_ERR_STATE, "this context replays its ticks from captured graphs (RM_GRAPH=1): the schedules' pass is not part of them");
+    // the whole list is validated before anything changes
+    RM_TRY(listen_check_list(nodes, n, c->n));
+    for (int32_t k = 0; k < n; ++k)
+        if (!rm::host_listen_valid(sched[k]))
+            return fail(RM_ERR_INVALID, "bad rm_listen_schedule: period_us 0 with on_us = phase_us = 0, or period_us > 0 with "
+                                        "0 <= on_us <= period_us and 0 <= phase_us < period_us");
+    RM_HIP(hipSetDevice(c->device));
+    RM_TRY(ev_flush_append(c)); // (the tick before was evaluated under the old schedules: its append does not wait for the next drain)
+    ev_touch(c);
+    RM_TRY(listen_make(c));
+    rm_context::Listen &ls = c->ls;
+    if (!nodes) {
+        if (n > 0) {
+            std::memcpy(ls.host.data(), sched, size_t(n) * sizeof(rm_listen_schedule));
+            // (from the host's copy, and waited for: neither the caller's array nor a later update of the copy can race with it)
+            RM_HIP(hipMemcpyAsync(ls.sched.p, ls.host.data(), size_t(n) * sizeof(rm_listen_schedule), hipMemcpyHostToDevice, c->stream));
+            RM_HIP(hipStreamSynchronize(c->stream));
+        }
+    } else if (n > 0) {
+        // a list: applied to the host's copy in order (the last entry of a node wins), then one small scatter launch that reads
+        // every entry with its node's final record from the host-mapped block -- duplicates write equal values
+        for (int32_t k = 0; k < n; ++k) ls.host[size_t(nodes[k])] = sched[k];
+        char *h_recs;
+        int32_t *h_nodes;
+        RM_TRY(listen_host_block(c, n, &h_recs, &h_nodes));
+        rm_listen_schedule *h_sched = reinterpret_cast<rm_listen_schedule *>(h_recs);
+        for (int32_t k = 0; k < n; ++k) h_sched[k] = ls.host[size_t(nodes[k])];
+        std::memcpy(h_nodes, nodes, size_t(n) * 4);
+        RM_HIP(rm::launch_listen_scatter(c->stream, ls.sched.p, ls.n, h_nodes, n, h_sched));
+    }
+    ls.on = true;
+    return RM_OK;
+}
+
+int rm_listen_get(rm_context *c, const int32_t *nodes, int32_t n, rm_listen_schedule *out)
+{
+    if (!c || n < 0 || (n > 0 && !out)) return fail(RM_ERR_INVALID, "bad arguments");
+    RM_TRY(listen_have(c));
+    RM_TRY(listen_check_list(nodes, n, c->ls.n));
+    for (int32_t k = 0; k < n; ++k) out[k] = c->ls.host[size_t(nodes ? nodes[k] : k)];
+    return RM_OK;
+}
+
+int rm_listen_clear(rm_context *c)
+{
+    if (!c) return fail(RM_ERR_INVALID, "ctx is NULL");
+    RM_HIP(hipSetDevice(c->device));
+    if (c->ls.n >= 0) {
+        RM_TRY(ev_flush_append(c));
+        ev_touch(c);
+    }
+    return listen_off(c);
+}
+
+int rm_listen_enabled(const rm_context *c) { return (c && c->ls.on) ? 1 : 0; }
+
+int rm_listen_missed_read(rm_context *c, const int32_t *nodes, int32_t n, uint64_t *out)
+{
+    if (!c || n < 0 || (n > 0 && !out)) return fail(RM_ERR_INVALID, "bad arguments");
+    RM_TRY(listen_have(c));
+    RM_TRY(listen_check_list(nodes, n, c->ls.n));
+    if (n == 0) return RM_OK;
+    RM_HIP(hipSetDevice(c->device));
+    if (!nodes) { // the whole table in node order: one copy on the stream, one synchronisation
+        RM_HIP(hipMemcpyAsync(out, c->ls.missed.p, size_t(n) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        RM_HIP(hipStreamSynchronize(c->stream));
+        return RM_OK;
+    }
+    // a list: one small gather launch reads it from the host-mapped block and writes the counts there
+    char *h_recs;
+    int32_t *h_nodes;
+    RM_TRY(listen_host_block(c, n, &h_recs, &h_nodes));
+    std::memcpy(h_nodes, nodes, size_t(n) * 4);
+    RM_HIP(rm::launch_listen_gather(c->stream, listen_dev(c), h_nodes, n, reinterpret_cast<uint64_t *>(h_recs)));
+    RM_HIP(hipStreamSynchronize(c->stream));
+    std::memcpy(out, h_recs, size_t(n) * sizeof(uint64_t));
+    return RM_OK;
+}
+
+int rm_listen_missed_reset(rm_context *c)
+{
+    if (!c) return fail(RM_ERR_INVALID, "ctx is NULL");
+    RM_TRY(listen_have(c));
+    RM_HIP(hipSetDevice(c->device));
+    RM_HIP(hipMemsetAsync(c->ls.missed.p, 0, size_t(std::max(c->ls.n, 1)) * sizeof(uint64_t), c->stream));
+    return RM_OK;
+}
+
+int rm_listen_device(rm_context *c, const rm_listen_schedule **dev_sched, const uint64_t **dev_missed)
+{
+    if (!c) return fail(RM_ERR_INVALID, "ctx is NULL");
+    RM_TRY(listen_have(c));
+    if (dev_sched) *dev_sched = c->ls.sched.p;
+    if (dev_missed) *dev_missed = c->ls.missed.p;
+    return RM_OK;
+}
+
+int rm_listen_at(const rm_listen_schedule *s, int64_t t_us)
+{
+    if (!s || !rm::host_listen_valid(*s)) return RM_ERR_INVALID;
+    return rm::host_listen_at(*s, t_us) ? 1 : 0;
+}
+
+} // extern "C"

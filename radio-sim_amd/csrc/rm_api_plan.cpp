@@ -112,7 +112,7 @@ int prepare_tick(rm_context *c, TickSlot &ts, TickPlan &plan, bool want_wg, cons
     ev_touch(c);
     ts.have_result = false;
     ts.compact_pending = false;
-    ts.dense_pending = ts.dense_result = ts.dense_layout_pending = false;
+    ts.dense_pending = ts.dense_result = ts.dense_layout_pending = ts.dense_listen = false;
     ts.last_n_new = n_new;
     RM_TRY(prepare_nodes(c));
 
@@ -429,6 +429,14 @@ int launch_tick(rm_context *c, TickSlot &ts, const TickPlan &plan, bool em_pass)
         ts.last_model = m;
         ts.last_cfg = cfg;
         ts.have_result = true;
+        if (em_pass && listen_on(c)) {
+            // the listening schedules (E13) over a dense tick: its records from the lane masks, then the pass over them.  The masks
+            // carry one verdict per packet and cannot express the pass: rm_result_dense refuses this tick
+            RM_TRY(stage(RM_STAGE_REORDER));
+            RM_TRY(materialize(c, ts));
+            RM_HIP(rm::launch_listen(s, listen_dev(c), ts.last));
+            ts.dense_listen = true;
+        }
         if (em_pass && stats_on(c)) {
             // the traffic counters (E11) over a dense tick: its records from the lane masks, then the pass (rm_result_dense keeps
             // answering: the masks stay where they are)
@@ -564,6 +572,14 @@ int launch_tick(rm_context *c, TickSlot &ts, const TickPlan &plan, bool em_pass)
         RM_TRY(materialize(c, ts));
         RM_TRY(stage(RM_STAGE_SINR));
         RM_HIP(rm::launch_errmodel(s, em_dev(c), ts.last));
+    }
+    if (em_pass && listen_on(c)) {
+        if (ts.draws_pending) return fail(RM_ERR_STATE, "internal: the listening schedules' pass cannot run before the ranks' draws are finished");
+        // the listening schedules (E13), behind the frame error model's pass and ahead of the traffic counters': the tick's compact
+        // arrays at once, then the pass over them -- every reader (pack launches, the reception stage, the copies) reads out_verdict
+        RM_TRY(stage(RM_STAGE_REORDER));
+        RM_TRY(materialize(c, ts));
+        RM_HIP(rm::launch_listen(s, listen_dev(c), ts.last));
     }
     if (em_pass && stats_on(c)) {
         if (ts.draws_pending) return fail(RM_ERR_STATE, "internal: the traffic counters' pass cannot run before the ranks' draws are finished");

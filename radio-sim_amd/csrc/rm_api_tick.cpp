@@ -181,6 +181,7 @@ int tick_run_host(rm_context *c)
     if (!c) return fail(RM_ERR_INVALID, "ctx is NULL");
     if (!c->in_tick) return fail(RM_ERR_STATE, "rm_tick_flush without rm_tick_begin");
     RM_TRY(stats_check(c, false)); // (the traffic counters refuse partitions: nothing launched, the tick stays open)
+    RM_TRY(listen_check(c, false)); // (the listening schedules: likewise)
     RM_HIP(hipSetDevice(c->device));
     c->in_tick = false;
     // SINR: the frames of earlier ticks stay on the device (the window air_tick_device keeps, shared with the ticks whose
@@ -376,10 +377,12 @@ int rm_transmit(rm_context *c, int32_t src, int64_t start_us, int64_t hex_length
     if (src < 0 || src >= c->n) return fail(RM_ERR_INVALID, "could not find source node");
     if (hex_length < 0) return fail(RM_ERR_INVALID, "negative packet length");
     RM_TRY(stats_check(c, false)); // (the traffic counters refuse partitions before anything is launched)
+    RM_TRY(listen_check(c, false)); // (the listening schedules: likewise)
     ev_touch(c);
     const bool draws_need_exchange = maybe_draws(c) && part_count(c) != c->n;
     // (with the traffic counters on, the one-launch shortcut below is off: its links never become a slot's result)
-    if (is_sinr(c) || draws_need_exchange || stats_on(c)) {
+    // (the same with listening schedules on: their pass runs over a slot's result)
+    if (is_sinr(c) || draws_need_exchange || stats_on(c) || listen_on(c)) {
         // the on-air list of earlier calls / the per-rank draw exchange: the general tick path
         RM_TRY(rm_tick_begin(c, start_us, start_us));
         RM_TRY(rm_enqueue_tx(c, src, start_us, rm_air_time_us(hex_length), txpower, channel));
@@ -500,6 +503,7 @@ int rm_tick_run_device(rm_context *c, int64_t t_begin_us, int64_t t_end_us, cons
         return fail(RM_ERR_STATE, "the SINR medium keeps frames on the air: records in device memory go through "
                                   "rm_tick_run_records_device, which is told how long they stay (latest_end_us)");
     RM_TRY(stats_check(c, false)); // (the traffic counters refuse partitions before anything is launched)
+    RM_TRY(listen_check(c, false)); // (the listening schedules: likewise)
     RM_HIP(hipSetDevice(c->device));
     c->t_begin = t_begin_us;
     c->t_end = t_end_us;
@@ -514,6 +518,7 @@ int rm_tick_run_sources_device(rm_context *c, int64_t t_begin_us, int64_t t_end_
 {
     if (!c || n < 0 || (n > 0 && !dev_src) || air_us < 0) return fail(RM_ERR_INVALID, "bad arguments");
     RM_TRY(stats_check(c, false)); // (the traffic counters refuse partitions before anything is launched)
+    RM_TRY(listen_check(c, false)); // (the listening schedules: likewise)
     RM_HIP(hipSetDevice(c->device));
     c->t_begin = t_begin_us;
     c->t_end = t_end_us;
@@ -605,6 +610,7 @@ int air_tick_device(rm_context *c, int64_t t_begin_us, const int32_t *dev_src, c
 {
     RM_TRY(em_check(c, false)); // (the frame error model refuses partitions before the window moves)
     RM_TRY(stats_check(c, false)); // (the traffic counters: likewise)
+    RM_TRY(listen_check(c, false)); // (the listening schedules: likewise)
     RM_TRY(air_window_expire(c, t_begin_us));
     RM_TRY(air_window_reserve(c, size_t(n)));
     const size_t live = c->air_tail - c->air_head;
@@ -668,6 +674,8 @@ int rm_result_dense(rm_context *c, rm_dense_result *out)
 {
     if (!c || !out) return fail(RM_ERR_INVALID, "NULL argument");
     if (!c->have_result || !c->dense_result) return fail(RM_ERR_STATE, "the last tick did not take the dense form (rm_result_device has its records)");
+    if (c->dense_listen || listen_on(c))
+        return fail(RM_ERR_STATE, "listening schedules are on: one verdict per packet cannot express their pass (rm_result_device has the records)");
     RM_HIP(hipSetDevice(c->device));
     RM_TRY(dense_layout(c, *c)); // (pkt_offset and count: laid out when the first reader asks)
     out->cell_mask = c->d_dense_mask.p;

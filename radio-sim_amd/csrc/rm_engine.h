@@ -529,6 +529,14 @@ struct StatsDev {
     int n_nodes;
 };
 
+// Receiver listening schedules (rm_listen.hip): the tables the pass over a finished result reads
+// and adds to
+struct ListenDev {
+    const rm_listen_schedule *sched; // [n_nodes], by node index
+    uint64_t *missed;                // [n_nodes]
+    int n_nodes;
+};
+
 // The unicast outcome query (rm_unicast.hip): what the query reads of one finished result slot --
 // the compact packet-major arrays every result reader gets, the records of the tick's new frames, the slot's counters
 struct UcSlot {
@@ -881,6 +889,15 @@ hipError_t launch_errmodel_batch(hipStream_t s, const EmDev &em, int n, const Ti
 hipError_t launch_stats(hipStream_t s, const StatsDev &sd, const TickDev &t);
 hipError_t launch_stats_batch(hipStream_t s, const StatsDev &sd, int n, const TickDev *dev_ticks);
 hipError_t launch_stats_gather(hipStream_t s, const StatsDev &sd, const int32_t *nodes, int n, rm_node_stats *out, rm_stats_totals *totals_out);
+
+// (rm_listen.hip) the listening schedules' pass over one finished result slot / over the n slots of a batch in one launch; the
+// scatter of a list update from a host-mapped block (entry k: sched[k] to node nodes[k]) and the gather of listed nodes' missed counts
+hipError_t launch_listen(hipStream_t s, const ListenDev &ld, const TickDev &t);
+hipError_t launch_listen_batch(hipStream_t s, const ListenDev &ld, int n, const TickDev *dev_ticks);
+hipError_t launch_listen_scatter(hipStream_t s, rm_listen_schedule *table, int n_nodes, const int32_t *nodes, int n, const rm_listen_schedule *sched);
+hipError_t launch_listen_gather(hipStream_t s, const ListenDev &ld, const int32_t *nodes, int n, uint64_t *out);
+bool host_listen_valid(const rm_listen_schedule &s);
+bool host_listen_at(const rm_listen_schedule &s, int64_t t_us);
 
 // (rm_unicast.hip) the unicast outcome query, one launch: a lane per entry.  n_slots result slots described by dev_slots -- or, with
 // dev_slots == nullptr, the one slot `lone`.  Slots form (dev_prefix: [n_slots + 1] exclusive prefix of the entries per slot; nullptr

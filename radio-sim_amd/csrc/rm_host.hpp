@@ -131,6 +131,7 @@ struct TickSlot {
     // the dense tick (rm_dense.hip) leaves the heard links as lane masks per (frame, 1024 nodes) cell: the records are written
     // when somebody asks for them (materialize); rm_result_dense hands out the masks themselves
     bool dense_pending = false, dense_result = false;
+    bool dense_listen = false; // the listening schedules' pass ran over this dense tick's records: the masks do not carry its verdicts
     bool dense_layout_pending = false; // ... and so are the cells' offsets and the totals (dense_layout)
     int dense_rx_first = 0, dense_chunks = 0;
     rm::ModelDev last_model{};
@@ -156,6 +157,18 @@ struct rm_context : TickSlot {
         char *h_block = nullptr;
         size_t h_cap = 0; // nodes the block has room for
     } st;
+    // receiver listening schedules (E13; rm_api_listen.cpp, rm_listen.hip): one schedule and one missed count per node index, the
+    // host's copy of the schedules (rm_listen_get reads it; a list update is applied to it in order), and the pinned, host-mapped
+    // block a list update or a list read is staged through
+    struct Listen {
+        bool on = false;
+        int32_t n = -1; // the node count the tables were made for; -1: never set (or cleared by another node count)
+        std::vector<rm_listen_schedule> host;
+        DevBuf<rm_listen_schedule> sched;
+        DevBuf<uint64_t> missed;
+        char *h_block = nullptr;
+        size_t h_cap = 0; // list entries the block has room for
+    } ls;
     // the unicast outcome query (E12; rm_api_unicast.cpp, rm_unicast.hip): what the last evaluating call left -- how many result slots,
     // and whether it was a gathered / rm_dist_* / rm_group_* form -- the slots' descriptors in device memory (rm::UcSlot per slot,
     // then the prefix of a slots-form query), their pinned staging (two blocks, each rewritten only after its copy has completed), and
@@ -585,7 +598,8 @@ int prepare_tick(rm_context *c, TickSlot &ts, TickPlan &plan, bool want_wg, cons
                  int first_new, const int32_t *src_list = nullptr, int64_t src_start_us = 0, int64_t src_air_us = 0,
                  int air_mode = kAirNone, uint32_t air_oldest = 0, const rm::PlanKnobs *knobs_in = nullptr);
 // em_pass: with the frame error model on, the tick ends with its compact arrays and the model's pass over them (a batch that
-// launches its ticks one by one runs ONE pass over all of them afterwards instead); the same holds for the traffic counters' pass
+// launches its ticks one by one runs ONE pass over all of them afterwards instead); the same holds for the listening schedules'
+// and the traffic counters' passes
 int launch_tick(rm_context *c, TickSlot &ts, const TickPlan &plan, bool em_pass = true);
 int materialize(rm_context *c, TickSlot &ts);
 int dense_layout(rm_context *c, TickSlot &ts); // (the cells' offsets and totals of a dense tick that ended with its cells)
@@ -676,6 +690,14 @@ rm::StatsDev stats_dev(const rm_context *c);
 int stats_check(const rm_context *c, bool gathered);
 // rm_nodes_upload: another node count resizes the table and zeroes it
 int stats_nodes_changed(rm_context *c);
+
+// ---- rm_api_listen.cpp: receiver listening schedules (E13)
+inline bool listen_on(const rm_context *c) { return c->ls.on; }
+rm::ListenDev listen_dev(const rm_context *c);
+// what an evaluating call refuses while schedules are on, before anything is launched (the shape of em_check)
+int listen_check(const rm_context *c, bool gathered);
+// rm_nodes_upload: another node count clears the feature
+int listen_nodes_changed(rm_context *c);
 
 // ---- rm_api_unicast.cpp: the unicast outcome query (E12)
 // an evaluating call has left its results in `slots` result slots (gathered: a gathered / rm_dist_* / rm_group_* form)

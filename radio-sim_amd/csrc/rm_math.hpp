@@ -158,6 +158,23 @@ RM_HD double em_draw(uint64_t seed, int32_t src, int64_t start_us, int32_t dst)
     return (double(h >> 12) + 0.5) * 0x1.0p-52;
 }
 
+// the receiver listening schedule: what a record may hold, and the listening rule -- the text the pass
+// (rm_listen.hip) and rm_listen_at are both built from
+RM_HD bool listen_valid(const rm_listen_schedule &s)
+{
+    if (s.period_us == 0) return s.on_us == 0 && s.phase_us == 0;
+    return s.period_us > 0 && s.on_us >= 0 && s.on_us <= s.period_us && s.phase_us >= 0 && s.phase_us < s.period_us;
+}
+
+RM_HD bool listen_at(const rm_listen_schedule &s, int64_t t_us)
+{
+    if (s.period_us == 0) return true;
+    const int64_t d = int64_t(uint64_t(t_us) - uint64_t(s.phase_us)); // (wraps)
+    int64_t r = d % s.period_us;
+    if (r < 0) r += s.period_us;
+    return r < s.on_us;
+}
+
 // Position.getDistance, Position.java:56-64: this = transmitter, p2 = receiver;
 // (dx*dx + dy*dy) + dz*dz, then a correctly rounded square root.
 RM_HD double ref_distance(double ax, double ay, double az, double bx, double by, double bz)

@@ -259,6 +259,71 @@ class Engine:
         check(_lib.lib().rm_unicast_from_result(C.byref(r), _ptr(src), n_nodes, want.ctypes.data, C.byref(out)))
         return arrs
 
+    # -- receiver listening schedules: duty-cycled radios on the device
+    @staticmethod
+    def _listen_table(sched):
+        """schedules as a contiguous LISTEN_SCHEDULE_DTYPE array: a structured array, or rows of (period_us, on_us, phase_us)"""
+        a = np.asarray(sched)
+        if a.dtype != _lib.LISTEN_SCHEDULE_DTYPE:
+            rows = np.ascontiguousarray(a, dtype=np.int64).reshape(-1, 3)
+            a = rows.view(_lib.LISTEN_SCHEDULE_DTYPE).reshape(-1)
+        return np.ascontiguousarray(a.reshape(-1))
+
+    def listen_set(self, sched, nodes=None):
+        """rm_listen_set: sched for all nodes in node order, or for the listed nodes in list order (the last entry of a node wins);
+        switches the feature on"""
+        tbl = self._listen_table(sched)
+        if nodes is None:
+            check(self._L.rm_listen_set(self._h, None, tbl.shape[0], tbl.ctypes.data))
+        else:
+            idx = np.ascontiguousarray(nodes, dtype=np.int32)
+            if idx.shape[0] != tbl.shape[0]:
+                raise ValueError("one schedule per listed node")
+            check(self._L.rm_listen_set(self._h, idx.ctypes.data, idx.shape[0], tbl.ctypes.data))
+
+    def listen_get(self, nodes=None):
+        """rm_listen_get: structured array of LISTEN_SCHEDULE_DTYPE (the listed nodes in list order, or all in node order)"""
+        if nodes is None:
+            out = np.zeros(max(int(self._L.rm_node_count(self._h)), 0), dtype=_lib.LISTEN_SCHEDULE_DTYPE)
+            check(self._L.rm_listen_get(self._h, None, out.shape[0], out.ctypes.data))
+        else:
+            idx = np.ascontiguousarray(nodes, dtype=np.int32)
+            out = np.zeros(idx.shape[0], dtype=_lib.LISTEN_SCHEDULE_DTYPE)
+            check(self._L.rm_listen_get(self._h, idx.ctypes.data, idx.shape[0], out.ctypes.data))
+        return out
+
+    def listen_clear(self):
+        check(self._L.rm_listen_clear(self._h))
+
+    def listen_enabled(self):
+        return bool(self._L.rm_listen_enabled(self._h))
+
+    def listen_missed(self, nodes=None):
+        """rm_listen_missed_read: uint64 per node (the listed nodes in list order, or all in node order)"""
+        if nodes is None:
+            out = np.zeros(max(int(self._L.rm_node_count(self._h)), 0), dtype=np.uint64)
+            check(self._L.rm_listen_missed_read(self._h, None, out.shape[0], out.ctypes.data))
+        else:
+            idx = np.ascontiguousarray(nodes, dtype=np.int32)
+            out = np.zeros(idx.shape[0], dtype=np.uint64)
+            check(self._L.rm_listen_missed_read(self._h, idx.ctypes.data, idx.shape[0], out.ctypes.data))
+        return out
+
+    def listen_missed_reset(self):
+        check(self._L.rm_listen_missed_reset(self._h))
+
+    def listen_device(self):
+        """rm_listen_device: (device pointer of the schedules [n_nodes] of 24-byte records, device pointer of missed [n_nodes] uint64)"""
+        sch, mis = C.c_void_p(), C.c_void_p()
+        check(self._L.rm_listen_device(self._h, C.byref(sch), C.byref(mis)))
+        return sch.value, mis.value
+
+    @staticmethod
+    def listen_at(sched, t):
+        """rm_listen_at (pure host): 1 / 0, or RM_ERR_INVALID for a bad record; sched = (period_us, on_us, phase_us)"""
+        s = _lib.ListenSchedule(*[int(v) for v in sched])
+        return int(_lib.lib().rm_listen_at(C.byref(s), int(t)))
+
     # -- java.util.Random
     def seed(self, seed):
         check(self._L.rm_seed(self._h, seed))

@@ -40,6 +40,7 @@
 #include <memory>
 #include <cstdio>
 #include <stdexcept>
+#include <map>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -604,6 +605,45 @@ public:
         }
         return out;
     }
+    // Receiver listening schedules (extension E13): a duty-cycled radio that sleeps at a frame's first microsecond does not get the
+    // frame -- with a schedule set, every evaluating call of the medium ends with one more pass over its verdicts, so the reception
+    // events of transmit(), the tick mode, transmitIfClear() and transmitCsmaBatch() honour it.  period_us 0 (with on_us = phase_us
+    // = 0): the node always listens.  The schedules survive apply(); false and lastError on a refusal.
+    bool setListenSchedule(const Node &node, int64_t period_us, int64_t on_us, int64_t phase_us)
+    {
+        if (!syncNodes()) return false; // the device mirrors the node table first: the tables have its size
+        const int32_t i = node.index;
+        const rm_listen_schedule s = {period_us, on_us, phase_us};
+        if (!restoreListenSchedules()) return false; // (a node table of another size has cleared the engine's tables: all of them again)
+        if (rm_listen_set(ctx_, &i, 1, &s) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        listen_[i] = s;
+        return true;
+    }
+    bool clearListenSchedules()
+    {
+        listen_.clear();
+        if (rm_listen_clear(ctx_) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        return true;
+    }
+    bool getListenEnabled() const { return rm_listen_enabled(ctx_) != 0; }
+    // frames everything else had delivered to the node and that sleep alone lost (0 and lastError on a refusal)
+    uint64_t getListenMissed(const Node &node)
+    {
+        uint64_t out = 0;
+        const int32_t i = node.index;
+        if (!syncNodes()) return 0;
+        if (rm_listen_missed_read(ctx_, &i, 1, &out) != RM_OK) {
+            lastError = rm_last_error();
+            return 0;
+        }
+        return out;
+    }
     // Did a frame reach the node it was addressed to (extension E12)?  One entry per packet of the LAST evaluated tick -- the tick
     // mode's flush, or transmitIfClear() -- in packet order: destinations[k] is packet k's intended receiver (nullptr: not asked).
     // status is RM_UC_*; link the index of the heard link in the tick's result (-1 without one); rssi and sinr as the result has
@@ -645,8 +685,30 @@ protected:
             statistics_ = false;
             lastError = rm_last_error();
         }
+        // (nor are the listening schedules: the engine keeps them over a change of the medium)
+        restoreListenSchedules();
+    }
+    // the schedules the medium set, set again where the engine has dropped them (a node table of another size clears its tables), as
+    // far as their nodes still exist; false and lastError on a refusal
+    bool restoreListenSchedules()
+    {
+        if (listen_.empty() || rm_listen_enabled(ctx_)) return true;
+        std::vector<int32_t> idx;
+        std::vector<rm_listen_schedule> recs;
+        const int32_t n = rm_node_count(ctx_);
+        for (const auto &kv : listen_)
+            if (kv.first < n) {
+                idx.push_back(kv.first);
+                recs.push_back(kv.second);
+            }
+        if (!idx.empty() && rm_listen_set(ctx_, idx.data(), int32_t(idx.size()), recs.data()) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        return true;
     }
     bool statistics_ = false; // what setStatistics set last, kept across apply()
+    std::map<int32_t, rm_listen_schedule> listen_; // what setListenSchedule set, by node index, kept across apply()
     rm_context *ctx_ = nullptr;
     bool syncNodes() { return !simulator || sync(simulator, simulator->getNodes()); } // the device mirrors the node table first
 
