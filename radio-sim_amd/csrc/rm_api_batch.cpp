@@ -109,7 +109,7 @@ static int plan_nbr_cache(rm_context *c, rm::TickDev *ticks, const TickPlan *pla
     RM_HIP(nc.hit.ensure(size_t(n) * per));
     RM_HIP(nc.fill.ensure(size_t(n) * per));
     RM_HIP(nc.cur.ensure(size_t(n) * per));
-    RM_HIP(hipMemsetAsync(nc.tick_cnt.p, 0, size_t(n) * 4 * sizeof(uint32_t), s));
+    // (tick_cnt: zeroed by the descriptor kernels, k_store_ticks / k_fetch_ticks)
     nc.batches[form]++;
     for (int b = 0; b < n; ++b) {
         rm::NbrCacheDev &d = ticks[b].nc;

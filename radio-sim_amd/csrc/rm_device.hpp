@@ -534,19 +534,85 @@ RM_D uint32_t wave_inclusive_scan(uint32_t v, int lane)
     return v;
 }
 
-// the lanes' runs laid end to end (inc: wave_inclusive_scan of their lengths): the lane whose run holds entry j -- the first one
-// whose running count is above j (63 for a j at or beyond the total)
-RM_D int wave_run_of(const uint32_t inc, const uint32_t j)
+// ---- a wave's 64 runs copied with full lanes (the heard form's two record copies: k_reorder_served_batch, k_nc_fill_batch)
+// The index rule, host-callable (tests/cpp/wave_runs_san_test.cpp holds it to a plain expansion of the runs): the entries
+// j = 0 .. total - 1 of the runs laid end to end are taken a SPAN of kCopyRounds * 64 at a time, entry j0 + 64 u + lane by
+// `lane` in round u -- every entry exactly once.
+constexpr int kCopyRounds = 4;
+constexpr uint32_t kCopySpan = 64u * kCopyRounds;
+// the run that holds entry j: the first one whose running count is above j (63 for a j at or beyond the total) -- wave_run_of's
+// bisection over any way of reading run i's running count (the host: an array; the wave: a lane's register)
+template <class IncAt>
+RM_HD int run_of(const IncAt inc_at, const uint32_t j)
 {
     int lo = 0, hi = 63;
 #pragma unroll
     for (int step = 0; step < 6; ++step) {
         const int mid = (lo + hi) >> 1;
-        const bool above = uint32_t(__shfl(int(inc), mid)) > j;
+        const bool above = inc_at(mid) > j;
         hi = above ? mid : hi;
         lo = above ? lo : mid + 1;
     }
-    return min(lo, 63);
+    return lo < 63 ? lo : 63;
+}
+// entry j's place in its run (the run's running count and length)
+RM_HD uint32_t run_place(const uint32_t run_inc, const uint32_t run_cnt, const uint32_t j) { return j - (run_inc - run_cnt); }
+// the lanes' runs (inc: wave_inclusive_scan of their lengths): the lane whose run holds entry j
+RM_D int wave_run_of(const uint32_t inc, const uint32_t j)
+{
+    return run_of([inc](const int i) { return uint32_t(__shfl(int(inc), i)); }, j);
+}
+
+// The copy itself.  Lane f's run: cnt records (inc: wave_inclusive_scan of cnt, total: the wave's sum), at list0 in the arena's
+// columns and at rec0 in the tick's ordered records.  TO_ARENA: records -> arena (a claimed list is filled), else arena -> records
+// (a hit frame is served; out_pkt is written as well: frame e0 + f).  kCopyRounds rounds of 64 entries at a time, all their loads
+// requested before the first store (the arena and the records may alias as far as the compiler knows, so it would wait for every
+// round's loads on its own).  Every access is guarded: both ends are memory that all ticks of the batch share.
+template <bool TO_ARENA>
+RM_D void wave_copy_lists(const TickDev &t, const int lane, const int e0, const uint32_t cnt, const uint32_t inc, const uint32_t total,
+                          const uint32_t list0, const uint32_t rec0)
+{
+    for (uint32_t j0 = 0; j0 < total; j0 += kCopySpan) { // wave-uniform
+        uint32_t a[kCopyRounds], o[kCopyRounds];
+        bool ok[kCopyRounds];
+        int pkt[kCopyRounds], v_dst[kCopyRounds];
+        double v_rssi[kCopyRounds];
+        uint8_t v_verdict[kCopyRounds];
+#pragma unroll
+        for (int u = 0; u < kCopyRounds; ++u) {
+            const uint32_t j = j0 + uint32_t(u * 64 + lane);
+            const int f = wave_run_of(inc, j);
+            const uint32_t f_inc = uint32_t(__shfl(int(inc), f)), f_cnt = uint32_t(__shfl(int(cnt), f));
+            const uint32_t k = run_place(f_inc, f_cnt, j);
+            a[u] = uint32_t(__shfl(int(list0), f)) + k;
+            o[u] = uint32_t(__shfl(int(rec0), f)) + k;
+            pkt[u] = e0 + f;
+            ok[u] = j < total && o[u] < t.cap && a[u] < t.nc.arena_len;
+            if (TO_ARENA) {
+                v_dst[u] = ok[u] ? t.out_dst[o[u]] : 0;
+                v_rssi[u] = ok[u] ? t.out_rssi[o[u]] : 0.0;
+                v_verdict[u] = ok[u] ? t.out_verdict[o[u]] : uint8_t(0);
+            } else {
+                v_dst[u] = ok[u] ? t.nc.arena[a[u]] : 0;
+                v_rssi[u] = ok[u] ? t.nc.arena_rssi[a[u]] : 0.0;
+                v_verdict[u] = ok[u] ? t.nc.arena_verdict[a[u]] : uint8_t(0);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kCopyRounds; ++u) {
+            if (!ok[u]) continue;
+            if (TO_ARENA) {
+                t.nc.arena[a[u]] = v_dst[u];
+                t.nc.arena_rssi[a[u]] = v_rssi[u];
+                t.nc.arena_verdict[a[u]] = v_verdict[u];
+            } else {
+                t.out_pkt[o[u]] = pkt[u];
+                t.out_dst[o[u]] = v_dst[u];
+                t.out_rssi[o[u]] = v_rssi[u];
+                t.out_verdict[o[u]] = v_verdict[u];
+            }
+        }
+    }
 }
 
 // exclusive scan of one value per thread over a 1024-thread block; returns the block total in `total`

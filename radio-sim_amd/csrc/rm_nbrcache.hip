@@ -26,10 +26,14 @@ __global__ void __launch_bounds__(256) k_nc_claim_batch(const TickDev *__restric
         atomicAdd(&t.nc.ctr[1], (unsigned long long)t.nc.tick_cnt[2]);
         atomicAdd(&t.nc.ctr[2], (unsigned long long)t.nc.tick_cnt[0]);
     }
+    const bool heard = t.nc.arena_rssi != nullptr;
+    // heard form: every frame of the tick was served -- each has a hit, none can claim (block-uniform).  Nothing is written:
+    // tick_cnt[1] stays 0, so k_nc_fill_batch returns before it reads fill[], which is NOT cleared between launch sequences --
+    // a tick that goes on below therefore writes fill[e] for every one of its frames.
+    if (heard && uniform_u(t.nc.tick_cnt[2]) == uint32_t(n_eval)) return;
     const int lane = threadIdx.x & 63;
     // (a tick whose shards overflowed has gaps where runs were dropped: none of its frames leaves a list; in the heard form
     // neither does a tick whose heard links exceed the link capacity: its ordered records stop at `cap`)
-    const bool heard = t.nc.arena_rssi != nullptr;
     const bool dropped = t.stage_count[1] != 0u || (heard && t.out_count[1] != 0u);
     bool mine = false;
     int s = -1;
@@ -63,50 +67,40 @@ __global__ void __launch_bounds__(256) k_nc_claim_batch(const TickDev *__restric
     }
     if (e >= n_eval) return;
     t.nc.fill[e] = fill;
-    t.nc.cur[e] = 0u;
+    if (!heard) t.nc.cur[e] = 0u; // (candidates copied so far: the heard form's fill does not count)
     const uint64_t fm = ballot64(fill >= 0);
     if (fm && int(threadIdx.x & 63) == __ffsll((long long)fm) - 1) atomicAdd(&t.nc.tick_cnt[1], uint32_t(__popcll(fm)));
 }
 
 // the entries of the lists claimed in this launch sequence (nothing to do for a tick that claimed none)
-// Heard form: one wave per 64 frames.  A claimed frame's records are contiguous and already in node order at its place in the
-// ordered arrays; all of the wave's lists are copied to the arena's columns with full lanes (no atomics).
+// Heard form: 64 frames per wave.  A claimed frame's records are contiguous and already in node order at its place in the
+// ordered arrays; all of the wave's lists are copied to the arena's columns with full lanes (no atomics; wave_copy_lists,
+// rm_device.hpp).
 // Candidates form: one workgroup per shard: the shard's entries (the sweep's: the cached ones are appended afterwards) whose
 // frame fills a list go there, one atomic per run of entries of one frame.
+// Measured and dropped: 2, 4 or 8 waves (gridDim.y) sharing the 64 frames' records, each taking every P-th span, as for
+// k_reorder_served_batch (rm_reorder.hip; this kernel's total over a run, ms, two runs each of the default run | --warmup 24):
+// 1 wave 0.32 0.35 | 0.35 0.36   2 waves 0.28 0.28 | 0.42 0.42   4 waves 0.32 0.36 | 0.37 0.37   8 waves 0.43 0.47 | 0.56 0.51 (one
+// round per step, as before this loop: 0.43 0.46 | 0.49 0.48).  2 gain on one run what they lose on the other, 4 gain nothing.
 __global__ void __launch_bounds__(256) k_nc_fill_batch(const TickDev *__restrict__ ticks)
 {
     const TickDev &t = ticks[blockIdx.z];
     if (t.nc.state == nullptr || uniform_u(t.nc.tick_cnt[1]) == 0u) return;
-    if (t.nc.arena_rssi != nullptr) { // (block-uniform; grid: frames / kBlock in x)
+    if (t.nc.arena_rssi != nullptr) { // (block-uniform; grid: frames / kBlock in x, 1 in y)
         const int lane = threadIdx.x & 63;
         const int e0 = int(blockIdx.x) * kBlock + wave_index() * 64;
         const int e = e0 + lane;
         int32_t fo = -1;
         if (e < t.n_active - t.first_eval) fo = t.nc.fill[e];
-        uint32_t cnt = 0, src = 0;
-        if (fo >= 0) { // (claimed: the tick was not dropped, so every record of the frame lies below `cap`)
-            cnt = t.cursor[e - t.cnt_base];
-            src = t.slot_off[e - t.cnt_base];
-        }
+        // (claimed: the tick was not dropped, so every record of the frame lies below `cap`)
+        const uint32_t cnt = fo >= 0 ? t.cursor[e - t.cnt_base] : 0u;
         const uint32_t inc = wave_inclusive_scan(cnt, lane);
         const uint32_t total = uniform_u(uint32_t(__shfl(int(inc), 63)));
-        for (uint32_t j0 = 0; j0 < total; j0 += 64u) { // wave-uniform
-            const uint32_t j = j0 + uint32_t(lane);
-            const int f = wave_run_of(inc, j);
-            const uint32_t f_inc = uint32_t(__shfl(int(inc), f)), f_cnt = uint32_t(__shfl(int(cnt), f)), f_src = uint32_t(__shfl(int(src), f));
-            const uint32_t f_dst = uint32_t(__shfl(fo, f));
-            if (j < total) {
-                const uint32_t k = j - (f_inc - f_cnt);
-                const uint32_t a = f_dst + k, o = f_src + k;
-                // (the claim has made sure of both -- the list ends inside the arena, the tick was not dropped; like the
-                // candidates form's fill below, the store is guarded all the same: it is a write into memory shared by every tick)
-                if (a < t.nc.arena_len && o < t.cap) {
-                    t.nc.arena[a] = t.out_dst[o];
-                    t.nc.arena_rssi[a] = t.out_rssi[o];
-                    t.nc.arena_verdict[a] = t.out_verdict[o];
-                }
-            }
-        }
+        if (total == 0u) return; // (wave-uniform)
+        const uint32_t src = fo >= 0 ? t.slot_off[e - t.cnt_base] : 0u;
+        // (the claim has made sure of both ends -- the list ends inside the arena, the tick was not dropped; like the candidates
+        // form's fill below, the copy guards them all the same: it writes into memory shared by every tick)
+        wave_copy_lists<true>(t, lane, e0, cnt, inc, total, uint32_t(fo), src);
         return;
     }
     const uint32_t shard = blockIdx.y;

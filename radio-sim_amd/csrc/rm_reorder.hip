@@ -28,6 +28,13 @@ RM_D void reorder_body(const ModelDev &m, const TickDev &t, const int cwl)
     __shared__ uint32_t s_off[scan_lds(MODE)];
     __shared__ uint32_t s_wave[4];
     const bool publisher = blockIdx.x == 0;
+    // a tick of the heard form whose frames were all served (tick_cnt[0]: frames left to the sweep -- a frame that reaches nobody
+    // and has no list is neither): there is no segment to walk.  Only the publisher goes on, for slot_off and out_count, which
+    // k_reorder_served_batch needs; every other workgroup leaves before the prefetch, the scan and any barrier (block-uniform).
+    if (NC && nc_heard && !publisher && uniform_u(t.nc.tick_cnt[0]) == 0u) {
+        if (t.fl_map == nullptr) write_pkt_interference(m, t, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+        return;
+    }
     const int lane = threadIdx.x & 63;
     const int n_new = t.n_active - t.first_new;
     constexpr bool kRegScan = (MODE == 3 || MODE == 4);
@@ -216,10 +223,19 @@ __global__ void __launch_bounds__(256) k_reorder_batch(const ModelDev m, const T
     reorder_body<STOCH, SINR, SCAN, !STOCH && !SINR>(m, ticks[blockIdx.z], cwl);
 }
 
-// The source cache's heard form (NbrCacheDev): the ordered records of the frames that were served from a list.  One wave per
-// 64 consecutive frames; every hit frame's list is copied with full lanes from the arena's columns to the frame's place
-// slot_off[slot] (an entry finds its frame by bisection over the lanes' running counts).  Consecutive frames have adjacent
-// output ranges, so the wave's stores coalesce.  Launched right behind k_reorder_batch, whose publisher wrote slot_off.
+// The source cache's heard form (NbrCacheDev): the ordered records of the frames that were served from a list.  A wave takes 64
+// consecutive frames; every hit frame's list is copied with full lanes from the arena's columns to the frame's place
+// slot_off[slot] (wave_copy_lists, rm_device.hpp).  Consecutive frames have adjacent output ranges, so the wave's stores coalesce.
+// Launched right behind k_reorder_batch, whose publisher wrote slot_off.
+// Measured and dropped: P waves (gridDim.y) sharing the 64 frames' records, each redoing the prologue below and taking every P-th
+// span (a wave's work is its frames' records, not its frames: the bench shape has 2800 records per 64 frames, eleven dependent
+// load -> store spans for one wave, two waves per SIMD in all).  c3, three contexts in flight, this kernel's total over a traced run,
+// ms, two runs each of the default run | --warmup 24:  1 wave 1.29 1.49 | 2.08 2.21   2 waves 1.06 1.27 | 2.04 2.14   4 waves
+// 0.95 1.11 | 1.81 2.04   8 waves 1.25 1.33 | 2.26 2.31.  4 are 22-26 % below 1 on the default run, more than the kernel's spread,
+// and the step does not see it (profiles/README.md).  They cannot be shipped: `bench.py --full` prices every k_reorder* kernel
+// with the launch's required bytes, receiver table included, which a served sequence never reads; its 1 M-node probe (16 ticks,
+// 717 k served records, 131 MB priced: 16.4 us at the HBM peak) refuses the line for the 10.5 us that 4 waves take there, and
+// 2 waves (about 21 us) do not beat 1 by more than the spread.
 __global__ void __launch_bounds__(256) k_reorder_served_batch(const TickDev *__restrict__ ticks)
 {
     const TickDev &t = ticks[blockIdx.z];
@@ -230,43 +246,12 @@ __global__ void __launch_bounds__(256) k_reorder_served_batch(const TickDev *__r
     uint2 h = make_uint2(0u, 0u);
     if (e < t.n_active - t.first_new) h = t.nc.hit[e]; // (the cache serves ticks with first_eval == first_new == 0: frame == packet)
     const uint32_t cnt = h.x > 1u ? h.x - 1u : 0u; // (0: swept, or an empty list)
-    const uint32_t dst = cnt ? t.slot_off[e + t.shift] : 0u;
     const uint32_t inc = wave_inclusive_scan(cnt, lane);
     const uint32_t total = uniform_u(uint32_t(__shfl(int(inc), 63)));
-    // four rounds of 64 entries at a time: all their loads are requested before the first store (the arena and the records may
-    // alias as far as the compiler knows, so it would wait for every round's loads on its own)
-    constexpr int kRounds = 4;
-    for (uint32_t j0 = 0; j0 < total; j0 += 64u * kRounds) { // wave-uniform
-        uint32_t d[kRounds];
-        bool ok[kRounds];
-        int pkt[kRounds], v_dst[kRounds];
-        double v_rssi[kRounds];
-        uint8_t v_verdict[kRounds];
-#pragma unroll
-        for (int u = 0; u < kRounds; ++u) {
-            const uint32_t j = j0 + uint32_t(u * 64 + lane);
-            const int f = wave_run_of(inc, j);
-            const uint32_t f_inc = uint32_t(__shfl(int(inc), f)), f_cnt = uint32_t(__shfl(int(cnt), f)), f_off = uint32_t(__shfl(int(h.y), f));
-            const uint32_t f_dst = uint32_t(__shfl(int(dst), f));
-            const uint32_t k = j - (f_inc - f_cnt);
-            const uint32_t a = f_off + k;
-            d[u] = f_dst + k;
-            pkt[u] = e0 + f;
-            ok[u] = j < total && d[u] < t.cap && a < t.nc.arena_len; // (a: the claim kept every list inside the arena; guarded like every read of it)
-            v_dst[u] = ok[u] ? t.nc.arena[a] : 0;
-            v_rssi[u] = ok[u] ? t.nc.arena_rssi[a] : 0.0;
-            v_verdict[u] = ok[u] ? t.nc.arena_verdict[a] : uint8_t(0);
-        }
-#pragma unroll
-        for (int u = 0; u < kRounds; ++u) {
-            if (ok[u]) {
-                t.out_pkt[d[u]] = pkt[u];
-                t.out_dst[d[u]] = v_dst[u];
-                t.out_rssi[d[u]] = v_rssi[u];
-                t.out_verdict[d[u]] = v_verdict[u];
-            }
-        }
-    }
+    if (total == 0u) return; // (wave-uniform)
+    const uint32_t dst = cnt ? t.slot_off[e + t.shift] : 0u;
+    // (the list's place: the claim kept every list inside the arena; guarded like every read of it)
+    wave_copy_lists<false>(t, lane, e0, cnt, inc, total, h.y, dst);
 }
 
 // ============================================================================ Java-RNG draws

@@ -36,6 +36,14 @@ struct TickGroup {
 };
 static_assert(sizeof(TickGroup) + 32 <= 4096, "kernel arguments are limited to 4 KB");
 
+// the source cache's per-tick counters start every launch sequence at zero: the workgroup that copies a tick's descriptor zeroes
+// them, on the stream behind the previous sequence's kernels and in front of this one's pre-pass (a fill between two kernels
+// is a stream operation of its own; k_ov_begin, rm_airbatch.hip, has the cost)
+RM_D void zero_tick_cnt(const NbrCacheDev &nc)
+{
+    if (nc.state != nullptr && threadIdx.x < 4) nc.tick_cnt[threadIdx.x] = 0u;
+}
+
 __global__ void __launch_bounds__(64) k_store_ticks(const TickGroup g, TickDev *dst, int n)
 {
     // one descriptor per workgroup, copied as 32-bit words
@@ -44,6 +52,7 @@ __global__ void __launch_bounds__(64) k_store_ticks(const TickGroup g, TickDev *
     const uint32_t *src = reinterpret_cast<const uint32_t *>(&g.t[blockIdx.x]);
     uint32_t *out = reinterpret_cast<uint32_t *>(dst + blockIdx.x);
     for (int i = threadIdx.x; i < int(sizeof(TickDev) / 4); i += blockDim.x) out[i] = src[i];
+    zero_tick_cnt(g.t[blockIdx.x].nc);
 }
 
 // larger batches: the descriptors are read from pinned, host-mapped memory by the device itself (no copy
@@ -54,6 +63,8 @@ __global__ void __launch_bounds__(64) k_fetch_ticks(const TickDev *__restrict__ 
     const uint32_t *src = reinterpret_cast<const uint32_t *>(host_mapped + blockIdx.x);
     uint32_t *out = reinterpret_cast<uint32_t *>(dst + blockIdx.x);
     for (int i = threadIdx.x; i < int(sizeof(TickDev) / 4); i += blockDim.x) out[i] = src[i];
+    __syncthreads();
+    zero_tick_cnt(dst[blockIdx.x].nc); // (the copy just written: no second read of the descriptor over the bus)
 }
 
 hipError_t launch_fetch_ticks(hipStream_t s, const TickDev *host_mapped, int n, TickDev *dev_ticks)
