@@ -842,6 +842,65 @@ int rm_listen_device(rm_context *ctx, const rm_listen_schedule **dev_sched, cons
 /* the listening rule itself, a pure host function without a device: 1, 0, or RM_ERR_INVALID for a NULL or bad record */
 int rm_listen_at(const rm_listen_schedule *s, int64_t t_us);
 
+/* ---- watched-link statistics: per-link counters on the device -------------------------------------------------------
+ * (not reference behaviour.)  Opt-in, on every medium.  What a link estimator reads (ETX / PRR
+ * over beacons, neighbour time-outs) without copying heard links to the host: every node has K slots of watched peers, set by the
+ * caller, and one rm_link_stats per (node, slot).  Two tables of the context, both [n_nodes][K] in device memory: peer (int32,
+ * -1: an empty slot) and the entries; and one rm_stats_totals.  K is 1, 2, 4 or 8 (a power of two: a node's peer row is one
+ * aligned load of 4 K bytes).  A cleared entry is {0, 0, 0, 0, INT64_MAX, INT64_MIN}.
+ * With the feature on, every evaluating call ends with one more pass over its finished result, behind the frame error model's,
+ * the listening schedules' and the traffic counters' passes (E10, E13, E11, then this).  A slot that is empty changes nothing; one
+ * that overflowed its link capacity or was dropped adds nothing and ticks_skipped += 1 (the traffic counters' conditions); every
+ * other one ticks_counted += 1, and for every heard link i of it, with rec = tx[first_new + pkt[i]], s = rec.src, j = dst[i]: if
+ * s and j are node indices and peer[j][k] == s for some k, entry (j, k) gets heard += 1; delivered += 1 iff the link's final
+ * verdict (after the draws, the SINR stages, E10's and E13's passes) is RM_DELIVERED; rssi_q8_sum += q8(rssi[i]); sinr_q8_sum +=
+ * q8(sinr[i]) on a medium with the sinr column (elsewhere it stays 0); first_start_us = min(first_start_us, rec.start_us);
+ * last_start_us = max(last_start_us, rec.start_us).  q8(x) = 0 unless fabs(x) < 2147483648.0 (so NaN and the infinities give 0),
+ * otherwise (int64_t)floor(x * 256.0 + 0.5), one rounding per operation and no fma: rm_linkstats_q8.  Nothing else is read or
+ * written: results, the on-air window, java.util.Random, the traffic counters and the listening schedules' tables are as with the
+ * feature off.  All sums are integers, minima or maxima: the tables after any sequence of calls do not depend on whether lone
+ * ticks, a batch, a gated batch, a CSMA-CA batch or any split of a CSMA-CA run into carry batches evaluated the frames.
+ * Peers are the caller's: nothing is inserted or evicted by what is heard.
+ * Accepted and refused where the traffic counters are: every evaluating call on a whole-table context (a dense tick ends with its
+ * records and rm_result_dense keeps answering; rm_transmit on a reference medium takes the general tick path); refused with
+ * RM_ERR_STATE before anything is launched, window, generator and tables untouched: contexts with a receiver partition, the
+ * gathered / rm_dist_* / rm_group_* forms; rm_linkstats_enable(ctx, K > 0) on a context made under RM_GRAPH=1.
+ * rm_set_model, rm_seed, rm_node_update, rm_nodes_move and rm_nodes_upload with the same node count keep the tables;
+ * rm_nodes_upload with another node count switches the feature off.  Off (the default): nothing is launched, nothing allocated.
+ * Memory: n_nodes * K * 52 bytes (416 MB at a million nodes and K = 8). */
+typedef struct rm_link_stats {
+    uint64_t heard;          /* heard links from the watched peer at this node */
+    uint64_t delivered;      /* of those, links whose final verdict is RM_DELIVERED */
+    int64_t rssi_q8_sum;     /* sum of q8(rssi) over the heard links: dBm in 1/256 */
+    int64_t sinr_q8_sum;     /* sum of q8(sinr) over the heard links (0 on a medium without the sinr column) */
+    int64_t first_start_us;  /* smallest start_us of a heard frame; INT64_MAX: none yet */
+    int64_t last_start_us;   /* largest start_us of a heard frame; INT64_MIN: none yet */
+} rm_link_stats;             /* 48 bytes */
+/* K = 1, 2, 4 or 8: switches the feature on with K slots per node, every slot empty, every entry cleared, the totals 0; the same K
+ * again changes nothing, another K starts from empty tables.  K = 0: off, the tables released.  Any other K: RM_ERR_INVALID. */
+int rm_linkstats_enable(rm_context *ctx, int32_t K);
+/* K, or 0 while the feature is off */
+int rm_linkstats_enabled(const rm_context *ctx);
+/* peers is n x K, row-major: row r for node nodes[r] (nodes == NULL: for all nodes in node order, n has to be the node count).  A
+ * row's entry is -1 or a node index 0 .. n_nodes - 1 other than the row's own node; the non-negative entries of a row are
+ * distinct; a node appears at most once in nodes.  The whole list is validated before anything changes (RM_ERR_INVALID).  A slot
+ * whose peer stays as it was keeps its entry; a slot whose peer changes gets a cleared entry.  Ordered on the context's stream:
+ * it applies to calls evaluated after it.  RM_ERR_STATE while the feature is off, as the four calls below. */
+int rm_linkstats_watch(rm_context *ctx, const int32_t *nodes, int32_t n, const int32_t *peers);
+/* the peer rows of the listed nodes (the same list convention), n x K */
+int rm_linkstats_peers_get(rm_context *ctx, const int32_t *nodes, int32_t n, int32_t *out);
+/* the entries of the listed nodes, n x K, and the totals (or NULL).  Synchronises the context's stream once. */
+int rm_linkstats_read(rm_context *ctx, const int32_t *nodes, int32_t n, rm_link_stats *out, rm_stats_totals *totals);
+/* clears every entry and the totals and keeps the peers, on the context's stream */
+int rm_linkstats_reset(rm_context *ctx);
+/* the three tables in device memory: valid until the feature is switched off or enabled with another K, another node count or
+ * rm_destroy; the caller's reads are ordered by the context's stream */
+int rm_linkstats_device(rm_context *ctx, const int32_t **dev_peer, const rm_link_stats **dev_table, const rm_stats_totals **dev_totals);
+/* q8 itself, a pure host function without a device */
+int64_t rm_linkstats_q8(double x);
+/* the validation of rm_linkstats_watch alone, a pure host function without a device: RM_OK or RM_ERR_INVALID */
+int rm_linkstats_validate(int32_t n_nodes, int32_t K, const int32_t *nodes, int32_t n, const int32_t *peers);
+
 /* ---- several devices behind one caller --------------------------------------------------------------
  * The reference host is ONE process (Main.java:65-73): a group drives n contexts from one host thread, one
  * per device (an ordinal may repeat: several partitions on one GPU).  Receivers are partitioned over the

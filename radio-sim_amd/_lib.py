@@ -84,6 +84,16 @@ LISTEN_SCHEDULE_DTYPE = np.dtype([(name, "<i8") for name, _ in ListenSchedule._f
 assert LISTEN_SCHEDULE_DTYPE.itemsize == C.sizeof(ListenSchedule) == 24
 
 
+class LinkStats(C.Structure):
+    """rm_link_stats: one watched (node, peer) link's counters (48 bytes)"""
+    _fields_ = [("heard", C.c_uint64), ("delivered", C.c_uint64), ("rssi_q8_sum", C.c_int64), ("sinr_q8_sum", C.c_int64),
+                ("first_start_us", C.c_int64), ("last_start_us", C.c_int64)]
+
+
+LINK_STATS_DTYPE = np.dtype([(name, "<u8" if t is C.c_uint64 else "<i8") for name, t in LinkStats._fields_])
+assert LINK_STATS_DTYPE.itemsize == C.sizeof(LinkStats) == 48
+
+
 class ModelParams(C.Structure):
     _fields_ = [("kind", C.c_int32), ("flags", C.c_int32),
                 ("udgm_success_ratio_tx", C.c_double), ("udgm_success_ratio_rx", C.c_double),
@@ -333,6 +343,15 @@ SIGNATURES = {
     "rm_listen_missed_reset": (C.c_int, [C.c_void_p]),
     "rm_listen_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "rm_listen_at": (C.c_int, [C.c_void_p, C.c_int64]),
+    "rm_linkstats_enable": (C.c_int, [C.c_void_p, C.c_int32]),
+    "rm_linkstats_enabled": (C.c_int, [C.c_void_p]),
+    "rm_linkstats_watch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "rm_linkstats_peers_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "rm_linkstats_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(StatsTotals)]),
+    "rm_linkstats_reset": (C.c_int, [C.c_void_p]),
+    "rm_linkstats_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "rm_linkstats_q8": (C.c_int64, [C.c_double]),
+    "rm_linkstats_validate": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "rm_det_math": (C.c_double, [C.c_int32, C.c_double]),
     "rm_link_hash": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
     "rm_evq_init": (None, [C.c_void_p]),

@@ -231,9 +231,10 @@ int rmh::launch_batch(rm_context *c, TickSlot *const *slots, const TickPlan *pla
     }
     // (RM_BATCH_FRAMES; not over a rank's frame list: k_tick_frames_batch writes no offsets by global packet number, which the result readers
     // of such a slot take)
-    // (nor with the traffic counters or the listening schedules on: their one launch reads every slot's compact arrays, which this
-    // form leaves for later)
-    if (batch_frames && !cfg.stochastic && !plans[0].sinr && !after_sweep && !(rank_frames && ticks[0].n_pub > 0) && !stats_on(c) && !listen_on(c)) {
+    // (nor with the traffic counters, the listening schedules or the watched-link statistics on: their one launch reads every slot's
+    // compact arrays, which this form leaves for later)
+    if (batch_frames && !cfg.stochastic && !plans[0].sinr && !after_sweep && !(rank_frames && ticks[0].n_pub > 0) && !stats_on(c) && !listen_on(c) &&
+        !linkstats_on(c)) {
         int seg_len = rm::frame_tick_segment(ticks[0], cfg, m);
         for (int b = 1; b < n && seg_len > 0; ++b) seg_len = std::min(seg_len, rm::frame_tick_segment(ticks[b], cfg, m));
         if (seg_len > 0) {
@@ -294,6 +295,11 @@ int rmh::launch_batch(rm_context *c, TickSlot *const *slots, const TickPlan *pla
         RM_TRY(stage(RM_STAGE_REORDER));
         RM_HIP(rm::launch_stats_batch(s, stats_dev(c), n, dev_ticks));
     }
+    if (linkstats_on(c)) {
+        // the watched-link statistics (E14): behind the traffic counters' pass, reading what it reads; ONE launch over all slots
+        RM_TRY(stage(RM_STAGE_REORDER));
+        RM_HIP(rm::launch_linkstats_batch(s, linkstats_dev(c), n, dev_ticks));
+    }
     for (int b = 0; b < n; ++b) {
         slots[b]->have_result = true;
         slots[b]->compact_pending = false;
@@ -318,6 +324,7 @@ int rmh::batch_run(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us, co
     RM_TRY(em_check(c, any_gathered)); // (the frame error model: refused before anything is planned or the window moves)
     RM_TRY(stats_check(c, any_gathered)); // (the traffic counters: likewise)
     RM_TRY(listen_check(c, any_gathered)); // (the listening schedules: likewise)
+    RM_TRY(linkstats_check(c, any_gathered)); // (the watched-link statistics: likewise)
     static thread_local std::vector<int32_t> n_gath;
     if (any_gathered) {
         n_gath.assign(size_t(n_ticks), gather_world * gather_slots);
@@ -469,9 +476,9 @@ int rmh::batch_run(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us, co
     parity.dismiss();
     for (int b = 0; b < n_ticks; ++b) RM_TRY(launch_tick(c, *slots[b], plans[b], false));
     const bool em_pass = em_on(c) && sinr;
-    if (em_pass || stats_on(c) || listen_on(c)) {
-        // the frame error model, the listening schedules and the traffic counters over the ticks that were launched one by one:
-        // their compact arrays, the descriptors stored once, then one pass each over all of them (in this order)
+    if (em_pass || stats_on(c) || listen_on(c) || linkstats_on(c)) {
+        // the frame error model, the listening schedules, the traffic counters and the watched-link statistics over the ticks that
+        // were launched one by one: their compact arrays, the descriptors stored once, then one pass each over all of them (in this order)
         static thread_local std::vector<rm::TickDev> em_ticks;
         em_ticks.clear();
         for (int b = 0; b < n_ticks; ++b) {
@@ -489,6 +496,7 @@ int rmh::batch_run(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us, co
             if (em_pass) RM_HIP(rm::launch_errmodel_batch(c->stream, em_dev(c), int(em_ticks.size()), c->d_ticks.p));
             if (listen_on(c)) RM_HIP(rm::launch_listen_batch(c->stream, listen_dev(c), int(em_ticks.size()), c->d_ticks.p));
             if (stats_on(c)) RM_HIP(rm::launch_stats_batch(c->stream, stats_dev(c), int(em_ticks.size()), c->d_ticks.p));
+            if (linkstats_on(c)) RM_HIP(rm::launch_linkstats_batch(c->stream, linkstats_dev(c), int(em_ticks.size()), c->d_ticks.p));
         }
     }
     return RM_OK;

@@ -444,6 +444,12 @@ int launch_tick(rm_context *c, TickSlot &ts, const TickPlan &plan, bool em_pass)
             RM_TRY(materialize(c, ts));
             RM_HIP(rm::launch_stats(s, stats_dev(c), ts.last));
         }
+        if (em_pass && linkstats_on(c)) {
+            // the watched-link statistics (E14) over a dense tick: as the traffic counters, behind them
+            RM_TRY(stage(RM_STAGE_REORDER));
+            RM_TRY(materialize(c, ts));
+            RM_HIP(rm::launch_linkstats(s, linkstats_dev(c), ts.last));
+        }
         return RM_OK;
     }
     const int seg_len = (t.n_active - t.first_new <= frame_tick_max()) ? rm::frame_tick_segment(t, cfg, m) : 0;
@@ -587,6 +593,13 @@ int launch_tick(rm_context *c, TickSlot &ts, const TickPlan &plan, bool em_pass)
         RM_TRY(stage(RM_STAGE_REORDER));
         RM_TRY(materialize(c, ts));
         RM_HIP(rm::launch_stats(s, stats_dev(c), ts.last));
+    }
+    if (em_pass && linkstats_on(c)) {
+        if (ts.draws_pending) return fail(RM_ERR_STATE, "internal: the watched-link statistics' pass cannot run before the ranks' draws are finished");
+        // the watched-link statistics (E14), behind the traffic counters' pass: the tick's compact arrays at once, then one pass over them
+        RM_TRY(stage(RM_STAGE_REORDER));
+        RM_TRY(materialize(c, ts));
+        RM_HIP(rm::launch_linkstats(s, linkstats_dev(c), ts.last));
     }
     return RM_OK;
 }

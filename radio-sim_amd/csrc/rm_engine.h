@@ -537,6 +537,16 @@ struct ListenDev {
     int n_nodes;
 };
 
+// Watched-link statistics (rm_linkstats.hip): the tables the pass over a finished result reads
+// (peer) and adds to (table, totals)
+struct LinkStatsDev {
+    const int32_t *peer;     // [n_nodes][K], -1: an empty slot; a row is 4 K bytes, aligned to its size
+    rm_link_stats *table;    // [n_nodes][K]
+    rm_stats_totals *totals; // [1]
+    int n_nodes;
+    int K;                   // 1, 2, 4 or 8
+};
+
 // The unicast outcome query (rm_unicast.hip): what the query reads of one finished result slot --
 // the compact packet-major arrays every result reader gets, the records of the tick's new frames, the slot's counters
 struct UcSlot {
@@ -898,6 +908,18 @@ hipError_t launch_listen_scatter(hipStream_t s, rm_listen_schedule *table, int n
 hipError_t launch_listen_gather(hipStream_t s, const ListenDev &ld, const int32_t *nodes, int n, uint64_t *out);
 bool host_listen_valid(const rm_listen_schedule &s);
 bool host_listen_at(const rm_listen_schedule &s, int64_t t_us);
+
+// (rm_linkstats.hip) the watched-link statistics' pass over one finished result slot / over the n slots of a batch in one launch;
+// the fill of new tables (every slot empty, every entry cleared; peers == nullptr: the entries alone); the watch rule over n rows
+// (row r: new_peers[r][K] for node nodes[r], or node r with nodes == nullptr -- a slot whose peer changes is written and its entry
+// cleared); the gather of listed nodes' entries and the totals
+hipError_t launch_linkstats(hipStream_t s, const LinkStatsDev &ld, const TickDev &t);
+hipError_t launch_linkstats_batch(hipStream_t s, const LinkStatsDev &ld, int n, const TickDev *dev_ticks);
+hipError_t launch_linkstats_clear(hipStream_t s, int32_t *peers, rm_link_stats *table, size_t n_entries);
+hipError_t launch_linkstats_scatter(hipStream_t s, int32_t *peer, rm_link_stats *table, int n_nodes, int K, const int32_t *nodes, int n,
+                                    const int32_t *new_peers);
+hipError_t launch_linkstats_gather(hipStream_t s, const LinkStatsDev &ld, const int32_t *nodes, int n, rm_link_stats *out, rm_stats_totals *totals_out);
+int64_t host_linkstats_q8(double x);
 
 // (rm_unicast.hip) the unicast outcome query, one launch: a lane per entry.  n_slots result slots described by dev_slots -- or, with
 // dev_slots == nullptr, the one slot `lone`.  Slots form (dev_prefix: [n_slots + 1] exclusive prefix of the entries per slot; nullptr

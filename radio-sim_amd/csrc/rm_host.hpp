@@ -169,6 +169,19 @@ struct rm_context : TickSlot {
         char *h_block = nullptr;
         size_t h_cap = 0; // list entries the block has room for
     } ls;
+    // watched-link statistics (E14; rm_api_linkstats.cpp, rm_linkstats.hip): K peer slots and K entries per node index, the totals,
+    // the host's copy of the peer rows (rm_linkstats_peers_get reads it), the device staging of a whole-table watch and the pinned,
+    // host-mapped block a list watch or a list read is staged through
+    struct LinkStats {
+        int32_t K = 0;  // slots per node; 0: off
+        int32_t n = -1; // the node count the tables were made for; -1: off
+        std::vector<int32_t> host;
+        DevBuf<int32_t> peer, stage;
+        DevBuf<rm_link_stats> table;
+        DevBuf<rm_stats_totals> totals;
+        char *h_block = nullptr;
+        size_t h_cap = 0; // rows the block has room for
+    } lk;
     // the unicast outcome query (E12; rm_api_unicast.cpp, rm_unicast.hip): what the last evaluating call left -- how many result slots,
     // and whether it was a gathered / rm_dist_* / rm_group_* form -- the slots' descriptors in device memory (rm::UcSlot per slot,
     // then the prefix of a slots-form query), their pinned staging (two blocks, each rewritten only after its copy has completed), and
@@ -698,6 +711,16 @@ rm::ListenDev listen_dev(const rm_context *c);
 int listen_check(const rm_context *c, bool gathered);
 // rm_nodes_upload: another node count clears the feature
 int listen_nodes_changed(rm_context *c);
+
+// ---- rm_api_linkstats.cpp: watched-link statistics (E14)
+inline bool linkstats_on(const rm_context *c) { return c->lk.K > 0; }
+rm::LinkStatsDev linkstats_dev(const rm_context *c);
+// what an evaluating call refuses while the feature is on, before anything is launched (the shape of em_check)
+int linkstats_check(const rm_context *c, bool gathered);
+// rm_nodes_upload: another node count switches the feature off
+int linkstats_nodes_changed(rm_context *c);
+// rm_destroy: the tables and the host block
+void linkstats_release(rm_context *c);
 
 // ---- rm_api_unicast.cpp: the unicast outcome query (E12)
 // an evaluating call has left its results in `slots` result slots (gathered: a gathered / rm_dist_* / rm_group_* form)

@@ -175,6 +175,15 @@ RM_HD bool listen_at(const rm_listen_schedule &s, int64_t t_us)
     return r < s.on_us;
 }
 
+// the watched-link statistics' fixed point: a dB value in 1/256 dB, rounded half up; 0 for NaN, an
+// infinity and everything whose product would leave 64-bit range by far.  E-math: one multiplication, one addition, one floor --
+// the text the pass (rm_linkstats.hip) and rm_linkstats_q8 are both built from
+RM_HD int64_t linkstats_q8(double x)
+{
+    if (!(fabs(x) < 2147483648.0)) return 0;
+    return int64_t(floor(x * 256.0 + 0.5));
+}
+
 // Position.getDistance, Position.java:56-64: this = transmitter, p2 = receiver;
 // (dx*dx + dy*dy) + dz*dz, then a correctly rounded square root.
 RM_HD double ref_distance(double ax, double ay, double az, double bx, double by, double bz)

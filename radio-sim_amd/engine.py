@@ -324,6 +324,71 @@ class Engine:
         s = _lib.ListenSchedule(*[int(v) for v in sched])
         return int(_lib.lib().rm_listen_at(C.byref(s), int(t)))
 
+    # -- watched-link statistics: per-link counters on the device
+    def linkstats_enable(self, K):
+        """rm_linkstats_enable: K = 1, 2, 4 or 8 slots of watched peers per node (all empty); 0 switches the feature off"""
+        check(self._L.rm_linkstats_enable(self._h, int(K)))
+
+    def linkstats_enabled(self):
+        """rm_linkstats_enabled: K, or 0 while the feature is off"""
+        return int(self._L.rm_linkstats_enabled(self._h))
+
+    def _linkstats_rows(self, nodes):
+        """(K, index array or None, rows) of a list call"""
+        K = self.linkstats_enabled()
+        if nodes is None:
+            return K, None, max(int(self._L.rm_node_count(self._h)), 0)
+        idx = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+        return K, idx, idx.shape[0]
+
+    def linkstats_watch(self, peers, nodes=None):
+        """rm_linkstats_watch: peers [n][K] (-1: an empty slot) for all nodes in node order, or for the listed nodes; a slot whose
+        peer changes starts from a cleared entry, every other slot keeps its own"""
+        K, idx, _ = self._linkstats_rows(nodes)
+        rows = np.ascontiguousarray(peers, dtype=np.int32).reshape(-1, max(K, 1))
+        if idx is not None and idx.shape[0] != rows.shape[0]:
+            raise ValueError("one row of peers per listed node")
+        check(self._L.rm_linkstats_watch(self._h, None if idx is None else idx.ctypes.data, rows.shape[0], rows.ctypes.data))
+
+    def linkstats_peers(self, nodes=None):
+        """rm_linkstats_peers_get: int32 [n][K] (the listed nodes in list order, or all in node order)"""
+        K, idx, n = self._linkstats_rows(nodes)
+        out = np.full((n, max(K, 1)), -1, dtype=np.int32)
+        check(self._L.rm_linkstats_peers_get(self._h, None if idx is None else idx.ctypes.data, n, out.ctypes.data))
+        return out
+
+    def linkstats_read(self, nodes=None):
+        """rm_linkstats_read: (structured array [n][K] of LINK_STATS_DTYPE -- the listed nodes in list order, or all in node order
+        --, {"ticks_counted", "ticks_skipped"})"""
+        K, idx, n = self._linkstats_rows(nodes)
+        tot = _lib.StatsTotals()
+        out = np.zeros((n, max(K, 1)), dtype=_lib.LINK_STATS_DTYPE)
+        check(self._L.rm_linkstats_read(self._h, None if idx is None else idx.ctypes.data, n, out.ctypes.data, C.byref(tot)))
+        return out, {"ticks_counted": int(tot.ticks_counted), "ticks_skipped": int(tot.ticks_skipped)}
+
+    def linkstats_reset(self):
+        check(self._L.rm_linkstats_reset(self._h))
+
+    def linkstats_device(self):
+        """rm_linkstats_device: device pointers of (peer [n_nodes][K] int32, entries [n_nodes][K] of 48-byte records, totals)"""
+        peer, tbl, tot = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(self._L.rm_linkstats_device(self._h, C.byref(peer), C.byref(tbl), C.byref(tot)))
+        return peer.value, tbl.value, tot.value
+
+    @staticmethod
+    def linkstats_q8(x):
+        """rm_linkstats_q8 (pure host): a dB value in 1/256 dB, rounded half up; 0 for NaN, an infinity or |x| >= 2^31"""
+        return int(_lib.lib().rm_linkstats_q8(float(x)))
+
+    @staticmethod
+    def linkstats_validate(n_nodes, K, peers, nodes=None):
+        """rm_linkstats_validate (pure host): the return code of the validation rm_linkstats_watch runs (0: accepted)"""
+        rows = np.ascontiguousarray(peers, dtype=np.int32).reshape(-1)
+        n = rows.shape[0] // K if K > 0 else rows.shape[0]
+        idx = None if nodes is None else np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+        return int(_lib.lib().rm_linkstats_validate(int(n_nodes), int(K), None if idx is None else idx.ctypes.data,
+                                                   n if idx is None else idx.shape[0], rows.ctypes.data))
+
     # -- java.util.Random
     def seed(self, seed):
         check(self._L.rm_seed(self._h, seed))

@@ -644,6 +644,55 @@ public:
         }
         return out;
     }
+    // Watched-link statistics (extension E14): per-link counters for a node's routing parent and a handful of candidate parents.
+    // setLinkWatch(K) gives every node K slots of watched peers (K = 1, 2, 4 or 8; 0 switches the feature off); watchLinks(node,
+    // peers) fills the node's slots (nullptr: an empty slot; fewer than K peers: the rest empty) -- a slot whose peer stays keeps
+    // its counters, one whose peer changes starts from a cleared entry --; every evaluating call of the medium then adds each heard
+    // link from a watched peer to that (node, slot) entry.  K and the watch rows survive apply(); false and lastError on a refusal.
+    bool setLinkWatch(int K)
+    {
+        if (K > 0 && !syncNodes()) return false; // the device mirrors the node table first: the tables have its size
+        if (rm_linkstats_enable(ctx_, int32_t(K)) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        if (K != linkWatchK_) linkWatch_.clear();
+        linkWatchK_ = K;
+        return true;
+    }
+    int getLinkWatch() const { return rm_linkstats_enabled(ctx_); }
+    bool watchLinks(const Node &node, const std::vector<const Node *> &peers)
+    {
+        if (!syncNodes()) return false;
+        if (!restoreLinkWatch()) return false; // (a node table of another size has switched the engine's feature off: all rows again)
+        if (linkWatchK_ <= 0 || peers.size() > size_t(linkWatchK_)) {
+            lastError = "watchLinks: setLinkWatch(K) comes first, and a node has K slots";
+            return false;
+        }
+        std::vector<int32_t> row(size_t(linkWatchK_), -1);
+        for (size_t k = 0; k < peers.size(); ++k) row[k] = peers[k] ? peers[k]->index : -1;
+        const int32_t i = node.index;
+        if (rm_linkstats_watch(ctx_, &i, 1, row.data()) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        linkWatch_[i] = row;
+        return true;
+    }
+    // the node's K entries in slot order (empty and lastError on a refusal); `totals`: the ticks counted and skipped
+    std::vector<rm_link_stats> getLinkStatistics(const Node &node, rm_stats_totals *totals = nullptr)
+    {
+        std::vector<rm_link_stats> out;
+        if (!syncNodes()) return out;
+        const int K = rm_linkstats_enabled(ctx_);
+        out.resize(size_t(K > 0 ? K : 0));
+        const int32_t i = node.index;
+        if (K <= 0 || rm_linkstats_read(ctx_, &i, 1, out.data(), totals) != RM_OK) {
+            lastError = K <= 0 ? "no watched-link statistics: setLinkWatch(K) comes first" : rm_last_error();
+            out.clear();
+        }
+        return out;
+    }
     // Did a frame reach the node it was addressed to (extension E12)?  One entry per packet of the LAST evaluated tick -- the tick
     // mode's flush, or transmitIfClear() -- in packet order: destinations[k] is packet k's intended receiver (nullptr: not asked).
     // status is RM_UC_*; link the index of the heard link in the tick's result (-1 without one); rssi and sinr as the result has
@@ -687,6 +736,32 @@ protected:
         }
         // (nor are the listening schedules: the engine keeps them over a change of the medium)
         restoreListenSchedules();
+        // (nor are the watched links)
+        restoreLinkWatch();
+    }
+    // K and the watch rows the medium set, set again where the engine has dropped them (a node table of another size switches the
+    // feature off), as far as their nodes still exist; false and lastError on a refusal
+    bool restoreLinkWatch()
+    {
+        if (linkWatchK_ <= 0 || rm_linkstats_enabled(ctx_) == linkWatchK_) return true;
+        if (rm_linkstats_enable(ctx_, int32_t(linkWatchK_)) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        std::vector<int32_t> idx, rows;
+        const int32_t n = rm_node_count(ctx_);
+        for (const auto &kv : linkWatch_) {
+            bool ok = kv.first < n;
+            for (int32_t p : kv.second) ok = ok && p < n;
+            if (!ok) continue;
+            idx.push_back(kv.first);
+            rows.insert(rows.end(), kv.second.begin(), kv.second.end());
+        }
+        if (!idx.empty() && rm_linkstats_watch(ctx_, idx.data(), int32_t(idx.size()), rows.data()) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        return true;
     }
     // the schedules the medium set, set again where the engine has dropped them (a node table of another size clears its tables), as
     // far as their nodes still exist; false and lastError on a refusal
@@ -709,6 +784,8 @@ protected:
     }
     bool statistics_ = false; // what setStatistics set last, kept across apply()
     std::map<int32_t, rm_listen_schedule> listen_; // what setListenSchedule set, by node index, kept across apply()
+    int linkWatchK_ = 0;                                // what setLinkWatch set last, kept across apply()
+    std::map<int32_t, std::vector<int32_t>> linkWatch_; // what watchLinks set: K peers by node index, kept across apply()
     rm_context *ctx_ = nullptr;
     bool syncNodes() { return !simulator || sync(simulator, simulator->getNodes()); } // the device mirrors the node table first
 
