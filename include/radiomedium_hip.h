@@ -901,6 +901,62 @@ int64_t rm_linkstats_q8(double x);
 /* the validation of rm_linkstats_watch alone, a pure host function without a device: RM_OK or RM_ERR_INVALID */
 int rm_linkstats_validate(int32_t n_nodes, int32_t K, const int32_t *nodes, int32_t n, const int32_t *peers);
 
+/* ---- traffic schedules: periodic sources generated on the device ----------------------------------------------------
+ * (not reference behaviour.)  Opt-in.  One rm_traffic_schedule per node index, a table of the
+ * context.  period_us = 0: the node generates nothing (the default of every node; the other fields have to be 0 then).  Otherwise
+ * 1 <= period_us <= 2^40, 0 <= phase_us < period_us, 0 <= jitter_us <= period_us, reserved = 0.
+ * Node i with P = period_us > 0 has packets k = 0, 1, 2, ...: due(i, k) = phase_us + k * P + j(i, k); j = 0 when jitter_us = 0,
+ * otherwise j = (h * uint64(jitter_us)) >> 64 (the high half of the 128-bit product), h = mix64(mix64(mix64(seed +
+ * 0x9E3779B97F4A7C15) ^ uint64(uint32(i))) ^ uint64(k)), mix64 the finaliser of E2.  jitter_us <= period_us, so due grows
+ * strictly with k; jitter_us = period_us is "once per period at a uniformly random instant".
+ * The generator turns the table, for n_ticks (1 .. RM_MAX_BATCH) half-open windows [win_lo[b], win_hi[b]) (host arrays; 0 <=
+ * win_lo[b] <= win_hi[b] <= 2^62, win_hi[b] <= win_lo[b + 1]: in time order and disjoint, gaps and empty windows allowed), into
+ * the per-tick source lists the batch calls take: node i is a source of window b iff one of its packets has win_lo[b] <= due <
+ * win_hi[b].  Row b of src (int32[n_ticks][cap]) holds those nodes in ascending node index -- distinct, as the gated and CSMA-CA
+ * batches require of a tick's own list -- padded with -1 up to cap; count[b] is the true number of sources; with count[b] > cap the
+ * row holds the first cap of them in node order.  The windows are the generator's own arguments: it does not interpret the
+ * engine's t_begin / t_end / start_us, and a due time inside a window is quantised to whatever start_us the caller gives that
+ * tick.  A node's enabled flag, txprob and channel play no part.  Totals: packets = packets due in any window; coalesced = packets
+ * minus the (node, window) pairs (second and later packets of a node in one window); truncated = the sum over b of max(0,
+ * count[b] - cap).  The result is a pure function of (table, seed, windows, cap): the packets, and so the union of the lists, over
+ * any partition of a time span into windows and into calls are the same; nothing depends on launch geometry, batch size or call
+ * order, and no state is carried between calls.
+ * No evaluating call changes, and the generator reads only its own table: it is accepted on partitioned contexts too (every rank
+ * gets the same lists).  rm_set_model, rm_seed, rm_node_update, rm_nodes_move and rm_nodes_upload with the same node count keep
+ * the table; rm_nodes_upload with another node count clears the feature as rm_traffic_clear does.  Off (the default): nothing is
+ * allocated or launched. */
+typedef struct rm_traffic_schedule { int64_t period_us; int64_t phase_us; int64_t jitter_us; int64_t reserved; } rm_traffic_schedule; /* 32 bytes */
+typedef struct rm_traffic_totals { uint64_t packets; uint64_t coalesced; uint64_t truncated; } rm_traffic_totals;
+/* nodes == NULL: sched[n] for all nodes in node order, n has to be the node count; otherwise sched[k] for node nodes[k], applied in
+ * list order (the last entry of a node wins).  The whole list is validated before anything changes (RM_ERR_INVALID: a bad record, an
+ * index outside 0 .. n_nodes - 1, NULL arguments, a negative count).  Switches the feature on; ordered on the context's stream.
+ * RM_ERR_STATE on a context made under RM_GRAPH=1. */
+int rm_traffic_set(rm_context *ctx, const int32_t *nodes, int32_t n, const rm_traffic_schedule *sched);
+/* the schedules of the listed nodes (the same list convention), read from the device's table; synchronises the stream once.
+ * RM_ERR_STATE before the first rm_traffic_set and after rm_traffic_clear, as rm_traffic_device and the generator. */
+int rm_traffic_get(rm_context *ctx, const int32_t *nodes, int32_t n, rm_traffic_schedule *out);
+/* switches the feature off: the table is forgotten */
+int rm_traffic_clear(rm_context *ctx);
+int rm_traffic_enabled(const rm_context *ctx);
+/* the table ([n_nodes], by node index) in device memory: valid until rm_traffic_clear, another node count or rm_destroy; the
+ * caller's reads are ordered by the context's stream.  RM_ERR_INVALID for a NULL dev_sched. */
+int rm_traffic_device(rm_context *ctx, const rm_traffic_schedule **dev_sched);
+/* The generator, enqueued on the context's stream without waiting for it: dev_src int32[n_ticks][cap], dev_count int32[n_ticks],
+ * dev_totals one rm_traffic_totals or NULL, all device memory.  Row b is a ready source list of rm_batch_run_sources_device and the
+ * gated forms: dev_src + b * cap with n_src[b] = count[b], or, without reading count back, with n_src[b] = cap (-1 entries are
+ * padding there).  RM_ERR_INVALID: NULL arguments, n_ticks outside 1 .. RM_MAX_BATCH, cap < 1, windows that break the rule above;
+ * RM_ERR_CAPACITY: n_ticks * cap above 2^27. */
+int rm_traffic_generate_device(rm_context *ctx, uint64_t seed, int32_t n_ticks, const int64_t *win_lo, const int64_t *win_hi, int32_t cap,
+                               int32_t *dev_src, int32_t *dev_count, rm_traffic_totals *dev_totals);
+/* the same into host arrays (src int32[n_ticks][cap], count int32[n_ticks], totals or NULL); synchronises the stream once */
+int rm_traffic_generate(rm_context *ctx, uint64_t seed, int32_t n_ticks, const int64_t *win_lo, const int64_t *win_hi, int32_t cap,
+                        int32_t *src, int32_t *count, rm_traffic_totals *totals);
+/* due(node, k) itself, a pure host function without a device: 1 and *due_us; 0 for period_us 0 (no packets); RM_ERR_INVALID for a
+ * NULL or bad record, NULL due_us, node < 0, k < 0 or k * period_us above 2^62 (no window reaches such a packet) */
+int rm_traffic_due(const rm_traffic_schedule *s, uint64_t seed, int32_t node, int64_t k, int64_t *due_us);
+/* the validation of rm_traffic_set alone, a pure host function without a device: RM_OK or RM_ERR_INVALID */
+int rm_traffic_validate(int32_t n_nodes, const int32_t *nodes, int32_t n, const rm_traffic_schedule *sched);
+
 /* ---- several devices behind one caller --------------------------------------------------------------
  * The reference host is ONE process (Main.java:65-73): a group drives n contexts from one host thread, one
  * per device (an ordinal may repeat: several partitions on one GPU).  Receivers are partitioned over the

@@ -16,6 +16,7 @@ from ._lib import (MODEL_NULL, MODEL_UDGM, MODEL_UDGM_CONST, MODEL_N2N, MODEL_LO
                    UNHEARD, INTERFERED, DELIVERED, LD_SINR, MAX_BATCH, RadioMediumError, ModelParams, TxRecord,
                    TX_RECORD_DTYPE, build_library, library_path, ErrorModel, EM_NONE, EM_OQPSK_250K,
                    NodeStats, StatsTotals, NODE_STATS_DTYPE,
-                   ListenSchedule, LISTEN_SCHEDULE_DTYPE, LinkStats, LINK_STATS_DTYPE, UnicastOut, UC_NONE, UC_NOT_SENT, UC_UNHEARD, UC_INTERFERED,
+                   ListenSchedule, LISTEN_SCHEDULE_DTYPE, LinkStats, LINK_STATS_DTYPE,
+                   TrafficSchedule, TrafficTotals, TRAFFIC_SCHEDULE_DTYPE, UnicastOut, UC_NONE, UC_NOT_SENT, UC_UNHEARD, UC_INTERFERED,
                    UC_DELIVERED, UC_LOST)
 from .engine import Engine, Group  # noqa: F401

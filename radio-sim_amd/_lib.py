@@ -94,6 +94,20 @@ LINK_STATS_DTYPE = np.dtype([(name, "<u8" if t is C.c_uint64 else "<i8") for nam
 assert LINK_STATS_DTYPE.itemsize == C.sizeof(LinkStats) == 48
 
 
+class TrafficSchedule(C.Structure):
+    """rm_traffic_schedule: one node's periodic traffic (32 bytes)"""
+    _fields_ = [("period_us", C.c_int64), ("phase_us", C.c_int64), ("jitter_us", C.c_int64), ("reserved", C.c_int64)]
+
+
+TRAFFIC_SCHEDULE_DTYPE = np.dtype([(name, "<i8") for name, _ in TrafficSchedule._fields_])
+assert TRAFFIC_SCHEDULE_DTYPE.itemsize == C.sizeof(TrafficSchedule) == 32
+
+
+class TrafficTotals(C.Structure):
+    """rm_traffic_totals: what one generate counted"""
+    _fields_ = [("packets", C.c_uint64), ("coalesced", C.c_uint64), ("truncated", C.c_uint64)]
+
+
 class ModelParams(C.Structure):
     _fields_ = [("kind", C.c_int32), ("flags", C.c_int32),
                 ("udgm_success_ratio_tx", C.c_double), ("udgm_success_ratio_rx", C.c_double),
@@ -352,6 +366,16 @@ SIGNATURES = {
     "rm_linkstats_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "rm_linkstats_q8": (C.c_int64, [C.c_double]),
     "rm_linkstats_validate": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "rm_traffic_set": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "rm_traffic_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "rm_traffic_clear": (C.c_int, [C.c_void_p]),
+    "rm_traffic_enabled": (C.c_int, [C.c_void_p]),
+    "rm_traffic_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "rm_traffic_generate_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "rm_traffic_generate": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_traffic_due": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
+    "rm_traffic_validate": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "rm_det_math": (C.c_double, [C.c_int32, C.c_double]),
     "rm_link_hash": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
     "rm_evq_init": (None, [C.c_void_p]),

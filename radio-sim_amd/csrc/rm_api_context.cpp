@@ -327,6 +327,7 @@ void rm_destroy(rm_context *c)
     c->ls.sched.release(); c->ls.missed.release();
     if (c->ls.h_block) (void)hipHostFree(c->ls.h_block);
     c->ls.h_block = nullptr;
+    traffic_release(c);
     linkstats_release(c);
     c->uc.d_desc.release(); c->uc.d_io.release();
     for (int g = 0; g < 2; ++g) {

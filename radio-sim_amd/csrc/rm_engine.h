@@ -921,6 +921,33 @@ hipError_t launch_linkstats_scatter(hipStream_t s, int32_t *peer, rm_link_stats 
 hipError_t launch_linkstats_gather(hipStream_t s, const LinkStatsDev &ld, const int32_t *nodes, int n, rm_link_stats *out, rm_stats_totals *totals_out);
 int64_t host_linkstats_q8(double x);
 
+// (rm_traffic.hip) the traffic generator.  The node table is cut into `units` runs of `chunk`
+// consecutive nodes (traffic_geometry), one wave each; a generate is three launches: the units' sources per window into
+// unit_count [units][n_ticks] and their packets into unit_packets [units]; one workgroup per window turns its column into
+// exclusive prefixes, writes count[b] and pads the row's tail with -1; the units write their nodes behind their prefixes, and the
+// first of them the totals (out_totals may be nullptr).  win: [2 * n_ticks] device words, the n_ticks win_lo then the n_ticks win_hi.
+struct TrafficGen {
+    const rm_traffic_schedule *sched; // [n_nodes], by node index
+    int n_nodes;
+    uint64_t seed;
+    int n_ticks;
+    const int64_t *win;
+    int cap;
+    int units, chunk;
+    int32_t *unit_count;
+    uint64_t *unit_packets;
+    int32_t *out_src;   // [n_ticks][cap]
+    int32_t *out_count; // [n_ticks]
+    rm_traffic_totals *out_totals;
+};
+void traffic_geometry(int n_nodes, int *units, int *chunk);
+hipError_t launch_traffic_generate(hipStream_t s, const TrafficGen &g);
+// the scatter of a list update from a host-mapped block (entry k: sched[k] to node nodes[k]) and the gather of listed nodes' records
+hipError_t launch_traffic_scatter(hipStream_t s, rm_traffic_schedule *table, int n_nodes, const int32_t *nodes, int n, const rm_traffic_schedule *sched);
+hipError_t launch_traffic_gather(hipStream_t s, const rm_traffic_schedule *table, int n_nodes, const int32_t *nodes, int n, rm_traffic_schedule *out);
+bool host_traffic_valid(const rm_traffic_schedule &s);
+int64_t host_traffic_due(const rm_traffic_schedule &s, uint64_t seed, int32_t node, int64_t k);
+
 // (rm_unicast.hip) the unicast outcome query, one launch: a lane per entry.  n_slots result slots described by dev_slots -- or, with
 // dev_slots == nullptr, the one slot `lone`.  Slots form (dev_prefix: [n_slots + 1] exclusive prefix of the entries per slot; nullptr
 // with one slot): entry e is packet e - prefix[b] of slot b.  At form: entry e names (dev_slot[e], dev_pkt[e]).

@@ -182,6 +182,22 @@ struct rm_context : TickSlot {
         char *h_block = nullptr;
         size_t h_cap = 0; // rows the block has room for
     } lk;
+    // traffic schedules (E15; rm_api_traffic.cpp, rm_traffic.hip): one schedule per node index; the pinned, host-mapped block a list
+    // update or a list read is staged through; the generator's scratch (the windows, the units' counts and packets) and the pinned
+    // staging of its windows -- two blocks, each rewritten only after its copy has completed
+    struct Traffic {
+        bool on = false;
+        int32_t n = -1; // the node count the table was made for; -1: never set (or cleared)
+        DevBuf<rm_traffic_schedule> sched;
+        char *h_block = nullptr;
+        size_t h_cap = 0; // list entries the block has room for
+        DevBuf<int64_t> d_win;
+        DevBuf<int32_t> d_unit_count;
+        DevBuf<uint64_t> d_unit_packets;
+        int64_t *h_win[2] = {nullptr, nullptr};
+        hipEvent_t h_ev[2] = {nullptr, nullptr};
+        int gen = 0;
+    } tf;
     // the unicast outcome query (E12; rm_api_unicast.cpp, rm_unicast.hip): what the last evaluating call left -- how many result slots,
     // and whether it was a gathered / rm_dist_* / rm_group_* form -- the slots' descriptors in device memory (rm::UcSlot per slot,
     // then the prefix of a slots-form query), their pinned staging (two blocks, each rewritten only after its copy has completed), and
@@ -721,6 +737,12 @@ int linkstats_check(const rm_context *c, bool gathered);
 int linkstats_nodes_changed(rm_context *c);
 // rm_destroy: the tables and the host block
 void linkstats_release(rm_context *c);
+
+// ---- rm_api_traffic.cpp: traffic schedules (E15)
+// rm_nodes_upload: another node count clears the feature
+int traffic_nodes_changed(rm_context *c);
+// rm_destroy
+void traffic_release(rm_context *c);
 
 // ---- rm_api_unicast.cpp: the unicast outcome query (E12)
 // an evaluating call has left its results in `slots` result slots (gathered: a gathered / rm_dist_* / rm_group_* form)

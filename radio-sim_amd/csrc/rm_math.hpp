@@ -184,6 +184,54 @@ RM_HD int64_t linkstats_q8(double x)
     return int64_t(floor(x * 256.0 + 0.5));
 }
 
+// the traffic schedule: what a record may hold, a packet's due time, and the number of a node's packets
+// due before a time -- the text the generator (rm_traffic.hip), rm_traffic_due and rm_traffic_validate are all built from.
+// 64-bit integers only.
+constexpr int64_t kTrafficMaxPeriod = int64_t(1) << 40;
+constexpr int64_t kTrafficMaxTime = int64_t(1) << 62;
+
+RM_HD bool traffic_valid(const rm_traffic_schedule &s)
+{
+    if (s.reserved != 0) return false;
+    if (s.period_us == 0) return s.phase_us == 0 && s.jitter_us == 0;
+    return s.period_us >= 1 && s.period_us <= kTrafficMaxPeriod && s.phase_us >= 0 && s.phase_us < s.period_us && s.jitter_us >= 0 &&
+           s.jitter_us <= s.period_us;
+}
+
+// j(i, k): 0 without jitter, otherwise the high half of h * jitter_us, so 0 <= j < jitter_us
+RM_HD int64_t traffic_jitter(const rm_traffic_schedule &s, uint64_t seed, int32_t node, int64_t k)
+{
+    if (s.jitter_us == 0) return 0;
+    const uint64_t h = mix64(mix64(mix64(seed + 0x9E3779B97F4A7C15ull) ^ uint64_t(uint32_t(node))) ^ uint64_t(k));
+#if defined(__HIP_DEVICE_COMPILE__)
+    return int64_t(__umul64hi(h, uint64_t(s.jitter_us)));
+#else
+    return int64_t(uint64_t((static_cast<unsigned __int128>(h) * uint64_t(s.jitter_us)) >> 64));
+#endif
+}
+
+// due(i, k) of a valid record with period_us > 0, for k >= 0 with k * period_us <= 2^62 (no overflow below that)
+RM_HD int64_t traffic_due(const rm_traffic_schedule &s, uint64_t seed, int32_t node, int64_t k)
+{
+    return s.phase_us + k * s.period_us + traffic_jitter(s, seed, node, k);
+}
+
+// The number of the node's packets with due < t (0 <= t <= 2^62; period_us > 0), which is also the number of the first packet
+// due at t or later, because due grows strictly with k.  With e = the last packet whose jitter interval BEGINS before t, every
+// packet before e is due before t (its interval ends before e's begins: jitter <= period), every one after e is not, and e
+// itself needs its hash only when its interval reaches t.  n is a lower bound of the answer the caller knows (0: nothing is
+// known -- the answer of an earlier time is one): up to one period behind packet n's interval no division is needed.
+RM_HD int64_t traffic_before(const rm_traffic_schedule &s, uint64_t seed, int32_t node, int64_t t, int64_t n)
+{
+    const int64_t period = s.period_us;
+    const int64_t base_n = s.phase_us + n * period;
+    if (t <= base_n) return n;
+    const int64_t e = (t - base_n <= period) ? n : (t - 1 - s.phase_us) / period;
+    const int64_t base = s.phase_us + e * period;
+    if (base + s.jitter_us <= t) return e + 1; // (the whole interval, base .. base + jitter - 1, lies before t; jitter 0: base < t)
+    return e + (base + traffic_jitter(s, seed, node, e) < t ? 1 : 0);
+}
+
 // Position.getDistance, Position.java:56-64: this = transmitter, p2 = receiver;
 // (dx*dx + dy*dy) + dz*dz, then a correctly rounded square root.
 RM_HD double ref_distance(double ax, double ay, double az, double bx, double by, double bz)

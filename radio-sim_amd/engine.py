@@ -389,6 +389,105 @@ class Engine:
         return int(_lib.lib().rm_linkstats_validate(int(n_nodes), int(K), None if idx is None else idx.ctypes.data,
                                                    n if idx is None else idx.shape[0], rows.ctypes.data))
 
+    # -- traffic schedules: periodic sources generated on the device
+    @staticmethod
+    def _traffic_table(sched):
+        """schedules as a contiguous TRAFFIC_SCHEDULE_DTYPE array: a structured array, or 2-D rows of (period_us, phase_us,
+        jitter_us[, reserved]); a 1-D sequence of three or four values is ONE record, an empty one is no record"""
+        a = np.asarray(sched)
+        if a.dtype != _lib.TRAFFIC_SCHEDULE_DTYPE:
+            rows = np.asarray(a, dtype=np.int64)
+            if rows.ndim == 1:
+                if rows.shape[0] not in (0, 3, 4):
+                    raise ValueError("a schedule is (period_us, phase_us, jitter_us); several schedules are 2-D rows")
+                rows = rows.reshape(-1, rows.shape[0] or 3)
+            rows = rows.reshape(-1, rows.shape[-1])
+            if rows.shape[1] == 3:
+                rows = np.concatenate([rows, np.zeros((rows.shape[0], 1), dtype=np.int64)], axis=1)
+            if rows.shape[1] != 4:
+                raise ValueError("a schedule is (period_us, phase_us, jitter_us)")
+            a = np.ascontiguousarray(rows).view(_lib.TRAFFIC_SCHEDULE_DTYPE).reshape(-1)
+        return np.ascontiguousarray(a.reshape(-1))
+
+    def traffic_set(self, sched, nodes=None):
+        """rm_traffic_set: sched for all nodes in node order, or for the listed nodes in list order (the last entry of a node wins);
+        switches the feature on"""
+        tbl = self._traffic_table(sched)
+        if nodes is None:
+            check(self._L.rm_traffic_set(self._h, None, tbl.shape[0], tbl.ctypes.data))
+        else:
+            idx = np.ascontiguousarray(nodes, dtype=np.int32)
+            if idx.shape[0] != tbl.shape[0]:
+                raise ValueError("one schedule per listed node")
+            check(self._L.rm_traffic_set(self._h, idx.ctypes.data, idx.shape[0], tbl.ctypes.data))
+
+    def traffic_get(self, nodes=None):
+        """rm_traffic_get: structured array of TRAFFIC_SCHEDULE_DTYPE (the listed nodes in list order, or all in node order)"""
+        if nodes is None:
+            out = np.zeros(max(int(self._L.rm_node_count(self._h)), 0), dtype=_lib.TRAFFIC_SCHEDULE_DTYPE)
+            check(self._L.rm_traffic_get(self._h, None, out.shape[0], out.ctypes.data))
+        else:
+            idx = np.ascontiguousarray(nodes, dtype=np.int32)
+            out = np.zeros(idx.shape[0], dtype=_lib.TRAFFIC_SCHEDULE_DTYPE)
+            check(self._L.rm_traffic_get(self._h, idx.ctypes.data, idx.shape[0], out.ctypes.data))
+        return out
+
+    def traffic_clear(self):
+        check(self._L.rm_traffic_clear(self._h))
+
+    def traffic_enabled(self):
+        return bool(self._L.rm_traffic_enabled(self._h))
+
+    def traffic_device(self):
+        """rm_traffic_device: device pointer of the schedules, [n_nodes] of 32-byte records"""
+        p = C.c_void_p()
+        check(self._L.rm_traffic_device(self._h, C.byref(p)))
+        return p.value
+
+    @staticmethod
+    def _traffic_windows(win_lo, win_hi):
+        lo, hi = np.ascontiguousarray(win_lo, dtype=np.int64).reshape(-1), np.ascontiguousarray(win_hi, dtype=np.int64).reshape(-1)
+        if lo.shape != hi.shape:
+            raise ValueError("one win_hi per win_lo")
+        return lo, hi
+
+    def traffic_generate(self, seed, win_lo, win_hi, cap):
+        """rm_traffic_generate: -> (rows int32[n_ticks][cap], ascending node indices padded with -1; count int32[n_ticks], the true
+        number of sources per window; totals {packets, coalesced, truncated})"""
+        lo, hi = self._traffic_windows(win_lo, win_hi)
+        rows = np.empty((lo.shape[0], max(int(cap), 0)), dtype=np.int32)
+        count = np.empty(lo.shape[0], dtype=np.int32)
+        tot = _lib.TrafficTotals()
+        check(self._L.rm_traffic_generate(self._h, int(seed) & (2 ** 64 - 1), lo.shape[0], lo.ctypes.data, hi.ctypes.data, int(cap),
+                                          rows.ctypes.data, count.ctypes.data, C.byref(tot)))
+        return rows, count, {"packets": tot.packets, "coalesced": tot.coalesced, "truncated": tot.truncated}
+
+    def traffic_generate_device(self, seed, win_lo, win_hi, cap, dev_src_ptr, dev_count_ptr, dev_totals_ptr=None):
+        """The raw form: device outputs (int32[n_ticks][cap], int32[n_ticks], one rm_traffic_totals or None), enqueued on the
+        context's stream without waiting; row b is a ready device source list at dev_src_ptr + 4 * b * cap."""
+        lo, hi = self._traffic_windows(win_lo, win_hi)
+        check(self._L.rm_traffic_generate_device(self._h, int(seed) & (2 ** 64 - 1), lo.shape[0], lo.ctypes.data, hi.ctypes.data, int(cap),
+                                                 dev_src_ptr, dev_count_ptr, dev_totals_ptr))
+
+    @staticmethod
+    def traffic_due(sched, seed, node, k):
+        """rm_traffic_due (pure host): the due time of packet k of `node`, None for period 0; sched = (period_us, phase_us, jitter_us).
+        Raises RadioMediumError for what the rule refuses."""
+        s = _lib.TrafficSchedule(*[int(v) for v in sched])
+        due = C.c_int64()
+        rc = int(_lib.lib().rm_traffic_due(C.byref(s), int(seed) & (2 ** 64 - 1), int(node), int(k), C.byref(due)))
+        if rc < 0:
+            raise _lib.RadioMediumError(rc, "rm_traffic_due: a bad record, node or packet number")
+        return due.value if rc == 1 else None
+
+    @staticmethod
+    def traffic_validate(n_nodes, sched, nodes=None):
+        """rm_traffic_validate (pure host): the return code of the validation rm_traffic_set runs (0: accepted)"""
+        tbl = Engine._traffic_table(sched)
+        idx = None if nodes is None else np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+        return int(_lib.lib().rm_traffic_validate(int(n_nodes), None if idx is None else idx.ctypes.data,
+                                                  tbl.shape[0] if idx is None else idx.shape[0], tbl.ctypes.data))
+
     # -- java.util.Random
     def seed(self, seed):
         check(self._L.rm_seed(self._h, seed))

@@ -644,6 +644,57 @@ public:
         }
         return out;
     }
+    // Traffic schedules (extension E15): a node with period_us > 0 has a packet due at phase_us + k period_us + jitter (a hash of
+    // seed, node and k below jitter_us) for k = 0, 1, ...; generateTraffic() gives, for every half-open window [win_lo[b],
+    // win_hi[b]) -- in time order, disjoint -- the nodes with a packet due in it, in the order of Simulator.getNodes(), computed on
+    // the device.  No call of the medium changes; period_us 0 (with the other values 0): the node generates nothing.  The schedules
+    // survive apply(); false and lastError on a refusal.
+    bool setTrafficSchedule(const Node &node, int64_t period_us, int64_t phase_us, int64_t jitter_us)
+    {
+        if (!syncNodes()) return false; // the device mirrors the node table first: the table has its size
+        const int32_t i = node.index;
+        const rm_traffic_schedule s = {period_us, phase_us, jitter_us, 0};
+        if (!restoreTrafficSchedules()) return false; // (a node table of another size has cleared the engine's table: all of them again)
+        if (rm_traffic_set(ctx_, &i, 1, &s) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        traffic_[i] = s;
+        return true;
+    }
+    bool clearTrafficSchedules()
+    {
+        traffic_.clear();
+        if (rm_traffic_clear(ctx_) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        return true;
+    }
+    bool getTrafficEnabled() const { return rm_traffic_enabled(ctx_) != 0; }
+    // sources[b]: the nodes of window b, at most cap of them (the first in node order); totals (may be nullptr): packets due,
+    // second and later packets of a node in one window, sources beyond cap
+    bool generateTraffic(uint64_t seed, const std::vector<int64_t> &win_lo, const std::vector<int64_t> &win_hi, int32_t cap,
+                         std::vector<std::vector<Node *>> &sources, rm_traffic_totals *totals = nullptr)
+    {
+        sources.clear();
+        if (!simulator || !syncNodes() || !restoreTrafficSchedules()) return false;
+        if (win_lo.size() != win_hi.size() || win_lo.empty() || cap < 1) {
+            lastError = "generateTraffic: one win_hi per win_lo, one window at least, cap >= 1";
+            return false;
+        }
+        const int32_t n_ticks = int32_t(win_lo.size());
+        std::vector<int32_t> rows(win_lo.size() * size_t(cap)), count(win_lo.size());
+        if (rm_traffic_generate(ctx_, seed, n_ticks, win_lo.data(), win_hi.data(), cap, rows.data(), count.data(), totals) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        const std::vector<Node *> &nodes = simulator->getNodes();
+        sources.resize(win_lo.size());
+        for (size_t b = 0; b < win_lo.size(); ++b)
+            for (int32_t k = 0; k < std::min(count[b], cap); ++k) sources[b].push_back(nodes[size_t(rows[b * size_t(cap) + size_t(k)])]);
+        return true;
+    }
     // Watched-link statistics (extension E14): per-link counters for a node's routing parent and a handful of candidate parents.
     // setLinkWatch(K) gives every node K slots of watched peers (K = 1, 2, 4 or 8; 0 switches the feature off); watchLinks(node,
     // peers) fills the node's slots (nullptr: an empty slot; fewer than K peers: the rest empty) -- a slot whose peer stays keeps
@@ -738,6 +789,27 @@ protected:
         restoreListenSchedules();
         // (nor are the watched links)
         restoreLinkWatch();
+        // (nor are the traffic schedules)
+        restoreTrafficSchedules();
+    }
+    // the traffic schedules the medium set, set again where the engine has dropped them (a node table of another size clears its
+    // table), as far as their nodes still exist; false and lastError on a refusal
+    bool restoreTrafficSchedules()
+    {
+        if (traffic_.empty() || rm_traffic_enabled(ctx_)) return true;
+        std::vector<int32_t> idx;
+        std::vector<rm_traffic_schedule> recs;
+        const int32_t n = rm_node_count(ctx_);
+        for (const auto &kv : traffic_)
+            if (kv.first < n) {
+                idx.push_back(kv.first);
+                recs.push_back(kv.second);
+            }
+        if (!idx.empty() && rm_traffic_set(ctx_, idx.data(), int32_t(idx.size()), recs.data()) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        return true;
     }
     // K and the watch rows the medium set, set again where the engine has dropped them (a node table of another size switches the
     // feature off), as far as their nodes still exist; false and lastError on a refusal
@@ -784,6 +856,7 @@ protected:
     }
     bool statistics_ = false; // what setStatistics set last, kept across apply()
     std::map<int32_t, rm_listen_schedule> listen_; // what setListenSchedule set, by node index, kept across apply()
+    std::map<int32_t, rm_traffic_schedule> traffic_; // what setTrafficSchedule set, by node index, kept across apply()
     int linkWatchK_ = 0;                                // what setLinkWatch set last, kept across apply()
     std::map<int32_t, std::vector<int32_t>> linkWatch_; // what watchLinks set: K peers by node index, kept across apply()
     rm_context *ctx_ = nullptr;
