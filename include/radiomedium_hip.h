@@ -957,6 +957,50 @@ int rm_traffic_due(const rm_traffic_schedule *s, uint64_t seed, int32_t node, in
 /* the validation of rm_traffic_set alone, a pure host function without a device: RM_OK or RM_ERR_INVALID */
 int rm_traffic_validate(int32_t n_nodes, const int32_t *nodes, int32_t n, const rm_traffic_schedule *sched);
 
+/* ---- neighbour query: each node's K strongest potential links on the device -------------------------------------------
+ * (not reference behaviour.)  A pure function of the node table and the model, on
+ * RM_MODEL_LOGDIST only (with or without RM_LD_SINR; the flag plays no part): the reference's media report the frame's txpower as
+ * every link's rssi, a ranking by it says nothing there.
+ * The potential link s -> r exists iff r != s, r's radio is enabled, r's channel is s's, !(rxprob_r <= 0) and rssi >=
+ * sensitivity_dbm, rssi being the log-distance medium's value (shadowing included) for the Tx record rm_tick_run_sources_device
+ * builds for s from the table: exactly the heard links of a lone tick whose only source is s, with their rssi bit for bit.  A NaN
+ * rssi is no link; s's enabled flag and txprob and every verdict-side quantity play no part.
+ * Link a precedes link b iff rssi_a > rssi_b, or rssi_a == rssi_b (as doubles) and a's far end has the lower node index.
+ * RM_NB_HEARD_BY: the queried node j transmits, its row holds the receivers that hear it best.  RM_NB_HEARS: j receives, its row
+ * holds the transmitters it hears best, each with its own table txpower -- the row a watch of rm_linkstats wants.
+ * Per queried entry e, with 1 <= K <= RM_NB_MAX_K: peer[e][0 .. K) the far ends of the first K links in that order, padded with -1;
+ * rssi[e][0 .. K) those links' rssi, the NaN 0x7FF8000000000000 beside a -1 (may be NULL); degree[e] the number of ALL potential
+ * links of j in that direction, not capped at K (may be NULL).  Nothing is changed by a query. */
+#define RM_NB_HEARD_BY 0
+#define RM_NB_HEARS 1
+#define RM_NB_MAX_K 16
+/* Enqueued on the context's stream without waiting for it; all arrays are device memory.  dev_nodes == NULL: all nodes in index
+ * order, n has to be the node count; otherwise entry e is node dev_nodes[e], and an entry outside 0 .. n_nodes - 1 gives a row of -1
+ * and degree 0 and disturbs nothing else.  RM_ERR_STATE, nothing launched: another medium than RM_MODEL_LOGDIST, between
+ * rm_tick_begin and rm_tick_flush, a context with a receiver partition, a context made under RM_GRAPH=1.  RM_ERR_INVALID: NULL ctx
+ * or dev_peer, K outside 1 .. RM_NB_MAX_K, an unknown direction, n < 0, dev_nodes == NULL with n != n_nodes.  RM_ERR_CAPACITY:
+ * n * K above 2^27.  n == 0 is RM_OK. */
+int rm_neighbors_query_device(rm_context *ctx, int32_t direction, int32_t K, const int32_t *dev_nodes, int32_t n, int32_t *dev_peer,
+                              double *dev_rssi, int32_t *dev_degree);
+/* the same with host arrays; a node index outside the table is RM_ERR_INVALID before anything is launched.  Synchronises once. */
+int rm_neighbors_query(rm_context *ctx, int32_t direction, int32_t K, const int32_t *nodes, int32_t n, int32_t *peer, double *rssi,
+                       int32_t *degree);
+/* The same order applied to the heard links of the first n_pkt packets of one tick's host result, a pure host function without a
+ * device: peer / rssi [n_pkt][K], degree [n_pkt] (rssi and degree may be NULL).  These are the RM_NB_HEARD_BY rows of the packets'
+ * sources when every packet is a distinct source alone in its tick's channel.  RM_ERR_INVALID: NULL r or peer, K outside
+ * 1 .. RM_NB_MAX_K, n_pkt < 0 or above r->n_packets, a result with links but without pkt_offset, dst or an rssi column. */
+int rm_neighbors_from_result(const rm_host_result *r, int32_t n_pkt, int32_t K, int32_t *peer, double *rssi, int32_t *degree);
+/* rm_linkstats_watch with the list and the rows in device memory (dev_nodes == NULL: all nodes, n has to be the node count;
+ * dev_peers n x K of the enabled K): rm_linkstats_validate's rules are checked by one launch on the device and its flag is waited
+ * for -- RM_ERR_INVALID with nothing changed -- then the rows are applied as rm_linkstats_watch applies them.  An RM_NB_HEARS
+ * result with the same K is valid by construction.  RM_ERR_STATE while the feature is off. */
+int rm_linkstats_watch_device(rm_context *ctx, const int32_t *dev_nodes, int32_t n, const int32_t *dev_peers);
+/* a block of device memory the context owns with room for n_nodes x K rows, for a caller without a device allocator of its own:
+ * rm_neighbors_query_device writes there, rm_linkstats_watch_device reads from there.  Valid until the feature is switched off or
+ * enabled with another K, another node count or rm_destroy; a whole-table rm_linkstats_watch overwrites it.  RM_ERR_STATE while
+ * the feature is off. */
+int rm_linkstats_stage_device(rm_context *ctx, int32_t **dev_rows);
+
 /* ---- several devices behind one caller --------------------------------------------------------------
  * The reference host is ONE process (Main.java:65-73): a group drives n contexts from one host thread, one
  * per device (an ordinal may repeat: several partitions on one GPU).  Receivers are partitioned over the

@@ -70,6 +70,8 @@ class UnicastOut(C.Structure):
 
 UC_NONE, UC_NOT_SENT, UC_UNHEARD, UC_INTERFERED, UC_DELIVERED, UC_LOST = 0, 1, 2, 3, 4, 5
 UNICAST_FIELDS = (("status", np.uint8), ("link", np.int32), ("rssi", np.float64), ("sinr", np.float64), ("reply_src", np.int32))
+# the neighbour query: directions, the largest K
+NB_HEARD_BY, NB_HEARS, NB_MAX_K = 0, 1, 16
 
 NODE_STATS_DTYPE = np.dtype([(name, "<u8") for name, _ in NodeStats._fields_])
 assert NODE_STATS_DTYPE.itemsize == C.sizeof(NodeStats) == 64
@@ -376,6 +378,11 @@ SIGNATURES = {
     "rm_traffic_generate": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rm_traffic_due": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
     "rm_traffic_validate": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "rm_neighbors_query_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_neighbors_query": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_neighbors_from_result": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_linkstats_watch_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "rm_linkstats_stage_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "rm_det_math": (C.c_double, [C.c_int32, C.c_double]),
     "rm_link_hash": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
     "rm_evq_init": (None, [C.c_void_p]),

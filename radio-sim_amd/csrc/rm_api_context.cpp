@@ -329,6 +329,7 @@ void rm_destroy(rm_context *c)
     c->ls.h_block = nullptr;
     traffic_release(c);
     linkstats_release(c);
+    neighbors_release(c);
     c->uc.d_desc.release(); c->uc.d_io.release();
     for (int g = 0; g < 2; ++g) {
         if (c->uc.h_ev[g]) (void)hipEventDestroy(c->uc.h_ev[g]);

@@ -37,10 +37,25 @@ int linkstats_check(const rm_context *c, bool gathered)
 void linkstats_release(rm_context *c)
 {
     rm_context::LinkStats &lk = c->lk;
-    lk.peer.release(); lk.stage.release(); lk.table.release(); lk.totals.release();
+    lk.peer.release(); lk.stage.release(); lk.table.release(); lk.totals.release(); lk.mark.release();
     if (lk.h_block) (void)hipHostFree(lk.h_block);
     lk.h_block = nullptr;
     lk.h_cap = 0;
+    if (lk.h_bad) (void)hipHostFree(lk.h_bad);
+    lk.h_bad = nullptr;
+    lk.host_stale = false;
+}
+
+int linkstats_host_fresh(rm_context *c)
+{
+    rm_context::LinkStats &lk = c->lk;
+    if (!lk.host_stale) return RM_OK;
+    if (!lk.host.empty()) {
+        RM_HIP(hipMemcpyAsync(lk.host.data(), lk.peer.p, lk.host.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        RM_HIP(hipStreamSynchronize(c->stream));
+    }
+    lk.host_stale = false;
+    return RM_OK;
 }
 
 // off: nothing is launched afterwards, the tables released (pointers handed out end here)
@@ -139,6 +154,8 @@ int rm_linkstats_watch(rm_context *c, const int32_t *nodes, int32_t n, const int
     RM_TRY(rm_linkstats_validate(lk.n, lk.K, nodes, n, peers));
     if (n == 0) return RM_OK;
     RM_HIP(hipSetDevice(c->device));
+    if (nodes) RM_TRY(linkstats_host_fresh(c)); // (a list updates rows of the host's copy; the whole table replaces it)
+    else lk.host_stale = false;
     const size_t K = size_t(lk.K);
     if (!nodes) {
         // the whole table: staged in device memory from the host's copy, and waited for -- a later update of the copy cannot race
@@ -167,6 +184,10 @@ int rm_linkstats_peers_get(rm_context *c, const int32_t *nodes, int32_t n, int32
     RM_TRY(linkstats_have(c));
     const rm_context::LinkStats &lk = c->lk;
     RM_TRY(linkstats_check_list(nodes, n, lk.n));
+    if (lk.host_stale) {
+        RM_HIP(hipSetDevice(c->device));
+        RM_TRY(linkstats_host_fresh(c));
+    }
     const size_t K = size_t(lk.K);
     for (int32_t r = 0; r < n; ++r) std::memcpy(out + size_t(r) * K, lk.host.data() + size_t(nodes ? nodes[r] : r) * K, K * 4);
     return RM_OK;

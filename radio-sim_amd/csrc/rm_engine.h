@@ -948,6 +948,25 @@ hipError_t launch_traffic_gather(hipStream_t s, const rm_traffic_schedule *table
 bool host_traffic_valid(const rm_traffic_schedule &s);
 int64_t host_traffic_due(const rm_traffic_schedule &s, uint64_t seed, int32_t node, int64_t k);
 
+// (rm_neighbors.hip) the neighbour query: one wave per queried entry.  list == nullptr: all
+// nodes, entry e is the node at engine position e and its row is the node's (n == n_nodes == n_rx); otherwise entry e is node
+// list[e] and row e (an entry outside the table: an empty row).  RM_NB_HEARS reads what k_nb_prep, launched in front of it, leaves
+// in prep (two words, zeroed by the caller on the stream) and off_list ([n_nodes]).  scan: every pair is evaluated exactly, no box
+// is read.
+struct NbDev {
+    const int32_t *list;
+    int n, K;
+    unsigned long long *prep;
+    int32_t *off_list;
+    int32_t *peer;    // [rows][K]
+    uint64_t *rssi;   // [rows][K] the links' rssi bits, or nullptr
+    int32_t *degree;  // [rows], or nullptr
+};
+hipError_t launch_nb_query(hipStream_t s, const NodesDev &nd, const ModelDev &m, const NbDev &q, int direction, bool scan);
+// rm_linkstats_validate's rules over rows in device memory (rm_linkstats_watch_device): *bad becomes 1 if one is broken
+hipError_t launch_nb_watch_check(hipStream_t s, const int32_t *nodes, int n, const int32_t *peers, int n_nodes, int K, uint32_t *mark, uint32_t stamp,
+                                 uint32_t *bad);
+
 // (rm_unicast.hip) the unicast outcome query, one launch: a lane per entry.  n_slots result slots described by dev_slots -- or, with
 // dev_slots == nullptr, the one slot `lone`.  Slots form (dev_prefix: [n_slots + 1] exclusive prefix of the entries per slot; nullptr
 // with one slot): entry e is packet e - prefix[b] of slot b.  At form: entry e names (dev_slot[e], dev_pkt[e]).

@@ -181,7 +181,19 @@ struct rm_context : TickSlot {
         DevBuf<rm_stats_totals> totals;
         char *h_block = nullptr;
         size_t h_cap = 0; // rows the block has room for
+        // rm_linkstats_watch_device (rm_api_neighbors.cpp): the rows never pass through the host, so its copy is refreshed from the
+        // device's table when somebody next reads it; the validation's per-node marks, its stamp and its pinned flag word
+        bool host_stale = false;
+        DevBuf<uint32_t> mark;
+        uint32_t stamp = 0;
+        uint32_t *h_bad = nullptr;
     } lk;
+    // the neighbour query (E16; rm_api_neighbors.cpp, rm_neighbors.hip): what a RM_NB_HEARS query gathers from the table per call --
+    // two words (the largest txpower, the number of radios that are off) and the list of those nodes
+    struct Neighbors {
+        DevBuf<unsigned long long> prep;
+        DevBuf<int32_t> off_list;
+    } nb;
     // traffic schedules (E15; rm_api_traffic.cpp, rm_traffic.hip): one schedule per node index; the pinned, host-mapped block a list
     // update or a list read is staged through; the generator's scratch (the windows, the units' counts and packets) and the pinned
     // staging of its windows -- two blocks, each rewritten only after its copy has completed
@@ -737,6 +749,12 @@ int linkstats_check(const rm_context *c, bool gathered);
 int linkstats_nodes_changed(rm_context *c);
 // rm_destroy: the tables and the host block
 void linkstats_release(rm_context *c);
+// the host's copy of the peer rows, read back from the device if rm_linkstats_watch_device has written the table since
+int linkstats_host_fresh(rm_context *c);
+
+// ---- rm_api_neighbors.cpp: the neighbour query (E16)
+// rm_destroy
+void neighbors_release(rm_context *c);
 
 // ---- rm_api_traffic.cpp: traffic schedules (E15)
 // rm_nodes_upload: another node count clears the feature

@@ -488,6 +488,80 @@ class Engine:
         return int(_lib.lib().rm_traffic_validate(int(n_nodes), None if idx is None else idx.ctypes.data,
                                                   tbl.shape[0] if idx is None else idx.shape[0], tbl.ctypes.data))
 
+    # -- neighbour query: each node's K strongest potential links
+    NB_HEARD_BY, NB_HEARS, NB_MAX_K = _lib.NB_HEARD_BY, _lib.NB_HEARS, _lib.NB_MAX_K
+
+    @staticmethod
+    def _neighbors_out(n, K, fields):
+        """host arrays for n rows -> {name: array}; fields: the optional outputs asked for (None: rssi and degree)"""
+        out = {"peer": np.empty((n, max(int(K), 0)), dtype=np.int32)}
+        if fields is None or "rssi" in fields:
+            out["rssi"] = np.empty((n, max(int(K), 0)), dtype=np.float64)
+        if fields is None or "degree" in fields:
+            out["degree"] = np.empty(n, dtype=np.int32)
+        return out
+
+    def neighbors(self, direction, K, nodes=None, fields=None):
+        """rm_neighbors_query: the first K potential links of the listed nodes (None: all nodes in node order), ranked by rssi
+        descending, then by node index -> {"peer": int32[n][K] padded with -1, "rssi": float64[n][K] (NaN beside a -1), "degree":
+        int32[n], all potential links}.  direction NB_HEARD_BY: the node transmits; NB_HEARS: it receives."""
+        idx = None if nodes is None else np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+        n = max(int(self._L.rm_node_count(self._h)), 0) if idx is None else idx.shape[0]
+        out = self._neighbors_out(n, K, fields)
+        check(self._L.rm_neighbors_query(self._h, int(direction), int(K), _ptr(idx), n, out["peer"].ctypes.data, _ptr(out.get("rssi")),
+                                         _ptr(out.get("degree"))))
+        return out
+
+    def neighbors_device(self, direction, K, dev_peer_ptr, dev_rssi_ptr=None, dev_degree_ptr=None, dev_nodes_ptr=None, n=None):
+        """rm_neighbors_query_device: the raw form -- device outputs (int32[n][K], float64[n][K] or None, int32[n] or None), the list
+        in device memory (None: all nodes, n the node count); enqueued on the context's stream without waiting"""
+        if n is None:
+            if dev_nodes_ptr is not None:
+                raise ValueError("a device list needs its length")
+            n = int(self._L.rm_node_count(self._h))
+        check(self._L.rm_neighbors_query_device(self._h, int(direction), int(K), dev_nodes_ptr, int(n), dev_peer_ptr, dev_rssi_ptr, dev_degree_ptr))
+
+    @staticmethod
+    def neighbors_from_result(result, K, n_pkt=None, fields=None):
+        """rm_neighbors_from_result (pure host function): the same order over the heard links of each packet of one tick's host
+        result -- a _lib.HostResult, or anything with count, pkt_offset, dst and rssi or pkt_rssi, e.g. what tick_flush_view returns"""
+        keep = []
+        if isinstance(result, HostResult):
+            r = result
+        else:
+            def col(name, dt):
+                a = getattr(result, name, None)
+                if a is None:
+                    return None
+                a = np.ascontiguousarray(a, dtype=dt)
+                keep.append(a)
+                return a.ctypes.data
+            off = np.ascontiguousarray(result.pkt_offset, dtype=np.uint32)
+            keep.append(off)
+            rssi = col("rssi", np.float64)
+            r = HostResult(count=int(result.count), n_packets=len(off) - 1, pkt_offset=off.ctypes.data, dst=col("dst", np.int32),
+                           rssi=rssi, pkt_rssi=None if rssi is not None else col("pkt_rssi", np.float64))
+        n = int(r.n_packets) if n_pkt is None else int(n_pkt)
+        out = Engine._neighbors_out(max(n, 0), K, fields)
+        check(_lib.lib().rm_neighbors_from_result(C.byref(r), n, int(K), out["peer"].ctypes.data, _ptr(out.get("rssi")), _ptr(out.get("degree"))))
+        return out
+
+    def linkstats_watch_device(self, dev_peers_ptr, dev_nodes_ptr=None, n=None):
+        """rm_linkstats_watch_device: rm_linkstats_watch with rows (int32[n][K] of the enabled K) and list in device memory (None: all
+        nodes) -- e.g. the peer block of neighbors_device(NB_HEARS, K); validated on the device, waited for"""
+        if n is None:
+            if dev_nodes_ptr is not None:
+                raise ValueError("a device list needs its length")
+            n = int(self._L.rm_node_count(self._h))
+        check(self._L.rm_linkstats_watch_device(self._h, dev_nodes_ptr, int(n), dev_peers_ptr))
+
+    def linkstats_stage_device(self):
+        """rm_linkstats_stage_device: device pointer of a block the context owns with room for n_nodes x K rows (a caller without a
+        device allocator chains neighbors_device -> linkstats_watch_device through it)"""
+        p = C.c_void_p()
+        check(self._L.rm_linkstats_stage_device(self._h, C.byref(p)))
+        return p.value
+
     # -- java.util.Random
     def seed(self, seed):
         check(self._L.rm_seed(self._h, seed))

@@ -981,6 +981,64 @@ public:
             lastError = rm_last_error();
         }
     }
+    // The neighbour query (extension E16): each listed node's K strongest potential links (1 <= K <= RM_NB_MAX_K), ranked by rssi,
+    // ties by node index.  RM_NB_HEARD_BY: the receivers that hear the node best; RM_NB_HEARS: the transmitters it hears best, each
+    // with its own txpower.  No list: all nodes in node order.  degree counts all potential links, not only the K listed.  Empty and
+    // lastError on a refusal.
+    struct NeighborRow {
+        std::vector<Node *> peers; // at most K, strongest first
+        std::vector<double> rssi;  // by the same index
+        int degree;
+    };
+    std::vector<NeighborRow> neighbors(int direction, int K, const std::vector<const Node *> &nodes = {})
+    {
+        lastError.clear();
+        if (!simulator || !syncNodes()) return {};
+        const std::vector<Node *> &all = simulator->getNodes();
+        std::vector<int32_t> idx;
+        for (const Node *nd : nodes) idx.push_back(nd ? nd->index : -1);
+        const size_t n = nodes.empty() ? all.size() : nodes.size();
+        const size_t k = size_t(K > 0 ? K : 0);
+        std::vector<int32_t> peer(n * k + 1), degree(n + 1);
+        std::vector<double> rssi(n * k + 1);
+        if (rm_neighbors_query(ctx_, int32_t(direction), int32_t(K), nodes.empty() ? nullptr : idx.data(), int32_t(n), peer.data(), rssi.data(),
+                               degree.data()) != RM_OK) {
+            lastError = rm_last_error();
+            return {};
+        }
+        std::vector<NeighborRow> rows(n);
+        for (size_t e = 0; e < n; ++e) {
+            rows[e].degree = degree[e];
+            for (size_t s = 0; s < k && peer[e * k + s] >= 0; ++s) {
+                rows[e].peers.push_back(all[size_t(peer[e * k + s])]);
+                rows[e].rssi.push_back(rssi[e * k + s]);
+            }
+        }
+        return rows;
+    }
+    // Topology discovery into the watched links (E16 -> E14) without a link passing through the host: setLinkWatch(K) (K = 1, 2, 4
+    // or 8), every node's RM_NB_HEARS row computed into the engine's staging block, taken as the watch rows on the device.  The
+    // mirror then reads the rows back once, so that they survive apply() like rows set by watchLinks.  false and lastError on a refusal.
+    bool watchStrongest(int K)
+    {
+        if (!simulator || !setLinkWatch(K)) return false;
+        if (K <= 0) return true;
+        const int32_t n = rm_node_count(ctx_);
+        int32_t *rows = nullptr;
+        if (rm_linkstats_stage_device(ctx_, &rows) != RM_OK || rm_neighbors_query_device(ctx_, RM_NB_HEARS, int32_t(K), nullptr, n, rows, nullptr, nullptr) != RM_OK ||
+            rm_linkstats_watch_device(ctx_, nullptr, n, rows) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        std::vector<int32_t> host(size_t(n) * size_t(K));
+        if (n > 0 && rm_linkstats_peers_get(ctx_, nullptr, n, host.data()) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        linkWatch_.clear();
+        for (int32_t i = 0; i < n; ++i) linkWatch_[i] = std::vector<int32_t>(host.begin() + size_t(i) * size_t(K), host.begin() + size_t(i + 1) * size_t(K));
+        return true;
+    }
     // The frame error model (extension E10; needs setSinr(true)): with RM_EM_OQPSK_250K a delivered link survives with the packet
     // success ratio of its SINR and its air time.  The verdicts come out of the engine, so transmit(), transmitIfClear(), the tick
     // mode and transmitCsmaBatch() deliver and interfere accordingly and their generateReceptionEvents calls carry the new verdict.
