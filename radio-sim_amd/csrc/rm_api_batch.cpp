@@ -233,8 +233,7 @@ int rmh::launch_batch(rm_context *c, TickSlot *const *slots, const TickPlan *pla
     // of such a slot take)
     // (nor with the traffic counters, the listening schedules or the watched-link statistics on: their one launch reads every slot's
     // compact arrays, which this form leaves for later)
-    if (batch_frames && !cfg.stochastic && !plans[0].sinr && !after_sweep && !(rank_frames && ticks[0].n_pub > 0) && !stats_on(c) && !listen_on(c) &&
-        !linkstats_on(c)) {
+    if (batch_frames && !cfg.stochastic && !plans[0].sinr && !after_sweep && !(rank_frames && ticks[0].n_pub > 0) && !passes_counting(c)) {
         int seg_len = rm::frame_tick_segment(ticks[0], cfg, m);
         for (int b = 1; b < n && seg_len > 0; ++b) seg_len = std::min(seg_len, rm::frame_tick_segment(ticks[b], cfg, m));
         if (seg_len > 0) {
@@ -277,29 +276,7 @@ int rmh::launch_batch(rm_context *c, TickSlot *const *slots, const TickPlan *pla
         RM_TRY(stage(RM_STAGE_SINR));
         RM_TRY(after_sweep(c, after_arg));
     }
-    if (em_on(c) && is_sinr(c)) {
-        // the frame error model (E10): every verdict of the batch is final here (the draws, the interference stages of a batch of
-        // overlapping ticks); ONE launch over all slots, ahead of everything that reads them (result copies, the packing launch of
-        // rm_batch_result_view, rm_events_process_batch)
-        RM_TRY(stage(RM_STAGE_SINR));
-        RM_HIP(rm::launch_errmodel_batch(s, em_dev(c), n, dev_ticks));
-    }
-    if (listen_on(c)) {
-        // the listening schedules (E13): behind the frame error model's pass, ahead of the traffic counters'; ONE launch over all slots
-        RM_TRY(stage(RM_STAGE_REORDER));
-        RM_HIP(rm::launch_listen_batch(s, listen_dev(c), n, dev_ticks));
-    }
-    if (stats_on(c)) {
-        // the traffic counters (E11): behind the frame error model's pass, so they count the verdicts every reader sees; ONE
-        // launch over all slots
-        RM_TRY(stage(RM_STAGE_REORDER));
-        RM_HIP(rm::launch_stats_batch(s, stats_dev(c), n, dev_ticks));
-    }
-    if (linkstats_on(c)) {
-        // the watched-link statistics (E14): behind the traffic counters' pass, reading what it reads; ONE launch over all slots
-        RM_TRY(stage(RM_STAGE_REORDER));
-        RM_HIP(rm::launch_linkstats_batch(s, linkstats_dev(c), n, dev_ticks));
-    }
+    RM_TRY(passes_batch(c, n, dev_ticks, smp, RM_STAGE_REORDER));
     for (int b = 0; b < n; ++b) {
         slots[b]->have_result = true;
         slots[b]->compact_pending = false;
@@ -321,10 +298,7 @@ int rmh::batch_run(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us, co
         (!dev_src && !dev_new && !any_gathered) || ((dev_src || gathered_idx) && (!start_us || !air_us)) ||
         (any_gathered && (gather_world < 1 || gather_slots < 1)))
         return fail(RM_ERR_INVALID, "bad arguments");
-    RM_TRY(em_check(c, any_gathered)); // (the frame error model: refused before anything is planned or the window moves)
-    RM_TRY(stats_check(c, any_gathered)); // (the traffic counters: likewise)
-    RM_TRY(listen_check(c, any_gathered)); // (the listening schedules: likewise)
-    RM_TRY(linkstats_check(c, any_gathered)); // (the watched-link statistics: likewise)
+    RM_TRY(passes_check(c, any_gathered, true)); // (refused before anything is planned or the window moves)
     static thread_local std::vector<int32_t> n_gath;
     if (any_gathered) {
         n_gath.assign(size_t(n_ticks), gather_world * gather_slots);
@@ -475,10 +449,9 @@ int rmh::batch_run(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us, co
     // empty ticks): the same ticks, one launch sequence each
     parity.dismiss();
     for (int b = 0; b < n_ticks; ++b) RM_TRY(launch_tick(c, *slots[b], plans[b], false));
-    const bool em_pass = em_on(c) && sinr;
-    if (em_pass || stats_on(c) || listen_on(c) || linkstats_on(c)) {
-        // the frame error model, the listening schedules, the traffic counters and the watched-link statistics over the ticks that
-        // were launched one by one: their compact arrays, the descriptors stored once, then one pass each over all of them (in this order)
+    if (passes_any(c)) {
+        // the passes over the ticks that were launched one by one: their compact arrays, the descriptors stored once, then one pass
+        // each over all of them
         static thread_local std::vector<rm::TickDev> em_ticks;
         em_ticks.clear();
         for (int b = 0; b < n_ticks; ++b) {
@@ -493,10 +466,7 @@ int rmh::batch_run(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us, co
             sample_stage(probe.smp, RM_STAGE_SINR);
             RM_HIP(c->d_ticks.ensure(RM_MAX_BATCH));
             RM_HIP(rm::launch_store_ticks(c->stream, em_ticks.data(), int(em_ticks.size()), c->d_ticks.p));
-            if (em_pass) RM_HIP(rm::launch_errmodel_batch(c->stream, em_dev(c), int(em_ticks.size()), c->d_ticks.p));
-            if (listen_on(c)) RM_HIP(rm::launch_listen_batch(c->stream, listen_dev(c), int(em_ticks.size()), c->d_ticks.p));
-            if (stats_on(c)) RM_HIP(rm::launch_stats_batch(c->stream, stats_dev(c), int(em_ticks.size()), c->d_ticks.p));
-            if (linkstats_on(c)) RM_HIP(rm::launch_linkstats_batch(c->stream, linkstats_dev(c), int(em_ticks.size()), c->d_ticks.p));
+            RM_TRY(passes_batch(c, int(em_ticks.size()), c->d_ticks.p, probe.smp, RM_STAGE_SINR));
         }
     }
     return RM_OK;

@@ -229,10 +229,7 @@ int rm_dist_batch_run_sources_device(rm_context *c, int32_t n_ticks, const int64
 {
     if (!c || n_ticks < 1 || n_ticks > RM_MAX_BATCH || slots < 1 || !dev_src || !start_us || !t_begin_us || !t_end_us || air_us < 0)
         return fail(RM_ERR_INVALID, "bad arguments");
-    RM_TRY(em_check(c, true)); // (the frame error model: refused before the all-gather)
-    RM_TRY(stats_check(c, true)); // (the traffic counters: likewise)
-    RM_TRY(listen_check(c, true)); // (the listening schedules: likewise)
-    RM_TRY(linkstats_check(c, true)); // (the watched-link statistics: likewise)
+    RM_TRY(passes_check(c, true, true)); // (refused before the all-gather)
     RM_HIP(hipSetDevice(c->device));
     // the all-gather carries the source INDICES (4 bytes per frame): every rank has the whole node table and builds the
     // records of all ranks' frames itself -- so the tables have to agree: each rank's block ends with its table's digest
@@ -250,10 +247,7 @@ int rm_dist_tick_run_sources_device(rm_context *c, int64_t t_begin_us, int64_t t
                                     int64_t start_us, int64_t air_us)
 {
     if (!c || slots < 1 || !dev_src || air_us < 0) return fail(RM_ERR_INVALID, "bad arguments");
-    RM_TRY(em_check(c, true)); // (the frame error model: refused before the records are packed and gathered)
-    RM_TRY(stats_check(c, true)); // (the traffic counters: likewise)
-    RM_TRY(listen_check(c, true)); // (the listening schedules: likewise)
-    RM_TRY(linkstats_check(c, true)); // (the watched-link statistics: likewise)
+    RM_TRY(passes_check(c, true, true)); // (refused before the records are packed and gathered)
     RM_HIP(hipSetDevice(c->device));
     const int world = c->comm ? c->comm_world : 1;
     const int32_t *all = dev_src;

@@ -323,20 +323,12 @@ void rm_destroy(rm_context *c)
         if (o.h_flag) (void)hipHostFree(o.h_flag);
     }
     c->ed.cnt.release(); c->ed.tx_mark.release(); c->ed.bucket_f.release(); c->ed.every_f.release(); c->ed.bucket_m.release(); c->ed.every_m.release(); c->ed.gated.release();
-    c->st.table.release(); c->st.totals.release();
-    c->ls.sched.release(); c->ls.missed.release();
-    if (c->ls.h_block) (void)hipHostFree(c->ls.h_block);
-    c->ls.h_block = nullptr;
-    traffic_release(c);
-    linkstats_release(c);
-    neighbors_release(c);
+    passes_release(c);
     c->uc.d_desc.release(); c->uc.d_io.release();
     for (int g = 0; g < 2; ++g) {
         if (c->uc.h_ev[g]) (void)hipEventDestroy(c->uc.h_ev[g]);
         if (c->uc.h_desc[g]) (void)hipHostFree(c->uc.h_desc[g]);
     }
-    if (c->st.h_block) (void)hipHostFree(c->st.h_block);
-    c->st.h_block = nullptr;
     if (c->ed.h_block) (void)hipHostFree(c->ed.h_block);
     c->ed.h_block = nullptr;
     c->ed.cb.release_all();

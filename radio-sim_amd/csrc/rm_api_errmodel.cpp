@@ -13,17 +13,6 @@ rm::EmDev em_dev(const rm_context *c)
     return d;
 }
 
-int em_check(const rm_context *c, bool gathered)
-{
-    if (!em_on(c)) return RM_OK;
-    if (gathered)
-        return fail(RM_ERR_STATE, "the frame error model is on: the gathered, rm_dist_* and rm_group_* forms do not run its pass "
-                                  "(rm_set_error_model with RM_EM_NONE switches it off)");
-    if (part_spatial(c) || part_count(c) != c->n)
-        return fail(RM_ERR_STATE, "the frame error model is on: a context with a receiver partition does not run its pass");
-    return RM_OK;
-}
-
 } // namespace rmh
 
 static int em_validate(const rm_error_model *e)
@@ -50,8 +39,7 @@ int rm_set_error_model(rm_context *c, const rm_error_model *e)
     if (!c || !e) return fail(RM_ERR_INVALID, "NULL argument");
     if (!is_sinr(c)) return fail(RM_ERR_STATE, "the frame error model needs RM_MODEL_LOGDIST with RM_LD_SINR: only that medium has a link's sinr");
     RM_TRY(em_validate(e));
-    if (e->kind != RM_EM_NONE && c->use_graphs)
-        return fail(RM_ERR_STATE, "this context replays its ticks from captured graphs (RM_GRAPH=1): the error model's pass is not part of them");
+    if (e->kind != RM_EM_NONE) RM_TRY(graphs_refuse(c, "the error model's pass is not part of them"));
     RM_TRY(ev_flush_append(c)); // (the tick before was evaluated without the new model: its append does not wait for the next drain)
     ev_touch(c);
     c->em = *e;

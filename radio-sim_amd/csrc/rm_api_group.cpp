@@ -286,10 +286,7 @@ int rm_group_tick_run_sources_device(rm_group *g, int64_t t_begin_us, int64_t t_
                                      int64_t start_us, int64_t air_us)
 {
     if (!g || !dev_src || slots < 1 || air_us < 0) return fail(RM_ERR_INVALID, "bad arguments");
-    for (rm_context *c : g->m) RM_TRY(em_check(c, true)); // (a member with a frame error model: refused before anything is launched)
-    for (rm_context *c : g->m) RM_TRY(stats_check(c, true)); // (a member with traffic counters: likewise)
-    for (rm_context *c : g->m) RM_TRY(listen_check(c, true)); // (a member with listening schedules: likewise)
-    for (rm_context *c : g->m) RM_TRY(linkstats_check(c, true)); // (a member with watched-link statistics: likewise)
+    RM_TRY(passes_check(g->m.data(), g->m.size(), true, true)); // (a member with a pass on: refused before anything is launched)
     RM_TRY(group_comm(g));
     const int world = int(g->m.size());
     const size_t block = size_t(slots) * sizeof(rm_tx_record);
@@ -342,10 +339,7 @@ int rm_group_tick_flush(rm_group *g, int32_t *pkt, int32_t *dst, uint8_t *verdic
                         uint32_t *count, uint8_t *pkt_interference, uint32_t *pkt_offset)
 {
     if (!g || !g->in_tick) return fail(RM_ERR_STATE, "rm_group_tick_flush without rm_group_tick_begin");
-    for (rm_context *c : g->m) RM_TRY(em_check(c, true)); // (a member with a frame error model: refused, the tick stays open)
-    for (rm_context *c : g->m) RM_TRY(stats_check(c, true)); // (a member with traffic counters: likewise)
-    for (rm_context *c : g->m) RM_TRY(listen_check(c, true)); // (a member with listening schedules: likewise)
-    for (rm_context *c : g->m) RM_TRY(linkstats_check(c, true)); // (a member with watched-link statistics: likewise)
+    RM_TRY(passes_check(g->m.data(), g->m.size(), true, true)); // (a member with a pass on: refused, the tick stays open)
     g->in_tick = false;
     const int n_new = g->n_new;
     // every member's launches are enqueued before anything is waited for

@@ -2,8 +2,8 @@
 // rm_linkstats.hip).
 //
 // The tables belong to the context, not to a medium or a tick slot: K peer slots and K rm_link_stats per node index and one
-// rm_stats_totals.  The evaluating calls run the pass (launch_tick, launch_batch, batch_run's fallback); everything here enables,
-// sets the peers, clears and reads.
+// rm_stats_totals.  The evaluating calls run the pass (through the seam of rm_api_passes.cpp); everything here enables, sets the
+// peers, clears and reads.
 #include "rm_host.hpp"
 
 #include <algorithm>
@@ -23,24 +23,11 @@ rm::LinkStatsDev linkstats_dev(const rm_context *c)
     return d;
 }
 
-int linkstats_check(const rm_context *c, bool gathered)
-{
-    if (!linkstats_on(c)) return RM_OK;
-    if (gathered)
-        return fail(RM_ERR_STATE, "watched-link statistics are on: the gathered, rm_dist_* and rm_group_* forms do not run their pass "
-                                  "(rm_linkstats_enable with 0 switches them off)");
-    if (part_spatial(c) || part_count(c) != c->n)
-        return fail(RM_ERR_STATE, "watched-link statistics are on: a context with a receiver partition does not run their pass");
-    return RM_OK;
-}
-
 void linkstats_release(rm_context *c)
 {
     rm_context::LinkStats &lk = c->lk;
     lk.peer.release(); lk.stage.release(); lk.table.release(); lk.totals.release(); lk.mark.release();
-    if (lk.h_block) (void)hipHostFree(lk.h_block);
-    lk.h_block = nullptr;
-    lk.h_cap = 0;
+    lk.h.release();
     if (lk.h_bad) (void)hipHostFree(lk.h_bad);
     lk.h_bad = nullptr;
     lk.host_stale = false;
@@ -83,36 +70,18 @@ static size_t linkstats_entries(const rm_context *c) { return size_t(std::max(c-
 // totals, then the list.  The stream is idle when this returns: the caller may overwrite the block
 static int linkstats_host_block(rm_context *c, int32_t n, char **h_rows, rm_stats_totals **h_totals, int32_t **h_nodes)
 {
-    rm_context::LinkStats &lk = c->lk;
-    RM_HIP(hipStreamSynchronize(c->stream)); // (an earlier list call's launch may still read or write the block)
-    if (lk.h_cap < size_t(n) || !lk.h_block) {
-        if (lk.h_block) RM_HIP(hipHostFree(lk.h_block));
-        lk.h_block = nullptr;
-        lk.h_cap = 0;
-        const size_t want = std::max<size_t>(size_t(n) + size_t(n) / 2, 256);
-        // (sized for eight slots a row: the block outlives a change of K)
-        RM_HIP(hipHostMalloc(reinterpret_cast<void **>(&lk.h_block), want * 8u * sizeof(rm_link_stats) + pad64(sizeof(rm_stats_totals)) + pad64(want * 4),
-                             hipHostMallocMapped));
-        lk.h_cap = want;
-    }
-    *h_rows = lk.h_block;
-    *h_totals = reinterpret_cast<rm_stats_totals *>(lk.h_block + lk.h_cap * 8u * sizeof(rm_link_stats));
-    *h_nodes = reinterpret_cast<int32_t *>(lk.h_block + lk.h_cap * 8u * sizeof(rm_link_stats) + pad64(sizeof(rm_stats_totals)));
+    PinnedBlock &h = c->lk.h;
+    // (sized for eight slots a row: the block outlives a change of K)
+    RM_TRY(h.ensure(c->stream, size_t(n), [](size_t cap) { return cap * 8u * sizeof(rm_link_stats) + pad64(sizeof(rm_stats_totals)) + pad64(cap * 4); }));
+    *h_rows = h.p;
+    *h_totals = reinterpret_cast<rm_stats_totals *>(h.p + h.cap * 8u * sizeof(rm_link_stats));
+    *h_nodes = reinterpret_cast<int32_t *>(h.p + h.cap * 8u * sizeof(rm_link_stats) + pad64(sizeof(rm_stats_totals)));
     return RM_OK;
 }
 
-static int linkstats_have(const rm_context *c)
+int linkstats_have(const rm_context *c)
 {
     if (!linkstats_on(c) || c->lk.n < 0) return fail(RM_ERR_STATE, "no watched-link statistics: rm_linkstats_enable(ctx, K) comes first");
-    return RM_OK;
-}
-
-static int linkstats_check_list(const int32_t *nodes, int32_t n, int32_t n_nodes)
-{
-    if (!nodes && n != n_nodes) return fail(RM_ERR_INVALID, "without a list n has to be the node count");
-    if (nodes)
-        for (int32_t k = 0; k < n; ++k)
-            if (nodes[k] < 0 || nodes[k] >= n_nodes) return fail(RM_ERR_INVALID, "node index out of range");
     return RM_OK;
 }
 
@@ -126,8 +95,7 @@ int rm_linkstats_enable(rm_context *c, int32_t K)
     if (K != 0 && K != 1 && K != 2 && K != 4 && K != 8) return fail(RM_ERR_INVALID, "K is 1, 2, 4 or 8 (0: off)");
     RM_HIP(hipSetDevice(c->device));
     if (K == 0) return linkstats_off(c);
-    if (c->use_graphs)
-        return fail(RM_ERR_STATE, "this context replays its ticks from captured graphs (RM_GRAPH=1): the watched links' pass is not part of them");
+    RM_TRY(graphs_refuse(c, "the watched links' pass is not part of them"));
     rm_context::LinkStats &lk = c->lk;
     if (lk.K == K && lk.n == c->n) return RM_OK; // the same K again: nothing changes
     RM_TRY(linkstats_off(c));
@@ -183,7 +151,7 @@ int rm_linkstats_peers_get(rm_context *c, const int32_t *nodes, int32_t n, int32
     if (!c || n < 0 || (n > 0 && !out)) return fail(RM_ERR_INVALID, "bad arguments");
     RM_TRY(linkstats_have(c));
     const rm_context::LinkStats &lk = c->lk;
-    RM_TRY(linkstats_check_list(nodes, n, lk.n));
+    RM_TRY(check_node_list(nodes, n, lk.n));
     if (lk.host_stale) {
         RM_HIP(hipSetDevice(c->device));
         RM_TRY(linkstats_host_fresh(c));
@@ -198,7 +166,7 @@ int rm_linkstats_read(rm_context *c, const int32_t *nodes, int32_t n, rm_link_st
     if (!c || n < 0 || (n > 0 && !out)) return fail(RM_ERR_INVALID, "bad arguments");
     RM_TRY(linkstats_have(c));
     const rm_context::LinkStats &lk = c->lk;
-    RM_TRY(linkstats_check_list(nodes, n, lk.n));
+    RM_TRY(check_node_list(nodes, n, lk.n));
     RM_HIP(hipSetDevice(c->device));
     const size_t K = size_t(lk.K);
     if (!nodes || n == 0) { // the whole table in node order (or the totals alone): copies on the stream, one synchronisation
@@ -246,7 +214,7 @@ int rm_linkstats_validate(int32_t n_nodes, int32_t K, const int32_t *nodes, int3
 {
     if (K != 1 && K != 2 && K != 4 && K != 8) return fail(RM_ERR_INVALID, "K is 1, 2, 4 or 8");
     if (n_nodes < 0 || n < 0 || (n > 0 && !peers)) return fail(RM_ERR_INVALID, "bad arguments");
-    if (!nodes && n != n_nodes) return fail(RM_ERR_INVALID, "without a list n has to be the node count");
+    if (!nodes) RM_TRY(check_node_list(nullptr, n, n_nodes)); // (the count alone: a listed node is checked with its row, below)
     for (int32_t r = 0; r < n; ++r) {
         const int32_t node = nodes ? nodes[r] : r;
         if (node < 0 || node >= n_nodes) return fail(RM_ERR_INVALID, "node index out of range");

@@ -2,7 +2,7 @@
 // rm_listen.hip).
 //
 // The tables belong to the context, not to a medium or a tick slot: one rm_listen_schedule and one missed count per node index.
-// The evaluating calls run the pass (launch_tick, launch_batch, batch_run's fallback); everything here sets, clears and reads.
+// The evaluating calls run the pass (through the seam of rm_api_passes.cpp); everything here sets, clears and reads.
 #include "rm_host.hpp"
 
 using namespace rmh;
@@ -16,17 +16,6 @@ rm::ListenDev listen_dev(const rm_context *c)
     d.missed = c->ls.missed.p;
     d.n_nodes = c->ls.n;
     return d;
-}
-
-int listen_check(const rm_context *c, bool gathered)
-{
-    if (!listen_on(c)) return RM_OK;
-    if (gathered)
-        return fail(RM_ERR_STATE, "listening schedules are on: the gathered, rm_dist_* and rm_group_* forms do not run their pass "
-                                  "(rm_listen_clear switches them off)");
-    if (part_spatial(c) || part_count(c) != c->n)
-        return fail(RM_ERR_STATE, "listening schedules are on: a context with a receiver partition does not run their pass");
-    return RM_OK;
 }
 
 // off: every node always listens, the tables forgotten (the buffers stay for the next rm_listen_set)
@@ -62,38 +51,19 @@ static int listen_make(rm_context *c)
 }
 
 // the pinned, host-mapped block of a list call: n records (a list update's schedules in, or a list read's counts out), then the list.
-// The stream is idle when this returns: the caller may overwrite the block
+// The stream is idle when this returns (a set's scatter, a read's gather may have been reading the block): the caller may overwrite it
 static int listen_host_block(rm_context *c, int32_t n, char **h_recs, int32_t **h_nodes)
 {
-    rm_context::Listen &ls = c->ls;
-    if (ls.h_cap < size_t(n) || !ls.h_block) {
-        RM_HIP(hipStreamSynchronize(c->stream));
-        if (ls.h_block) RM_HIP(hipHostFree(ls.h_block));
-        ls.h_block = nullptr;
-        ls.h_cap = 0;
-        const size_t want = std::max<size_t>(size_t(n) + size_t(n) / 2, 256);
-        RM_HIP(hipHostMalloc(reinterpret_cast<void **>(&ls.h_block), pad64(want * sizeof(rm_listen_schedule)) + pad64(want * 4), hipHostMallocMapped));
-        ls.h_cap = want;
-    }
-    else
-        RM_HIP(hipStreamSynchronize(c->stream)); // (an earlier list call's launch -- a set's scatter, a read's gather -- may still read the block)
-    *h_recs = ls.h_block;
-    *h_nodes = reinterpret_cast<int32_t *>(ls.h_block + pad64(ls.h_cap * sizeof(rm_listen_schedule)));
+    PinnedBlock &h = c->ls.h;
+    RM_TRY(h.ensure(c->stream, size_t(n), [](size_t cap) { return pad64(cap * sizeof(rm_listen_schedule)) + pad64(cap * 4); }));
+    *h_recs = h.p;
+    *h_nodes = reinterpret_cast<int32_t *>(h.p + pad64(h.cap * sizeof(rm_listen_schedule)));
     return RM_OK;
 }
 
 static int listen_have(const rm_context *c)
 {
     if (c->ls.n < 0) return fail(RM_ERR_STATE, "no listening schedules: rm_listen_set comes first");
-    return RM_OK;
-}
-
-static int listen_check_list(const int32_t *nodes, int32_t n, int32_t n_nodes)
-{
-    if (!nodes && n != n_nodes) return fail(RM_ERR_INVALID, "without a list n has to be the node count");
-    if (nodes)
-        for (int32_t k = 0; k < n; ++k)
-            if (nodes[k] < 0 || nodes[k] >= n_nodes) return fail(RM_ERR_INVALID, "node index out of range");
     return RM_OK;
 }
 
@@ -104,10 +74,9 @@ extern "C" {
 int rm_listen_set(rm_context *c, const int32_t *nodes, int32_t n, const rm_listen_schedule *sched)
 {
     if (!c || n < 0 || (n > 0 && !sched)) return fail(RM_ERR_INVALID, "bad arguments");
-    if (c->use_graphs)
-        return fail(RM_ERR_STATE, "this context replays its ticks from captured graphs (RM_GRAPH=1): the schedules' pass is not part of them");
+    RM_TRY(graphs_refuse(c, "the schedules' pass is not part of them"));
     // the whole list is validated before anything changes
-    RM_TRY(listen_check_list(nodes, n, c->n));
+    RM_TRY(check_node_list(nodes, n, c->n));
     for (int32_t k = 0; k < n; ++k)
         if (!rm::host_listen_valid(sched[k]))
             return fail(RM_ERR_INVALID, "bad rm_listen_schedule: period_us 0 with on_us = phase_us = 0, or period_us > 0 with "
@@ -144,7 +113,7 @@ int rm_listen_get(rm_context *c, const int32_t *nodes, int32_t n, rm_listen_sche
 {
     if (!c || n < 0 || (n > 0 && !out)) return fail(RM_ERR_INVALID, "bad arguments");
     RM_TRY(listen_have(c));
-    RM_TRY(listen_check_list(nodes, n, c->ls.n));
+    RM_TRY(check_node_list(nodes, n, c->ls.n));
     for (int32_t k = 0; k < n; ++k) out[k] = c->ls.host[size_t(nodes ? nodes[k] : k)];
     return RM_OK;
 }
@@ -166,7 +135,7 @@ int rm_listen_missed_read(rm_context *c, const int32_t *nodes, int32_t n, uint64
 {
     if (!c || n < 0 || (n > 0 && !out)) return fail(RM_ERR_INVALID, "bad arguments");
     RM_TRY(listen_have(c));
-    RM_TRY(listen_check_list(nodes, n, c->ls.n));
+    RM_TRY(check_node_list(nodes, n, c->ls.n));
     if (n == 0) return RM_OK;
     RM_HIP(hipSetDevice(c->device));
     if (!nodes) { // the whole table in node order: one copy on the stream, one synchronisation

@@ -27,14 +27,13 @@ static int neighbors_check(rm_context *c, int32_t direction, int32_t K, bool hav
     if (K < 1 || K > RM_NB_MAX_K) return fail(RM_ERR_INVALID, "K outside 1 .. RM_NB_MAX_K");
     if (n < 0) return fail(RM_ERR_INVALID, "negative entry count");
     if (!peer) return fail(RM_ERR_INVALID, "peer is NULL");
-    if (!have_list && n != c->n) return fail(RM_ERR_INVALID, "without a list n has to be the node count");
+    if (!have_list) RM_TRY(check_node_list(nullptr, n, c->n)); // (the count; the host form checks its list once this has passed)
     if (c->params.kind != RM_MODEL_LOGDIST)
         return fail(RM_ERR_STATE, "the neighbour query ranks links by rssi: only the log-distance medium computes one per link");
     if (c->in_tick) return fail(RM_ERR_STATE, "rm_neighbors_query between rm_tick_begin and rm_tick_flush");
     if (part_count(c) != c->n || part_spatial(c))
         return fail(RM_ERR_STATE, "the neighbour query needs the whole receiver table: this context has a receiver partition");
-    if (c->use_graphs)
-        return fail(RM_ERR_STATE, "this context replays its ticks from captured graphs (RM_GRAPH=1): the neighbour query is not part of them");
+    RM_TRY(graphs_refuse(c, "the neighbour query is not part of them"));
     if (int64_t(n) * int64_t(K) > (int64_t(1) << 27)) return fail(RM_ERR_CAPACITY, "n * K above 2^27");
     return RM_OK;
 }
@@ -89,9 +88,7 @@ int rm_neighbors_query_device(rm_context *c, int32_t direction, int32_t K, const
 int rm_neighbors_query(rm_context *c, int32_t direction, int32_t K, const int32_t *nodes, int32_t n, int32_t *peer, double *rssi, int32_t *degree)
 {
     RM_TRY(neighbors_check(c, direction, K, nodes != nullptr, n, peer));
-    if (nodes)
-        for (int32_t k = 0; k < n; ++k)
-            if (nodes[k] < 0 || nodes[k] >= c->n) return fail(RM_ERR_INVALID, "node index out of range");
+    RM_TRY(check_node_list(nodes, n, c->n));
     if (n == 0) return RM_OK;
     RM_HIP(hipSetDevice(c->device));
     // the call's device block lives for this call only: list, rows, rssi, degrees
@@ -165,7 +162,7 @@ int rm_neighbors_from_result(const rm_host_result *r, int32_t n_pkt, int32_t K, 
 int rm_linkstats_stage_device(rm_context *c, int32_t **dev_rows)
 {
     if (!c || !dev_rows) return fail(RM_ERR_INVALID, "ctx or dev_rows is NULL");
-    if (!linkstats_on(c) || c->lk.n < 0) return fail(RM_ERR_STATE, "no watched-link statistics: rm_linkstats_enable(ctx, K) comes first");
+    RM_TRY(linkstats_have(c));
     rm_context::LinkStats &lk = c->lk;
     RM_HIP(hipSetDevice(c->device));
     const size_t want = size_t(std::max(lk.n, 1)) * size_t(lk.K);
@@ -180,10 +177,10 @@ int rm_linkstats_stage_device(rm_context *c, int32_t **dev_rows)
 int rm_linkstats_watch_device(rm_context *c, const int32_t *dev_nodes, int32_t n, const int32_t *dev_peers)
 {
     if (!c) return fail(RM_ERR_INVALID, "ctx is NULL");
-    if (!linkstats_on(c) || c->lk.n < 0) return fail(RM_ERR_STATE, "no watched-link statistics: rm_linkstats_enable(ctx, K) comes first");
+    RM_TRY(linkstats_have(c));
     rm_context::LinkStats &lk = c->lk;
     if (n < 0 || (n > 0 && !dev_peers)) return fail(RM_ERR_INVALID, "bad arguments");
-    if (!dev_nodes && n != lk.n) return fail(RM_ERR_INVALID, "without a list n has to be the node count");
+    if (!dev_nodes) RM_TRY(check_node_list(nullptr, n, lk.n)); // (the count; a list in device memory is checked on the device)
     if (n == 0) return RM_OK;
     RM_HIP(hipSetDevice(c->device));
     if (!lk.h_bad) RM_HIP(hipHostMalloc(reinterpret_cast<void **>(&lk.h_bad), 64, hipHostMallocMapped));

@@ -432,10 +432,7 @@ int rm_nodes_upload(rm_context *c, int32_t n, const double *x, const double *y, 
     }
     RM_HIP(hipStreamSynchronize(c->stream));
     if (c->ev.on) RM_TRY(ev_ensure_nodes(c));
-    RM_TRY(stats_nodes_changed(c)); // (the traffic counters: another node count resizes the table and zeroes it)
-    RM_TRY(listen_nodes_changed(c)); // (the listening schedules: another node count clears them)
-    RM_TRY(traffic_nodes_changed(c)); // (the traffic schedules: another node count clears them)
-    RM_TRY(linkstats_nodes_changed(c)); // (the watched-link statistics: another node count switches them off)
+    RM_TRY(passes_nodes_changed(c)); // (the extensions' tables by node index: another node count resizes, clears or switches off)
     recompute_frame(c);
     c->rx_dirty = true;
     c->frac_probs = -1;

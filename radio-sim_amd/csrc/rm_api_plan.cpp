@@ -429,27 +429,7 @@ int launch_tick(rm_context *c, TickSlot &ts, const TickPlan &plan, bool em_pass)
         ts.last_model = m;
         ts.last_cfg = cfg;
         ts.have_result = true;
-        if (em_pass && listen_on(c)) {
-            // the listening schedules (E13) over a dense tick: its records from the lane masks, then the pass over them.  The masks
-            // carry one verdict per packet and cannot express the pass: rm_result_dense refuses this tick
-            RM_TRY(stage(RM_STAGE_REORDER));
-            RM_TRY(materialize(c, ts));
-            RM_HIP(rm::launch_listen(s, listen_dev(c), ts.last));
-            ts.dense_listen = true;
-        }
-        if (em_pass && stats_on(c)) {
-            // the traffic counters (E11) over a dense tick: its records from the lane masks, then the pass (rm_result_dense keeps
-            // answering: the masks stay where they are)
-            RM_TRY(stage(RM_STAGE_REORDER));
-            RM_TRY(materialize(c, ts));
-            RM_HIP(rm::launch_stats(s, stats_dev(c), ts.last));
-        }
-        if (em_pass && linkstats_on(c)) {
-            // the watched-link statistics (E14) over a dense tick: as the traffic counters, behind them
-            RM_TRY(stage(RM_STAGE_REORDER));
-            RM_TRY(materialize(c, ts));
-            RM_HIP(rm::launch_linkstats(s, linkstats_dev(c), ts.last));
-        }
+        if (em_pass) RM_TRY(passes_tick(c, ts, smp, false));
         return RM_OK;
     }
     const int seg_len = (t.n_active - t.first_new <= frame_tick_max()) ? rm::frame_tick_segment(t, cfg, m) : 0;
@@ -570,37 +550,7 @@ int launch_tick(rm_context *c, TickSlot &ts, const TickPlan &plan, bool em_pass)
     ts.last_model = m;
     ts.last_cfg = cfg;
     ts.have_result = true;
-    if (em_pass && sinr && em_on(c)) {
-        if (ts.draws_pending) return fail(RM_ERR_STATE, "internal: the frame error model's pass cannot run before the ranks' draws are finished");
-        // the frame error model (E10): the tick's compact arrays at once, then the pass over them -- on the stream before the hand-over
-        // to the reception stage (run_tick), before any pack launch and any copy, which all read out_verdict from here on
-        RM_TRY(stage(RM_STAGE_REORDER));
-        RM_TRY(materialize(c, ts));
-        RM_TRY(stage(RM_STAGE_SINR));
-        RM_HIP(rm::launch_errmodel(s, em_dev(c), ts.last));
-    }
-    if (em_pass && listen_on(c)) {
-        if (ts.draws_pending) return fail(RM_ERR_STATE, "internal: the listening schedules' pass cannot run before the ranks' draws are finished");
-        // the listening schedules (E13), behind the frame error model's pass and ahead of the traffic counters': the tick's compact
-        // arrays at once, then the pass over them -- every reader (pack launches, the reception stage, the copies) reads out_verdict
-        RM_TRY(stage(RM_STAGE_REORDER));
-        RM_TRY(materialize(c, ts));
-        RM_HIP(rm::launch_listen(s, listen_dev(c), ts.last));
-    }
-    if (em_pass && stats_on(c)) {
-        if (ts.draws_pending) return fail(RM_ERR_STATE, "internal: the traffic counters' pass cannot run before the ranks' draws are finished");
-        // the traffic counters (E11), behind the frame error model's pass: the tick's compact arrays at once, then one pass over them
-        RM_TRY(stage(RM_STAGE_REORDER));
-        RM_TRY(materialize(c, ts));
-        RM_HIP(rm::launch_stats(s, stats_dev(c), ts.last));
-    }
-    if (em_pass && linkstats_on(c)) {
-        if (ts.draws_pending) return fail(RM_ERR_STATE, "internal: the watched-link statistics' pass cannot run before the ranks' draws are finished");
-        // the watched-link statistics (E14), behind the traffic counters' pass: the tick's compact arrays at once, then one pass over them
-        RM_TRY(stage(RM_STAGE_REORDER));
-        RM_TRY(materialize(c, ts));
-        RM_HIP(rm::launch_linkstats(s, linkstats_dev(c), ts.last));
-    }
+    if (em_pass) RM_TRY(passes_tick(c, ts, smp, sinr));
     return RM_OK;
 }
 

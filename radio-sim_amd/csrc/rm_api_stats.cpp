@@ -1,7 +1,7 @@
 // rm_api_stats.cpp -- C ABI: per-node traffic counters accumulated on the device (the pass is rm_stats.hip).
 //
 // The table belongs to the context, not to a medium or a tick slot: one rm_node_stats per node index and one rm_stats_totals.
-// The evaluating calls add to it (launch_tick, launch_batch, batch_run's fallback); everything here enables, zeroes and reads it.
+// The evaluating calls add to it (through the seam of rm_api_passes.cpp); everything here enables, zeroes and reads it.
 #include "rm_host.hpp"
 
 using namespace rmh;
@@ -15,17 +15,6 @@ rm::StatsDev stats_dev(const rm_context *c)
     d.totals = c->st.totals.p;
     d.n_nodes = c->st.n;
     return d;
-}
-
-int stats_check(const rm_context *c, bool gathered)
-{
-    if (!stats_on(c)) return RM_OK;
-    if (gathered)
-        return fail(RM_ERR_STATE, "statistics are on: the gathered, rm_dist_* and rm_group_* forms do not run the counters' pass "
-                                  "(rm_stats_enable with 0 switches them off)");
-    if (part_spatial(c) || part_count(c) != c->n)
-        return fail(RM_ERR_STATE, "statistics are on: a context with a receiver partition does not run the counters' pass");
-    return RM_OK;
 }
 
 // the table for c->n nodes, zeroed (with the totals) when it is new or the node count is another one
@@ -48,23 +37,15 @@ int stats_nodes_changed(rm_context *c)
     return stats_size(c);
 }
 
-// the pinned, host-mapped block of a list read: records out, then the totals, then the list in
+// the pinned, host-mapped block of a list read: records out, then the totals, then the list in.  (The block waits for the stream
+// whether it grows or not; the one caller waits for it again behind its launch, so the wait here finds little left to wait for)
 static int stats_host_block(rm_context *c, int32_t n, rm_node_stats **h_out, rm_stats_totals **h_totals, int32_t **h_nodes)
 {
-    rm_context::Stats &st = c->st;
-    if (st.h_cap < size_t(n) || !st.h_block) {
-        RM_HIP(hipStreamSynchronize(c->stream));
-        if (st.h_block) RM_HIP(hipHostFree(st.h_block));
-        st.h_block = nullptr;
-        st.h_cap = 0;
-        const size_t want = std::max<size_t>(size_t(n) + size_t(n) / 2, 256);
-        RM_HIP(hipHostMalloc(reinterpret_cast<void **>(&st.h_block), want * sizeof(rm_node_stats) + pad64(sizeof(rm_stats_totals)) + pad64(want * 4),
-                             hipHostMallocMapped));
-        st.h_cap = want;
-    }
-    *h_out = reinterpret_cast<rm_node_stats *>(st.h_block);
-    *h_totals = reinterpret_cast<rm_stats_totals *>(st.h_block + st.h_cap * sizeof(rm_node_stats));
-    *h_nodes = reinterpret_cast<int32_t *>(st.h_block + st.h_cap * sizeof(rm_node_stats) + pad64(sizeof(rm_stats_totals)));
+    PinnedBlock &h = c->st.h;
+    RM_TRY(h.ensure(c->stream, size_t(n), [](size_t cap) { return cap * sizeof(rm_node_stats) + pad64(sizeof(rm_stats_totals)) + pad64(cap * 4); }));
+    *h_out = reinterpret_cast<rm_node_stats *>(h.p);
+    *h_totals = reinterpret_cast<rm_stats_totals *>(h.p + h.cap * sizeof(rm_node_stats));
+    *h_nodes = reinterpret_cast<int32_t *>(h.p + h.cap * sizeof(rm_node_stats) + pad64(sizeof(rm_stats_totals)));
     return RM_OK;
 }
 
@@ -85,8 +66,7 @@ int rm_stats_enable(rm_context *c, int32_t on)
         c->st.on = false;
         return RM_OK;
     }
-    if (c->use_graphs)
-        return fail(RM_ERR_STATE, "this context replays its ticks from captured graphs (RM_GRAPH=1): the counters' pass is not part of them");
+    RM_TRY(graphs_refuse(c, "the counters' pass is not part of them"));
     RM_HIP(hipSetDevice(c->device));
     RM_TRY(stats_size(c));
     c->st.on = true;
@@ -110,10 +90,7 @@ int rm_stats_read(rm_context *c, const int32_t *nodes, int32_t n, rm_node_stats 
     if (!c || n < 0 || (n > 0 && !out)) return fail(RM_ERR_INVALID, "bad arguments");
     RM_TRY(stats_have(c));
     const rm_context::Stats &st = c->st;
-    if (!nodes && n != st.n) return fail(RM_ERR_INVALID, "without a list n has to be the node count");
-    if (nodes)
-        for (int32_t k = 0; k < n; ++k)
-            if (nodes[k] < 0 || nodes[k] >= st.n) return fail(RM_ERR_INVALID, "node index out of range");
+    RM_TRY(check_node_list(nodes, n, st.n));
     RM_HIP(hipSetDevice(c->device));
     if (!nodes || n == 0) { // the whole table in node order (or the totals alone): copies on the stream, one synchronisation
         if (n > 0) RM_HIP(hipMemcpyAsync(out, st.table.p, size_t(n) * sizeof(rm_node_stats), hipMemcpyDeviceToHost, c->stream));

@@ -180,9 +180,7 @@ int tick_run_host(rm_context *c)
 {
     if (!c) return fail(RM_ERR_INVALID, "ctx is NULL");
     if (!c->in_tick) return fail(RM_ERR_STATE, "rm_tick_flush without rm_tick_begin");
-    RM_TRY(stats_check(c, false)); // (the traffic counters refuse partitions: nothing launched, the tick stays open)
-    RM_TRY(listen_check(c, false)); // (the listening schedules: likewise)
-    RM_TRY(linkstats_check(c, false)); // (the watched-link statistics: likewise)
+    RM_TRY(passes_check(c, false, false)); // (the passes refuse partitions: nothing launched, the tick stays open)
     RM_HIP(hipSetDevice(c->device));
     c->in_tick = false;
     // SINR: the frames of earlier ticks stay on the device (the window air_tick_device keeps, shared with the ticks whose
@@ -377,15 +375,11 @@ int rm_transmit(rm_context *c, int32_t src, int64_t start_us, int64_t hex_length
     if (!c) return fail(RM_ERR_INVALID, "ctx is NULL");
     if (src < 0 || src >= c->n) return fail(RM_ERR_INVALID, "could not find source node");
     if (hex_length < 0) return fail(RM_ERR_INVALID, "negative packet length");
-    RM_TRY(stats_check(c, false)); // (the traffic counters refuse partitions before anything is launched)
-    RM_TRY(listen_check(c, false)); // (the listening schedules: likewise)
-    RM_TRY(linkstats_check(c, false)); // (the watched-link statistics: likewise)
+    RM_TRY(passes_check(c, false, false)); // (the passes refuse partitions before anything is launched)
     ev_touch(c);
     const bool draws_need_exchange = maybe_draws(c) && part_count(c) != c->n;
-    // (with the traffic counters on, the one-launch shortcut below is off: its links never become a slot's result)
-    // (the same with listening schedules on: their pass runs over a slot's result)
-    // (and with watched-link statistics on: the same reason as the counters')
-    if (is_sinr(c) || draws_need_exchange || stats_on(c) || listen_on(c) || linkstats_on(c)) {
+    // (with a pass over a slot's result on, the one-launch shortcut below is off: its links never become one)
+    if (is_sinr(c) || draws_need_exchange || passes_counting(c)) {
         // the on-air list of earlier calls / the per-rank draw exchange: the general tick path
         RM_TRY(rm_tick_begin(c, start_us, start_us));
         RM_TRY(rm_enqueue_tx(c, src, start_us, rm_air_time_us(hex_length), txpower, channel));
@@ -505,9 +499,7 @@ int rm_tick_run_device(rm_context *c, int64_t t_begin_us, int64_t t_end_us, cons
     if (is_sinr(c))
         return fail(RM_ERR_STATE, "the SINR medium keeps frames on the air: records in device memory go through "
                                   "rm_tick_run_records_device, which is told how long they stay (latest_end_us)");
-    RM_TRY(stats_check(c, false)); // (the traffic counters refuse partitions before anything is launched)
-    RM_TRY(listen_check(c, false)); // (the listening schedules: likewise)
-    RM_TRY(linkstats_check(c, false)); // (the watched-link statistics: likewise)
+    RM_TRY(passes_check(c, false, false)); // (the passes refuse partitions before anything is launched)
     RM_HIP(hipSetDevice(c->device));
     c->t_begin = t_begin_us;
     c->t_end = t_end_us;
@@ -521,9 +513,7 @@ int rm_tick_run_sources_device(rm_context *c, int64_t t_begin_us, int64_t t_end_
                                int64_t start_us, int64_t air_us)
 {
     if (!c || n < 0 || (n > 0 && !dev_src) || air_us < 0) return fail(RM_ERR_INVALID, "bad arguments");
-    RM_TRY(stats_check(c, false)); // (the traffic counters refuse partitions before anything is launched)
-    RM_TRY(listen_check(c, false)); // (the listening schedules: likewise)
-    RM_TRY(linkstats_check(c, false)); // (the watched-link statistics: likewise)
+    RM_TRY(passes_check(c, false, false)); // (the passes refuse partitions before anything is launched)
     RM_HIP(hipSetDevice(c->device));
     c->t_begin = t_begin_us;
     c->t_end = t_end_us;
@@ -613,10 +603,7 @@ int air_window_reserve(rm_context *c, size_t n_more)
 int air_tick_device(rm_context *c, int64_t t_begin_us, const int32_t *dev_src, const rm_tx_record *dev_new, int32_t n, int64_t start_us,
                     int64_t air_us, int64_t latest_end_us, bool new_on_host)
 {
-    RM_TRY(em_check(c, false)); // (the frame error model refuses partitions before the window moves)
-    RM_TRY(stats_check(c, false)); // (the traffic counters: likewise)
-    RM_TRY(listen_check(c, false)); // (the listening schedules: likewise)
-    RM_TRY(linkstats_check(c, false)); // (the watched-link statistics: likewise)
+    RM_TRY(passes_check(c, false, true)); // (the passes refuse partitions before the window moves)
     RM_TRY(air_window_expire(c, t_begin_us));
     RM_TRY(air_window_reserve(c, size_t(n)));
     const size_t live = c->air_tail - c->air_head;

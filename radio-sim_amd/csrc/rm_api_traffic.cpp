@@ -31,8 +31,7 @@ void traffic_release(rm_context *c)
 {
     rm_context::Traffic &tf = c->tf;
     tf.sched.release(); tf.d_win.release(); tf.d_unit_count.release(); tf.d_unit_packets.release();
-    if (tf.h_block) (void)hipHostFree(tf.h_block);
-    tf.h_block = nullptr;
+    tf.h.release();
     for (int g = 0; g < 2; ++g) {
         if (tf.h_ev[g]) (void)hipEventDestroy(tf.h_ev[g]);
         if (tf.h_win[g]) (void)hipHostFree(tf.h_win[g]);
@@ -57,33 +56,16 @@ static int traffic_make(rm_context *c)
 // The stream is idle when this returns: the caller may overwrite the block
 static int traffic_host_block(rm_context *c, int32_t n, rm_traffic_schedule **h_recs, int32_t **h_nodes)
 {
-    rm_context::Traffic &tf = c->tf;
-    RM_HIP(hipStreamSynchronize(c->stream)); // (an earlier list call's launch may still read the block)
-    if (tf.h_cap < size_t(n) || !tf.h_block) {
-        if (tf.h_block) RM_HIP(hipHostFree(tf.h_block));
-        tf.h_block = nullptr;
-        tf.h_cap = 0;
-        const size_t want = std::max<size_t>(size_t(n) + size_t(n) / 2, 256);
-        RM_HIP(hipHostMalloc(reinterpret_cast<void **>(&tf.h_block), pad64(want * sizeof(rm_traffic_schedule)) + pad64(want * 4), hipHostMallocMapped));
-        tf.h_cap = want;
-    }
-    *h_recs = reinterpret_cast<rm_traffic_schedule *>(tf.h_block);
-    *h_nodes = reinterpret_cast<int32_t *>(tf.h_block + pad64(tf.h_cap * sizeof(rm_traffic_schedule)));
+    PinnedBlock &h = c->tf.h;
+    RM_TRY(h.ensure(c->stream, size_t(n), [](size_t cap) { return pad64(cap * sizeof(rm_traffic_schedule)) + pad64(cap * 4); }));
+    *h_recs = reinterpret_cast<rm_traffic_schedule *>(h.p);
+    *h_nodes = reinterpret_cast<int32_t *>(h.p + pad64(h.cap * sizeof(rm_traffic_schedule)));
     return RM_OK;
 }
 
 static int traffic_have(const rm_context *c)
 {
     if (c->tf.n < 0) return fail(RM_ERR_STATE, "no traffic schedules: rm_traffic_set comes first");
-    return RM_OK;
-}
-
-static int traffic_check_list(const int32_t *nodes, int32_t n, int32_t n_nodes)
-{
-    if (!nodes && n != n_nodes) return fail(RM_ERR_INVALID, "without a list n has to be the node count");
-    if (nodes)
-        for (int32_t k = 0; k < n; ++k)
-            if (nodes[k] < 0 || nodes[k] >= n_nodes) return fail(RM_ERR_INVALID, "node index out of range");
     return RM_OK;
 }
 
@@ -142,15 +124,14 @@ extern "C" {
 int rm_traffic_validate(int32_t n_nodes, const int32_t *nodes, int32_t n, const rm_traffic_schedule *sched)
 {
     if (n_nodes < 0 || n < 0 || (n > 0 && !sched)) return fail(RM_ERR_INVALID, "bad arguments");
-    RM_TRY(traffic_check_list(nodes, n, n_nodes));
+    RM_TRY(check_node_list(nodes, n, n_nodes));
     return traffic_check_records(sched, n);
 }
 
 int rm_traffic_set(rm_context *c, const int32_t *nodes, int32_t n, const rm_traffic_schedule *sched)
 {
     if (!c) return fail(RM_ERR_INVALID, "ctx is NULL");
-    if (c->use_graphs)
-        return fail(RM_ERR_STATE, "this context replays its ticks from captured graphs (RM_GRAPH=1): the extensions' tables are not set on it");
+    RM_TRY(graphs_refuse(c, "the extensions' tables are not set on it"));
     // the whole list is validated before anything changes
     RM_TRY(rm_traffic_validate(c->n, nodes, n, sched));
     RM_HIP(hipSetDevice(c->device));
@@ -169,7 +150,7 @@ int rm_traffic_get(rm_context *c, const int32_t *nodes, int32_t n, rm_traffic_sc
 {
     if (!c || n < 0 || (n > 0 && !out)) return fail(RM_ERR_INVALID, "bad arguments");
     RM_TRY(traffic_have(c));
-    RM_TRY(traffic_check_list(nodes, n, c->tf.n));
+    RM_TRY(check_node_list(nodes, n, c->tf.n));
     if (n == 0) return RM_OK;
     RM_HIP(hipSetDevice(c->device));
     if (!nodes) { // the whole table in node order: one copy on the stream, one synchronisation

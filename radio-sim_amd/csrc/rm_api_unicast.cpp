@@ -21,8 +21,7 @@ size_t uc_desc_bytes() { return uc_prefix_off() + pad64(sizeof(uint32_t) * (RM_M
 // what every form refuses with RM_ERR_STATE: nothing launched, nothing changed
 int uc_check_state(rm_context *c)
 {
-    if (c->use_graphs)
-        return fail(RM_ERR_STATE, "this context replays its ticks from captured graphs (RM_GRAPH=1): the query's pass is not part of them");
+    RM_TRY(graphs_refuse(c, "the query's pass is not part of them"));
     if (c->uc.slots <= 0 || !c->have_result) return fail(RM_ERR_STATE, "no evaluated result yet");
     if (part_spatial(c) || part_count(c) != c->n)
         return fail(RM_ERR_STATE, "a context with a receiver partition does not hold the other ranks' links: RM_UC_UNHEARD would be a lie");

@@ -70,9 +70,34 @@ template <typename T> struct DevBuf {
     }
 };
 
+// The pinned, host-mapped block a list call is staged through (node list in; records in or out), counted in list entries.
+struct PinnedBlock {
+    char *p = nullptr;
+    size_t cap = 0; // entries the block has room for
+    // room for n entries, grown by half (at least 256 entries); bytes(cap) is the block's size with room for cap entries.  The
+    // stream is idle when this returns: no earlier list call's launch reads or writes the block, the caller may overwrite it
+    template <typename Bytes> int ensure(hipStream_t s, size_t n, Bytes bytes)
+    {
+        RM_HIP(hipStreamSynchronize(s));
+        if (cap >= n && p) return RM_OK;
+        release();
+        const size_t want = std::max<size_t>(n + n / 2, 256);
+        RM_HIP(hipHostMalloc(reinterpret_cast<void **>(&p), bytes(want), hipHostMallocMapped));
+        cap = want;
+        return RM_OK;
+    }
+    void release()
+    {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
 } // namespace rmh
 
 using rmh::DevBuf;
+using rmh::PinnedBlock;
 
 // Everything one evaluated tick owns on the device.  A context is its own slot 0; rm_batch_*
 // adds further slots so that several ticks can be in flight through one launch sequence.
@@ -154,8 +179,7 @@ struct rm_context : TickSlot {
         int32_t n = -1; // the node count the table was made (and zeroed) for; -1: never enabled
         DevBuf<rm_node_stats> table;
         DevBuf<rm_stats_totals> totals;
-        char *h_block = nullptr;
-        size_t h_cap = 0; // nodes the block has room for
+        PinnedBlock h;
     } st;
     // receiver listening schedules (E13; rm_api_listen.cpp, rm_listen.hip): one schedule and one missed count per node index, the
     // host's copy of the schedules (rm_listen_get reads it; a list update is applied to it in order), and the pinned, host-mapped
@@ -166,8 +190,7 @@ struct rm_context : TickSlot {
         std::vector<rm_listen_schedule> host;
         DevBuf<rm_listen_schedule> sched;
         DevBuf<uint64_t> missed;
-        char *h_block = nullptr;
-        size_t h_cap = 0; // list entries the block has room for
+        PinnedBlock h;
     } ls;
     // watched-link statistics (E14; rm_api_linkstats.cpp, rm_linkstats.hip): K peer slots and K entries per node index, the totals,
     // the host's copy of the peer rows (rm_linkstats_peers_get reads it), the device staging of a whole-table watch and the pinned,
@@ -179,8 +202,7 @@ struct rm_context : TickSlot {
         DevBuf<int32_t> peer, stage;
         DevBuf<rm_link_stats> table;
         DevBuf<rm_stats_totals> totals;
-        char *h_block = nullptr;
-        size_t h_cap = 0; // rows the block has room for
+        PinnedBlock h; // (counted in rows)
         // rm_linkstats_watch_device (rm_api_neighbors.cpp): the rows never pass through the host, so its copy is refreshed from the
         // device's table when somebody next reads it; the validation's per-node marks, its stamp and its pinned flag word
         bool host_stale = false;
@@ -201,8 +223,7 @@ struct rm_context : TickSlot {
         bool on = false;
         int32_t n = -1; // the node count the table was made for; -1: never set (or cleared)
         DevBuf<rm_traffic_schedule> sched;
-        char *h_block = nullptr;
-        size_t h_cap = 0; // list entries the block has room for
+        PinnedBlock h;
         DevBuf<int64_t> d_win;
         DevBuf<int32_t> d_unit_count;
         DevBuf<uint64_t> d_unit_packets;
@@ -721,34 +742,28 @@ int cca_batch_dev(rm_context *c, size_t n_cand, int32_t n_ticks, const int32_t *
 // ---- rm_api_errmodel.cpp: the frame error model (E10)
 inline bool em_on(const rm_context *c) { return c->em.kind != RM_EM_NONE; }
 rm::EmDev em_dev(const rm_context *c);
-// what an evaluating call refuses while a model is on, before anything is launched (gathered: a gathered / rm_dist_* form)
-int em_check(const rm_context *c, bool gathered);
 
 // ---- rm_api_stats.cpp: per-node traffic counters (E11)
 inline bool stats_on(const rm_context *c) { return c->st.on; }
 rm::StatsDev stats_dev(const rm_context *c);
-// what an evaluating call refuses while statistics are on, before anything is launched (the shape of em_check)
-int stats_check(const rm_context *c, bool gathered);
 // rm_nodes_upload: another node count resizes the table and zeroes it
 int stats_nodes_changed(rm_context *c);
 
 // ---- rm_api_listen.cpp: receiver listening schedules (E13)
 inline bool listen_on(const rm_context *c) { return c->ls.on; }
 rm::ListenDev listen_dev(const rm_context *c);
-// what an evaluating call refuses while schedules are on, before anything is launched (the shape of em_check)
-int listen_check(const rm_context *c, bool gathered);
 // rm_nodes_upload: another node count clears the feature
 int listen_nodes_changed(rm_context *c);
 
 // ---- rm_api_linkstats.cpp: watched-link statistics (E14)
 inline bool linkstats_on(const rm_context *c) { return c->lk.K > 0; }
 rm::LinkStatsDev linkstats_dev(const rm_context *c);
-// what an evaluating call refuses while the feature is on, before anything is launched (the shape of em_check)
-int linkstats_check(const rm_context *c, bool gathered);
 // rm_nodes_upload: another node count switches the feature off
 int linkstats_nodes_changed(rm_context *c);
 // rm_destroy: the tables and the host block
 void linkstats_release(rm_context *c);
+// what every call that reads or sets the tables refuses while the feature is off
+int linkstats_have(const rm_context *c);
 // the host's copy of the peer rows, read back from the device if rm_linkstats_watch_device has written the table since
 int linkstats_host_fresh(rm_context *c);
 
@@ -761,6 +776,43 @@ void neighbors_release(rm_context *c);
 int traffic_nodes_changed(rm_context *c);
 // rm_destroy
 void traffic_release(rm_context *c);
+
+// ---- rm_api_passes.cpp: the passes over a finished result (E10, E13, E11, E14 -- in this order; DESIGN.md, end of section 4.14)
+// what an evaluating call refuses while a pass is on, before anything is launched: the gathered / rm_dist_* / rm_group_* forms
+// (gathered), else a context with a receiver partition.  with_em: the frame error model's refusal is among them (the lone-tick
+// entry points leave it to air_tick_device).  The members' form asks every member about one pass before the next pass
+int passes_check(const rm_context *c, bool gathered, bool with_em);
+int passes_check(const rm_context *const *members, size_t n, bool gathered, bool with_em);
+// a pass that needs every tick as a slot's result with its compact arrays is on: the counters, the schedules, the watched links
+bool passes_counting(const rm_context *c);
+inline bool passes_any(const rm_context *c) { return passes_counting(c) || (em_on(c) && is_sinr(c)); }
+// the passes behind a lone tick's launch sequence, dense form or not, over the slot's compact arrays (sinr: the tick is one of the
+// SINR medium's, which alone runs E10)
+int passes_tick(rm_context *c, TickSlot &ts, rm_context::Sample *smp, bool sinr);
+// the passes over the n slots of a batch, one launch each, on the context's stream; the three behind E10's are sampled under
+// counters_stage (E10's under RM_STAGE_SINR)
+int passes_batch(rm_context *c, int n, const rm::TickDev *dev_ticks, rm_context::Sample *smp, int counters_stage);
+// rm_nodes_upload: another node count -- the counters resize and zero, the schedules (E13, E15) clear, the watched links switch off
+int passes_nodes_changed(rm_context *c);
+// rm_destroy: the tables and host blocks of E11, E13, E14, E15 and E16
+void passes_release(rm_context *c);
+
+// ---- what the list calls of E11 .. E16 share
+// a call that takes a node list or, without one, the whole table in node order
+inline int check_node_list(const int32_t *nodes, int32_t n, int32_t n_nodes)
+{
+    if (!nodes && n != n_nodes) return fail(RM_ERR_INVALID, "without a list n has to be the node count");
+    if (nodes)
+        for (int32_t k = 0; k < n; ++k)
+            if (nodes[k] < 0 || nodes[k] >= n_nodes) return fail(RM_ERR_INVALID, "node index out of range");
+    return RM_OK;
+}
+// a context made under RM_GRAPH=1 takes none of the extensions; `why` is the clause that names what is refused
+inline int graphs_refuse(const rm_context *c, const char *why)
+{
+    if (!c->use_graphs) return RM_OK;
+    return fail(RM_ERR_STATE, std::string("this context replays its ticks from captured graphs (RM_GRAPH=1): ") + why);
+}
 
 // ---- rm_api_unicast.cpp: the unicast outcome query (E12)
 // an evaluating call has left its results in `slots` result slots (gathered: a gathered / rm_dist_* / rm_group_* form)

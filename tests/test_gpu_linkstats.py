@@ -289,6 +289,152 @@ def test_lone_tick_with_all_four_passes(rsa, O):
         eng.close()
 
 
+LONE_SWEEP = {"k_tick_frames", "k_tick_frames_sinr", "k_tick_frames_scan", "k_frames_cand", "k_filter", "k_filter_wg", "k_exact"}
+BATCH_SWEEP = {"k_filter_wg_batch", "k_filter_wg_group", "k_exact_batch", "k_reorder_batch", "k_tick_frames_batch"}
+LONE_PASSES = ("k_errmodel", "k_listen", "k_stats", "k_linkstats")
+BATCH_PASSES = ("k_errmodel_batch", "k_listen_batch", "k_stats_batch", "k_linkstats_batch")
+
+
+def test_batch_launched_tick_by_tick_with_all_four_passes(rsa, O):
+    """a batch with an empty tick is launched one tick at a time (rm::batch_eligible wants frames in every tick): the four passes
+    run once each over all its slots behind the last tick, in their order, and no lone tick's pass runs.  The scene's ticks are
+    self-contained (a frame ends inside its tick), so the ticks that keep their lists have the whole batch's results."""
+    nd, lists, starts, air, sched, run, rows, _, _ = _ref("batch", 4, R.SEED)
+    gone = 4
+    assert air <= TICK and len(lists[gone]) > 0
+    lists = [l if i != gone else l[:0] for i, l in enumerate(lists)]
+    kept = [i for i, l in enumerate(lists) if len(l)]
+    assert len(kept) == 4
+    want = K.table_of(nd.n, 4, rows, [(run.new[i], run.res[i]) for i in kept], [run.after[i] for i in kept])[0]
+    counters, missed = S.Table(nd.n), np.zeros(nd.n, dtype=np.uint64)
+    for i in kept:
+        counters.add_result(run.new[i], run.res[i], verdict=run.after[i])
+        missed += LR.apply(run.new[i], run.res[i], sched, run.before[i])[1]
+    assert int(want.t["heard"].sum()) >= 1000 and int(missed.sum()) >= 100
+    eng, dev = _engine(rsa, nd, 4, rows, em_seed=R.SEED, stats=True, sched=sched), []
+    try:
+        eng.profile_enable(1)
+        _run_batch(eng, lists, starts, air, dev)
+        eng.sync()
+        n, order = _launches(eng)
+        names = {k.split("<")[0].strip() for k in order}
+        assert names & LONE_SWEEP and "k_store_ticks" in names and not names & BATCH_SWEEP, order   # the route: tick by tick
+        assert [n.get(k) for k in BATCH_PASSES] == [1, 1, 1, 1] and not names & set(LONE_PASSES), (n, order)
+        at = [order.index(k) for k in BATCH_PASSES]
+        assert at == sorted(at) and all(at[0] > order.index(k) for k in order if k.split("<")[0].strip() in LONE_SWEEP), order
+        _check(eng, want, "tick by tick")
+        tbl, tot = eng.stats_read()
+        S.equal(tbl, counters, "tick by tick")
+        assert tot == counters.totals() == {"ticks_counted": len(kept), "ticks_skipped": 0}
+        np.testing.assert_array_equal(eng.listen_missed(), missed)
+        for i in kept:
+            got = eng.batch_result_copy(i, len(lists[i]), cap=1 << 20)
+            np.testing.assert_array_equal(got.dst, run.res[i].dst, err_msg="tick %d" % i)
+            np.testing.assert_array_equal(got.verdict, run.after[i], err_msg="tick %d" % i)
+    finally:
+        for d in dev:
+            d.free()
+        eng.close()
+
+
+_NULL = {}
+
+
+def _null_ref():
+    """the Null medium's scene under a schedule, computed once, shared and left unchanged:
+    -> (nd, kind, params, pk, oracle result, sched, verdicts after E13, missed, watch rows)"""
+    if not _NULL:
+        scene = S.scene_null()
+        nd, kind, params, pk, _, _ = scene
+        cpu = S.oracle_tick(scene)
+        sched, _ = LR.schedule(nd.n, LR.SCHED_SEED, LR.reached_receivers([(cpu, cpu.verdict)]))
+        after, missed = LR.apply(pk, cpu, sched)
+        _NULL["ref"] = (nd, kind, params, pk, cpu, sched, after, missed, K.rows_first_heard(nd.n, 4, [(pk, cpu)]))
+    return _NULL["ref"]
+
+
+def test_dense_lone_tick_with_the_three_counters(rsa, O):
+    """the Null medium's tick ends with its cells' lane masks: the schedules', the counters' and the watched links' passes run over
+    its records, once each and in this order, and rm_result_dense refuses a tick whose masks do not carry E13's verdicts"""
+    nd, kind, params, pk, cpu, sched, after, missed, rows = _null_ref()
+    want = K.table_of(nd.n, 4, rows, [(pk, cpu)], [after], sinr=False)[0]
+    counters = S.Table(nd.n)
+    counters.add_result(pk, cpu, verdict=after)
+    assert 1000 <= int(missed.sum()) <= cpu.count - 1000 and int(want.t["delivered"].sum()) < int(want.t["heard"].sum())
+    srcs = np.ascontiguousarray(pk["src"], dtype=np.int32)
+    eng, d = rsa.Engine(0), DeviceArray(srcs)
+    try:
+        configure_engine(eng, nd, kind, params)
+        eng.set_link_capacity(1 << 20)
+        eng.stats_enable()
+        eng.listen_set(sched)
+        eng.linkstats_enable(4)
+        eng.linkstats_watch(rows)
+        eng.profile_enable(1)
+        eng.tick_run_sources_device(0, TICK, d.ptr.value, len(srcs), 0, S.AIR)
+        eng.sync()
+        n, order = _launches(eng)
+        if os.environ.get("RM_DENSE_TICK") != "0":   # (a run whose knobs never take the dense form sweeps as any other medium)
+            assert any(k.startswith("k_dense_count") for k in order), order
+        assert [n.get(k) for k in LONE_PASSES[1:]] == [1, 1, 1] and "k_errmodel" not in n and not set(BATCH_PASSES) & set(n), (n, order)
+        assert order.index("k_listen") < order.index("k_stats") < order.index("k_linkstats"), order
+        _refused(rsa, eng, STATE, eng.result_dense)
+        _check(eng, want, "null, dense, three passes")
+        tbl, tot = eng.stats_read()
+        S.equal(tbl, counters, "null, dense, three passes")
+        assert tot == {"ticks_counted": 1, "ticks_skipped": 0}
+        np.testing.assert_array_equal(eng.listen_missed(), missed)
+        got = eng.result_copy(len(srcs), cap=1 << 20)
+        np.testing.assert_array_equal(got.dst, cpu.dst)
+        np.testing.assert_array_equal(got.verdict, after)
+    finally:
+        d.free()
+        eng.close()
+
+
+def test_refusal_precedence_with_all_four_on(rsa, O):
+    """a receiver partition with every pass on: the forms that ask about the frame error model name it first; a lone tick's entry
+    point asks about the three others before the tick reaches the SINR medium's own path, and names the counters.  Nothing is
+    launched and no table moves."""
+    nd, lists, starts, air, sched, run, rows, _, _ = _ref("lone", 4, R.SEED)
+    srcs = lists[0]
+    eng, d = _engine(rsa, nd, 4, rows, em_seed=R.SEED, stats=True, sched=sched), DeviceArray(srcs)
+    recs = DeviceArray(to_tx_records(rsa, nd.packets(srcs, 100 * TICK, air)))
+    try:
+        _lone(eng, "sources", d, srcs, starts[0], air)   # (the tables hold something to lose)
+        links, counters, missed = eng.linkstats_read(), eng.stats_read(), eng.listen_missed()
+        assert links[0]["heard"].any() and counters[0]["rx_heard"].any() and missed.any()
+        t = 100 * TICK
+
+        def refused(what, call, begins):
+            eng.profile_enable(1)
+            msg = _refused(rsa, eng, STATE, call)
+            assert msg.startswith("rm error %d: %s: " % (STATE, begins)), (what, msg)
+            eng.sync()
+            assert eng.profile_kernels() == {}, (what, eng.profile_kernels())
+            for got, was in zip(eng.linkstats_read() + eng.stats_read(), links + counters):
+                assert (got == was) if isinstance(was, dict) else np.array_equal(got, was), what
+            np.testing.assert_array_equal(eng.listen_missed(), missed, err_msg=what)
+
+        eng.set_partition(0, nd.n // 2)
+        refused("a batch", lambda: eng.batch_run_sources_device([t], [t + TICK], [d.ptr.value], [len(srcs)], [t], [air]),
+                "the frame error model is on")
+        refused("records on the SINR medium", lambda: eng.tick_run_records_device(t, t + TICK, recs.ptr.value, len(srcs), t + air),
+                "the frame error model is on")
+        refused("sources on the SINR medium", lambda: eng.tick_run_sources_device(t, t + TICK, d.ptr.value, len(srcs), t, air),
+                "statistics are on")
+        eng.set_partition(0, nd.n)
+        eng.set_model(1)   # a reference medium: the three counters stay on
+        assert eng.stats_enabled() and eng.listen_enabled() and eng.linkstats_enabled() == 4
+        eng.set_partition(0, nd.n // 2)
+        refused("sources on a reference medium", lambda: eng.tick_run_sources_device(t, t + TICK, d.ptr.value, len(srcs), t, air),
+                "statistics are on")
+    finally:
+        recs.free()
+        d.free()
+        eng.close()
+
+
 def test_off_launches_nothing(rsa, O):
     nd, lists, starts, air, _, run, rows, want, _ = _ref("batch", 4)
     eng, dev, d = _engine(rsa, nd, 4, rows), [], DeviceArray(lists[0])
