@@ -108,6 +108,7 @@ static int plan_nbr_cache(rm_context *c, rm::TickDev *ticks, const TickPlan *pla
     RM_HIP(nc.tick_cnt.ensure(size_t(n) * 4));
     RM_HIP(nc.hit.ensure(size_t(n) * per));
     RM_HIP(nc.fill.ensure(size_t(n) * per));
+    if (form == 1) RM_HIP(nc.unserved.ensure(size_t(n) * per));
     RM_HIP(nc.cur.ensure(size_t(n) * per));
     // (tick_cnt: zeroed by the descriptor kernels, k_store_ticks / k_fetch_ticks)
     nc.batches[form]++;
@@ -125,6 +126,7 @@ static int plan_nbr_cache(rm_context *c, rm::TickDev *ticks, const TickPlan *pla
         d.tick_cnt = nc.tick_cnt.p + size_t(b) * 4;
         d.hit = nc.hit.p + size_t(b) * per;
         d.fill = nc.fill.p + size_t(b) * per;
+        d.unserved = form == 1 ? nc.unserved.p + size_t(b) * per : nullptr;
         d.cur = nc.cur.p + size_t(b) * per;
     }
     return RM_OK;

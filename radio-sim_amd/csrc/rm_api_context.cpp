@@ -308,7 +308,7 @@ void rm_destroy(rm_context *c)
     c->d_n2n.release(); c->d_shadow_tbl.release(); c->d_air.release(); c->d_air_alt.release(); c->d_cull_ring.release(); c->d_rng.release(); c->d_ticks.release(); c->d_near_list.release(); c->d_near_cnt.release();
     nbr_cache_report(c);
     c->nc.state.release(); c->nc.off.release(); c->nc.len.release(); c->nc.tick_cnt.release(); c->nc.cur.release(); c->nc.arena.release();
-    c->nc.fill.release(); c->nc.hit.release(); c->nc.ctr.release(); c->nc.arena_rssi.release(); c->nc.arena_verdict.release();
+    c->nc.fill.release(); c->nc.unserved.release(); c->nc.hit.release(); c->nc.ctr.release(); c->nc.arena_rssi.release(); c->nc.arena_verdict.release();
     c->air.pool.release(); c->air.head.release(); c->air.tail.release(); c->air.mark.release(); c->air.bad.release();
     {
         rm_context::Overlap &o = c->ov;

@@ -397,9 +397,13 @@ struct NbrCacheDev {
     uint32_t arena_len;
     uint32_t word;             // (epoch << 1) | 1 of the running launch sequence
     // per tick of the running launch sequence
-    uint32_t *tick_cnt;        // [0] frames left to the sweep, [1] lists claimed for filling, [2] frames served from a list
+    uint32_t *tick_cnt;        // [0] frames left to the sweep, [1] lists claimed for filling, [2] frames served from a list,
+                               // [3] heard form: n_un, the frames without a hit (those of [0] and the ones that reach nobody)
     uint2 *hit;                // [n_cnt] per frame: (length + 1 of its source's list, 0: swept; the list's offset)
-    int32_t *fill;             // [n_cnt] per frame: offset of the list its candidates / records are copied to, -1: none
+    int32_t *unserved;         // [n_cnt] heard form: the n_un frames without a hit, in whatever order the pre-pass's waves arrived.
+                               // A tick without any hit ([2] == 0) has no list: its consumers take position k for frame k.
+    int32_t *fill;             // [n_cnt] offset of the list a frame's candidates / records are copied to, -1: none.  Candidates form:
+                               // by frame; heard form: by position in unserved[]
     uint32_t *cur;             // [n_cnt] per frame: candidates copied so far (candidates form)
 };
 

@@ -275,7 +275,11 @@ __global__ void __launch_bounds__(256) k_exact(const NodesDev nd, const ModelDev
 template <int MODEL, bool STOCH, int SCAN, bool SINR = false>
 __global__ void __launch_bounds__(256, (SCAN == 4 && !SINR) ? 4 : 1) k_exact_batch(const NodesDev nd, const ModelDev m, const TickDev *__restrict__ ticks)
 {
-    exact_body<MODEL, SINR, STOCH, SCAN, true>(nd, m, ticks[blockIdx.z]);
+    const TickDev &t = ticks[blockIdx.z];
+    // the source cache's heard form, a tick that left no frame to the sweep (block-uniform, as nc_nothing_to_sweep, rm_filter.hip):
+    // no shard holds an entry and no frame has a segment, so nobody reads the seg_off that the publisher would scan for
+    if (!STOCH && !SINR && t.nc.arena_rssi != nullptr && uniform_u(t.nc.tick_cnt[0]) == 0u) return;
+    exact_body<MODEL, SINR, STOCH, SCAN, true>(nd, m, t);
 }
 
 // half duplex (SINR mode): every frame on the air leaves a SELF entry in its source's list

@@ -335,6 +335,18 @@ RM_D void tick_prep_body(const NodesDev &nd, const ModelDev &m, const TickDev &t
         const int lane = threadIdx.x & 63;
         if (sm && lane == __ffsll((long long)sm) - 1) atomicAdd(&t.nc.tick_cnt[0], uint32_t(__popcll(sm)));
         if (hm && lane == __ffsll((long long)hm) - 1) atomicAdd(&t.nc.tick_cnt[2], uint32_t(__popcll(hm)));
+        // heard form (block-uniform): the tick's list of frames without a hit, the ones that reach nobody included -- what the
+        // reorder stage walks and the claim and the fill look at.  One allocation per wave; the order among waves is the atomics'.
+        if (t.nc.arena_rssi != nullptr) {
+            const uint64_t um = ballot64(h.x == 0u);
+            if (um) {
+                const int first = __ffsll((long long)um) - 1;
+                uint32_t base = 0;
+                if (lane == first) base = atomicAdd(&t.nc.tick_cnt[3], uint32_t(__popcll(um)));
+                base = uint32_t(__shfl(int(base), first));
+                if (h.x == 0u) t.nc.unserved[base + lane_prefix(um)] = e;
+            }
+        }
     }
     const float inv = prefilter_inv(m, f);
     t.p_txf[e] = f;
@@ -871,6 +883,12 @@ __global__ void __launch_bounds__(256) k_near_lists(const NodesDev nd, const Tic
     const int sb = blockIdx.x, lane = threadIdx.x & 63;
     const int n_eval = t.n_active - t.first_eval;
     if (t.near_list == nullptr) return;
+    // the source cache's heard form, a tick that left no frame to the sweep (block-uniform, as nc_nothing_to_sweep below): no
+    // frame is near to anything, the lists are empty
+    if (t.nc.arena_rssi != nullptr && uniform_u(t.nc.tick_cnt[0]) == 0u) {
+        if (threadIdx.x == 0) const_cast<uint32_t *>(t.near_cnt)[sb] = 0u;
+        return;
+    }
     if (threadIdx.x < 64) { // the union of the block's workgroup boxes and channel masks
         const int w = sb * kNearSb + lane;
         BoxUnion u = box_union_empty();

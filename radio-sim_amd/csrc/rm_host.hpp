@@ -519,7 +519,7 @@ struct rm_context : TickSlot {
     // before (heard: draw-free batches keep finished records, arena_rssi / arena_verdict beside the arena; candidates otherwise).
     struct NbrCache {
         DevBuf<uint32_t> state, off, len, tick_cnt, cur;
-        DevBuf<int32_t> arena, fill;
+        DevBuf<int32_t> arena, fill, unserved;
         DevBuf<double> arena_rssi;     // (heard form only: allocated by the first batch that takes it)
         DevBuf<uint8_t> arena_verdict;
         DevBuf<uint2> hit;

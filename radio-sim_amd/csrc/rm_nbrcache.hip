@@ -16,12 +16,13 @@ namespace rm {
 // one thread per frame: a swept frame whose source has no list in this epoch claims one (compare-and-swap on the state word: a
 // node that transmits in two ticks of the batch is filled once) and takes its room from the arena.  A source with more
 // candidates than kNcListCap, or one the arena has no room for, keeps the claim and stays uncached for the epoch.
+// Heard form, a tick with hits: one thread per entry of the tick's list of unserved frames instead (nc.unserved, rm_engine.h).
 __global__ void __launch_bounds__(256) k_nc_claim_batch(const TickDev *__restrict__ ticks)
 {
     const TickDev &t = ticks[blockIdx.z];
     if (t.nc.state == nullptr) return;
     const int n_eval = t.n_active - t.first_eval;
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e == 0) {
         atomicAdd(&t.nc.ctr[1], (unsigned long long)t.nc.tick_cnt[2]);
         atomicAdd(&t.nc.ctr[2], (unsigned long long)t.nc.tick_cnt[0]);
@@ -31,6 +32,15 @@ __global__ void __launch_bounds__(256) k_nc_claim_batch(const TickDev *__restric
     // tick_cnt[1] stays 0, so k_nc_fill_batch returns before it reads fill[], which is NOT cleared between launch sequences --
     // a tick that goes on below therefore writes fill[e] for every one of its frames.
     if (heard && uniform_u(t.nc.tick_cnt[2]) == uint32_t(n_eval)) return;
+    // heard form, a tick with hits: thread k takes the k-th entry of the tick's list of frames without a hit (nc.unserved; the
+    // pre-pass left n_un = tick_cnt[3] of them) and fill[] goes by that position -- the fill reads it the same way, and every
+    // position below n_un is written, so the rule above holds for the list as it held for the frames.  A tick without a hit has
+    // no list to follow: position k is frame k.  Workgroups beyond the list have nothing to look at (block-uniform).
+    const bool listed = heard && uniform_u(t.nc.tick_cnt[2]) != 0u;
+    const int n_walk = listed ? min(int(uniform_u(t.nc.tick_cnt[3])), n_eval) : n_eval;
+    if (int(blockIdx.x * blockDim.x) >= n_walk) return;
+    const int k = e; // the thread's position: in the list, or among the frames
+    if (listed) e = k < n_walk ? t.nc.unserved[k] : n_eval;
     const int lane = threadIdx.x & 63;
     // (a tick whose shards overflowed has gaps where runs were dropped: none of its frames leaves a list; in the heard form
     // neither does a tick whose heard links exceed the link capacity: its ordered records stop at `cap`)
@@ -38,7 +48,8 @@ __global__ void __launch_bounds__(256) k_nc_claim_batch(const TickDev *__restric
     bool mine = false;
     int s = -1;
     uint32_t cnt = 0;
-    if (e < n_eval && t.nc.hit[e].x == 0u && !dropped) {
+    // (heard: a listed frame has no hit, and neither has any frame of a tick without one)
+    if (e < n_eval && !dropped && (heard || t.nc.hit[e].x == 0u)) {
         s = t.p_src[e];
         if (s >= 0) {
             const uint32_t st = t.nc.state[s];
@@ -65,17 +76,20 @@ __global__ void __launch_bounds__(256) k_nc_claim_batch(const TickDev *__restric
         t.nc.state[s] = t.nc.word; // (this thread owns the word; read by later launch sequences only)
         if (cnt) fill = int32_t(o);
     }
-    if (e >= n_eval) return;
-    t.nc.fill[e] = fill;
+    if (k >= n_walk) return;
+    t.nc.fill[k] = fill;
     if (!heard) t.nc.cur[e] = 0u; // (candidates copied so far: the heard form's fill does not count)
     const uint64_t fm = ballot64(fill >= 0);
     if (fm && int(threadIdx.x & 63) == __ffsll((long long)fm) - 1) atomicAdd(&t.nc.tick_cnt[1], uint32_t(__popcll(fm)));
 }
 
 // the entries of the lists claimed in this launch sequence (nothing to do for a tick that claimed none)
-// Heard form: 64 frames per wave.  A claimed frame's records are contiguous and already in node order at its place in the
-// ordered arrays; all of the wave's lists are copied to the arena's columns with full lanes (no atomics; wave_copy_lists,
-// rm_device.hpp).
+// Heard form: up to 64 positions per wave (list entries in a tick with hits, else frames).  A claimed frame's records are
+// contiguous and already in node order at its place in the ordered arrays; all of the wave's lists are copied to the arena's
+// columns with full lanes (no atomics; wave_copy_lists, rm_device.hpp).  A list's positions are dealt out evenly over ALL waves
+// of the tick's grid: nearly every listed frame is claimed, and 64 of them to a wave left a tick with 28 % of its 1000 frames
+// unserved to five waves of eleven dependent load -> store spans each, where sixteen waves had shared them before there was a
+// list (this kernel's launches of such sequences, traced: 16-26 us before the list, 31-56 with 64 positions per wave).
 // Candidates form: one workgroup per shard: the shard's entries (the sweep's: the cached ones are appended afterwards) whose
 // frame fills a list go there, one atomic per run of entries of one frame.
 // Measured and dropped: 2, 4 or 8 waves (gridDim.y) sharing the 64 frames' records, each taking every P-th span, as for
@@ -87,11 +101,23 @@ __global__ void __launch_bounds__(256) k_nc_fill_batch(const TickDev *__restrict
     const TickDev &t = ticks[blockIdx.z];
     if (t.nc.state == nullptr || uniform_u(t.nc.tick_cnt[1]) == 0u) return;
     if (t.nc.arena_rssi != nullptr) { // (block-uniform; grid: frames / kBlock in x, 1 in y)
+        // positions of the tick's list of frames without a hit where the tick has hits, else its frames -- as in the claim, which
+        // wrote fill[] by the same positions.  `per` consecutive positions per wave: 64 of the frames, an even share of a list
+        // (the grid has a wave per 64 frames of the largest tick, so a share is at most 64)
+        const int n_eval = t.n_active - t.first_eval;
+        const bool listed = uniform_u(t.nc.tick_cnt[2]) != 0u;
+        const int n_walk = listed ? min(int(uniform_u(t.nc.tick_cnt[3])), n_eval) : n_eval;
         const int lane = threadIdx.x & 63;
-        const int e0 = int(blockIdx.x) * kBlock + wave_index() * 64;
-        const int e = e0 + lane;
+        const int wave = int(blockIdx.x) * (kBlock / 64) + wave_index();
+        const int n_waves = int(gridDim.x) * (kBlock / 64);
+        const int per = listed ? min(64, (n_walk + n_waves - 1) / n_waves) : 64;
+        const int e0 = wave * per;
+        if (e0 >= n_walk) return; // (wave-uniform)
+        const int k = e0 + lane;
         int32_t fo = -1;
-        if (e < t.n_active - t.first_eval) fo = t.nc.fill[e];
+        if (lane < per && k < n_walk) fo = t.nc.fill[k];
+        int e = k;
+        if (listed && fo >= 0) e = t.nc.unserved[k];
         // (claimed: the tick was not dropped, so every record of the frame lies below `cap`)
         const uint32_t cnt = fo >= 0 ? t.cursor[e - t.cnt_base] : 0u;
         const uint32_t inc = wave_inclusive_scan(cnt, lane);

@@ -19,7 +19,10 @@ namespace rm {
 // (configs[3]: 888 MB of counter traffic per 128 ticks for 45 MB of records).
 // NC (batches without draws and without SINR only: lone ticks keep their code): the source cache's heard form may be on
 // (t.nc.arena_rssi, block-uniform).  The scan of cursor[] then includes the frames served from a list -- slot_off, out_count and
-// the packets' offsets come from it -- but the walk leaves them out: k_reorder_served_batch writes their records.
+// the packets' offsets come from it -- but the walk leaves them out: k_reorder_served_batch writes their records.  A tick with
+// hits is walked by its list of frames WITHOUT one (nc.unserved, n_un = tick_cnt[3] entries, written by the pre-pass):
+// frame_of(k) is then a position in that list, and a workgroup whose first position lies beyond it has nothing to rank.  A
+// tick without any hit has no list to follow -- position k is frame k -- and runs as it did before there was one.
 template <bool STOCH, bool SINR, int MODE, bool NC = false>
 RM_D void reorder_body(const ModelDev &m, const TickDev &t, const int cwl)
 {
@@ -35,8 +38,17 @@ RM_D void reorder_body(const ModelDev &m, const TickDev &t, const int cwl)
         if (t.fl_map == nullptr) write_pkt_interference(m, t, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
         return;
     }
-    const int lane = threadIdx.x & 63;
     const int n_new = t.n_active - t.first_new;
+    // the walk's positions: the tick's frames, or the entries of its list of unserved frames (block-uniform)
+    const bool listed = NC && nc_heard && uniform_u(t.nc.tick_cnt[2]) != 0u;
+    const int n_walk = (NC && listed) ? min(int(uniform_u(t.nc.tick_cnt[3])), n_new) : n_new;
+    // ... and a workgroup whose first position (wave 0's: every other one is larger) lies beyond the list leaves like the one
+    // above: most workgroups of a nearly served tick, each of which would redo the tick's scan for frames it does not have
+    if (NC && listed && !publisher && ((int64_t(blockIdx.x) * 4) << cwl) >= int64_t(n_walk)) {
+        if (t.fl_map == nullptr) write_pkt_interference(m, t, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+        return;
+    }
+    const int lane = threadIdx.x & 63;
     constexpr bool kRegScan = (MODE == 3 || MODE == 4);
     SmallCounts<scan_per(MODE)> pre{};
     if (kRegScan) pre = small_scan_load<scan_per(MODE)>(t.cursor, t.n_cnt);
@@ -47,15 +59,15 @@ RM_D void reorder_body(const ModelDev &m, const TickDev &t, const int cwl)
     const int G = int(gridDim.x) * 4;
     // the wave's k-th frame: run k >> cwl of its runs, place k & (2^cwl - 1) in it (increasing in k)
     auto frame_of = [&](const int k) -> int64_t { return ((int64_t(W) + int64_t(k >> cwl) * G) << cwl) + int64_t(k & ((1 << cwl) - 1)); };
-    const int64_t q0 = frame_of(0);
+    int64_t q0 = frame_of(0); // (NC: the prefetched FRAME from here on, -1 where nothing was prefetched: a position is no frame)
     uint32_t src0 = 0, len = 0;
     int mine = 0x7fffffff, in_e = 0;
     double in_rssi = 0.0, in_prob = 1.0;
     uint8_t v = 0;
-    if (q0 < n_new) {
+    if (q0 < n_walk) {
+        if (NC && listed) q0 = uniform_i(t.nc.unserved[int(q0)]);
         src0 = uniform_u(t.seg_off[int(q0) + t.shift]);
         len = uniform_u(t.cursor[int(q0) + t.shift]);
-        if (NC && nc_heard && uniform_u(t.nc.hit[int(q0)].x) != 0u) len = 0u; // (served: cursor is its list's length, it has no segment)
         if (uint32_t(lane) < len) {
             const uint32_t o = src0 + lane;
             mine = t.a_dst[o];
@@ -64,6 +76,8 @@ RM_D void reorder_body(const ModelDev &m, const TickDev &t, const int cwl)
             if (STOCH) in_prob = t.a_prob[o];
             if (SINR && !t.seg_ordered && t.acc_lo == nullptr) in_e = t.a_e[o]; // (ordered segments and summed ticks carry sinr and verdict themselves)
         }
+    } else if (NC) {
+        q0 = -1;
     }
 
     if (MODE == 1 || kRegScan) {
@@ -94,15 +108,17 @@ RM_D void reorder_body(const ModelDev &m, const TickDev &t, const int cwl)
     // two dependent global loads per frame (offset, count) was most of this stage's time on a rank's share of a tick.
     constexpr bool kLdsCounts = (MODE == 1 || kRegScan);
     for (int ib = 0;; ib += 64) { // wave-uniform
-        if (frame_of(ib) >= n_new) break;
+        if (frame_of(ib) >= n_walk) break;
         uint32_t my_len = 0, my_src = 0;
+        int my_q = 0; // (NC) the lane's frame: its position's entry in the list
         uint64_t todo = ~0ull;
         if (kLdsCounts) {
-            const int64_t qi = frame_of(ib + lane);
-            if (qi < n_new) {
+            int64_t qi = frame_of(ib + lane);
+            if (qi < n_walk) {
+                if (NC && listed) qi = t.nc.unserved[int(qi)]; // (everything listed is unserved: it has a segment, or no link at all)
+                if (NC) my_q = int(qi);
                 const int sl = int(qi) + t.shift;
                 my_len = s_off[sl + 1] - s_off[sl];
-                if (NC && nc_heard && t.nc.hit[int(qi)].x != 0u) my_len = 0u; // served from its source's list
                 if (my_len) my_src = t.seg_off[sl];
             }
             // A frame with a handful of heard links (sixteen channels: three per frame) is its LANE's own business: the lane ranks its
@@ -149,8 +165,8 @@ RM_D void reorder_body(const ModelDev &m, const TickDev &t, const int cwl)
         const int i = __ffsll((long long)todo) - 1;
         todo &= todo - 1;
         const int64_t q64 = frame_of(ib + i);
-        if (q64 >= n_new) break; // (MODE 2 walks every frame of the block)
-        const int q = int(q64);
+        if (q64 >= n_walk) break; // (MODE 2 walks every frame of the block)
+        const int q = NC ? __builtin_amdgcn_readlane(my_q, i) : int(q64);
         const int slot = q + t.shift;
         const int q_pub = t.fl_map ? uniform_i(t.fl_map[q]) : q; // the packet's number in the result (a rank's frame list: global)
         if (kLdsCounts) {
