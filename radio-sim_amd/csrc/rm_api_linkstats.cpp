@@ -66,19 +66,6 @@ int linkstats_nodes_changed(rm_context *c)
 
 static size_t linkstats_entries(const rm_context *c) { return size_t(std::max(c->lk.n, 1)) * size_t(c->lk.K); }
 
-// the pinned, host-mapped block of a list call: n rows of K entries (a list read's entries out; a list watch's peers in), then the
-// totals, then the list.  The stream is idle when this returns: the caller may overwrite the block
-static int linkstats_host_block(rm_context *c, int32_t n, char **h_rows, rm_stats_totals **h_totals, int32_t **h_nodes)
-{
-    PinnedBlock &h = c->lk.h;
-    // (sized for eight slots a row: the block outlives a change of K)
-    RM_TRY(h.ensure(c->stream, size_t(n), [](size_t cap) { return cap * 8u * sizeof(rm_link_stats) + pad64(sizeof(rm_stats_totals)) + pad64(cap * 4); }));
-    *h_rows = h.p;
-    *h_totals = reinterpret_cast<rm_stats_totals *>(h.p + h.cap * 8u * sizeof(rm_link_stats));
-    *h_nodes = reinterpret_cast<int32_t *>(h.p + h.cap * 8u * sizeof(rm_link_stats) + pad64(sizeof(rm_stats_totals)));
-    return RM_OK;
-}
-
 int linkstats_have(const rm_context *c)
 {
     if (!linkstats_on(c) || c->lk.n < 0) return fail(RM_ERR_STATE, "no watched-link statistics: rm_linkstats_enable(ctx, K) comes first");
@@ -134,15 +121,12 @@ int rm_linkstats_watch(rm_context *c, const int32_t *nodes, int32_t n, const int
         RM_HIP(hipStreamSynchronize(c->stream));
         return RM_OK;
     }
-    // a list: one small launch that reads rows and list from the host-mapped block
-    char *h_rows;
-    rm_stats_totals *h_totals;
-    int32_t *h_nodes;
-    RM_TRY(linkstats_host_block(c, n, &h_rows, &h_totals, &h_nodes));
-    std::memcpy(h_rows, peers, size_t(n) * K * 4);
-    std::memcpy(h_nodes, nodes, size_t(n) * 4);
+    // a list: the peer rows and the list staged in the block (rows of K * 4 bytes), one launch of the watch rule, not waited for
+    RM_TRY(lk.h.ensure(c->stream, size_t(n), K * 4));
+    std::memcpy(lk.h.rows(), peers, size_t(n) * K * 4);
+    std::memcpy(lk.h.nodes(), nodes, size_t(n) * 4);
     for (int32_t r = 0; r < n; ++r) std::memcpy(lk.host.data() + size_t(nodes[r]) * K, peers + size_t(r) * K, K * 4);
-    RM_HIP(rm::launch_linkstats_scatter(c->stream, lk.peer.p, lk.table.p, lk.n, lk.K, h_nodes, n, reinterpret_cast<const int32_t *>(h_rows)));
+    RM_HIP(rm::launch_linkstats_scatter(c->stream, lk.peer.p, lk.table.p, lk.n, lk.K, lk.h.nodes(), n, reinterpret_cast<const int32_t *>(lk.h.rows())));
     return RM_OK;
 }
 
@@ -165,27 +149,10 @@ int rm_linkstats_read(rm_context *c, const int32_t *nodes, int32_t n, rm_link_st
 {
     if (!c || n < 0 || (n > 0 && !out)) return fail(RM_ERR_INVALID, "bad arguments");
     RM_TRY(linkstats_have(c));
-    const rm_context::LinkStats &lk = c->lk;
+    rm_context::LinkStats &lk = c->lk;
     RM_TRY(check_node_list(nodes, n, lk.n));
     RM_HIP(hipSetDevice(c->device));
-    const size_t K = size_t(lk.K);
-    if (!nodes || n == 0) { // the whole table in node order (or the totals alone): copies on the stream, one synchronisation
-        if (n > 0) RM_HIP(hipMemcpyAsync(out, lk.table.p, size_t(n) * K * sizeof(rm_link_stats), hipMemcpyDeviceToHost, c->stream));
-        if (totals) RM_HIP(hipMemcpyAsync(totals, lk.totals.p, sizeof(rm_stats_totals), hipMemcpyDeviceToHost, c->stream));
-        RM_HIP(hipStreamSynchronize(c->stream));
-        return RM_OK;
-    }
-    // a list: one small gather launch reads it from the host-mapped block and writes the entries and the totals there
-    char *h_rows;
-    rm_stats_totals *h_totals;
-    int32_t *h_nodes;
-    RM_TRY(linkstats_host_block(c, n, &h_rows, &h_totals, &h_nodes));
-    std::memcpy(h_nodes, nodes, size_t(n) * 4);
-    RM_HIP(rm::launch_linkstats_gather(c->stream, linkstats_dev(c), h_nodes, n, reinterpret_cast<rm_link_stats *>(h_rows), h_totals));
-    RM_HIP(hipStreamSynchronize(c->stream));
-    std::memcpy(out, h_rows, size_t(n) * K * sizeof(rm_link_stats));
-    if (totals) *totals = *h_totals;
-    return RM_OK;
+    return rows_read(c, lk.h, lk.table.p, lk.K * int(sizeof(rm_link_stats) / 8), lk.n, nodes, n, out, lk.totals.p, totals);
 }
 
 int rm_linkstats_reset(rm_context *c)

@@ -50,17 +50,6 @@ static int listen_make(rm_context *c)
     return RM_OK;
 }
 
-// the pinned, host-mapped block of a list call: n records (a list update's schedules in, or a list read's counts out), then the list.
-// The stream is idle when this returns (a set's scatter, a read's gather may have been reading the block): the caller may overwrite it
-static int listen_host_block(rm_context *c, int32_t n, char **h_recs, int32_t **h_nodes)
-{
-    PinnedBlock &h = c->ls.h;
-    RM_TRY(h.ensure(c->stream, size_t(n), [](size_t cap) { return pad64(cap * sizeof(rm_listen_schedule)) + pad64(cap * 4); }));
-    *h_recs = h.p;
-    *h_nodes = reinterpret_cast<int32_t *>(h.p + pad64(h.cap * sizeof(rm_listen_schedule)));
-    return RM_OK;
-}
-
 static int listen_have(const rm_context *c)
 {
     if (c->ls.n < 0) return fail(RM_ERR_STATE, "no listening schedules: rm_listen_set comes first");
@@ -94,16 +83,9 @@ int rm_listen_set(rm_context *c, const int32_t *nodes, int32_t n, const rm_liste
             RM_HIP(hipStreamSynchronize(c->stream));
         }
     } else if (n > 0) {
-        // a list: applied to the host's copy in order (the last entry of a node wins), then one small scatter launch that reads
-        // every entry with its node's final record from the host-mapped block -- duplicates write equal values
+        // a list: applied to the host's copy in order (the last entry of a node wins), and every entry staged from that copy
         for (int32_t k = 0; k < n; ++k) ls.host[size_t(nodes[k])] = sched[k];
-        char *h_recs;
-        int32_t *h_nodes;
-        RM_TRY(listen_host_block(c, n, &h_recs, &h_nodes));
-        rm_listen_schedule *h_sched = reinterpret_cast<rm_listen_schedule *>(h_recs);
-        for (int32_t k = 0; k < n; ++k) h_sched[k] = ls.host[size_t(nodes[k])];
-        std::memcpy(h_nodes, nodes, size_t(n) * 4);
-        RM_HIP(rm::launch_listen_scatter(c->stream, ls.sched.p, ls.n, h_nodes, n, h_sched));
+        RM_TRY(rows_write<rm_listen_schedule>(c, ls.h, ls.sched.p, ls.n, nodes, n, ls.host.data(), nodes));
     }
     ls.on = true;
     return RM_OK;
@@ -136,22 +118,8 @@ int rm_listen_missed_read(rm_context *c, const int32_t *nodes, int32_t n, uint64
     if (!c || n < 0 || (n > 0 && !out)) return fail(RM_ERR_INVALID, "bad arguments");
     RM_TRY(listen_have(c));
     RM_TRY(check_node_list(nodes, n, c->ls.n));
-    if (n == 0) return RM_OK;
     RM_HIP(hipSetDevice(c->device));
-    if (!nodes) { // the whole table in node order: one copy on the stream, one synchronisation
-        RM_HIP(hipMemcpyAsync(out, c->ls.missed.p, size_t(n) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-        RM_HIP(hipStreamSynchronize(c->stream));
-        return RM_OK;
-    }
-    // a list: one small gather launch reads it from the host-mapped block and writes the counts there
-    char *h_recs;
-    int32_t *h_nodes;
-    RM_TRY(listen_host_block(c, n, &h_recs, &h_nodes));
-    std::memcpy(h_nodes, nodes, size_t(n) * 4);
-    RM_HIP(rm::launch_listen_gather(c->stream, listen_dev(c), h_nodes, n, reinterpret_cast<uint64_t *>(h_recs)));
-    RM_HIP(hipStreamSynchronize(c->stream));
-    std::memcpy(out, h_recs, size_t(n) * sizeof(uint64_t));
-    return RM_OK;
+    return rows_read(c, c->ls.h, c->ls.missed.p, 1, c->ls.n, nodes, n, out, nullptr, nullptr);
 }
 
 int rm_listen_missed_reset(rm_context *c)

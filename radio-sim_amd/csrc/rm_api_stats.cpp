@@ -37,18 +37,6 @@ int stats_nodes_changed(rm_context *c)
     return stats_size(c);
 }
 
-// the pinned, host-mapped block of a list read: records out, then the totals, then the list in.  (The block waits for the stream
-// whether it grows or not; the one caller waits for it again behind its launch, so the wait here finds little left to wait for)
-static int stats_host_block(rm_context *c, int32_t n, rm_node_stats **h_out, rm_stats_totals **h_totals, int32_t **h_nodes)
-{
-    PinnedBlock &h = c->st.h;
-    RM_TRY(h.ensure(c->stream, size_t(n), [](size_t cap) { return cap * sizeof(rm_node_stats) + pad64(sizeof(rm_stats_totals)) + pad64(cap * 4); }));
-    *h_out = reinterpret_cast<rm_node_stats *>(h.p);
-    *h_totals = reinterpret_cast<rm_stats_totals *>(h.p + h.cap * sizeof(rm_node_stats));
-    *h_nodes = reinterpret_cast<int32_t *>(h.p + h.cap * sizeof(rm_node_stats) + pad64(sizeof(rm_stats_totals)));
-    return RM_OK;
-}
-
 static int stats_have(const rm_context *c)
 {
     if (c->st.n < 0) return fail(RM_ERR_STATE, "no statistics: rm_stats_enable(ctx, 1) comes first");
@@ -89,26 +77,10 @@ int rm_stats_read(rm_context *c, const int32_t *nodes, int32_t n, rm_node_stats 
 {
     if (!c || n < 0 || (n > 0 && !out)) return fail(RM_ERR_INVALID, "bad arguments");
     RM_TRY(stats_have(c));
-    const rm_context::Stats &st = c->st;
+    rm_context::Stats &st = c->st;
     RM_TRY(check_node_list(nodes, n, st.n));
     RM_HIP(hipSetDevice(c->device));
-    if (!nodes || n == 0) { // the whole table in node order (or the totals alone): copies on the stream, one synchronisation
-        if (n > 0) RM_HIP(hipMemcpyAsync(out, st.table.p, size_t(n) * sizeof(rm_node_stats), hipMemcpyDeviceToHost, c->stream));
-        if (totals) RM_HIP(hipMemcpyAsync(totals, st.totals.p, sizeof(rm_stats_totals), hipMemcpyDeviceToHost, c->stream));
-        RM_HIP(hipStreamSynchronize(c->stream));
-        return RM_OK;
-    }
-    // a list: one small gather launch reads it from the host-mapped block and writes the records and the totals there
-    rm_node_stats *h_out;
-    rm_stats_totals *h_totals;
-    int32_t *h_nodes;
-    RM_TRY(stats_host_block(c, n, &h_out, &h_totals, &h_nodes));
-    std::memcpy(h_nodes, nodes, size_t(n) * 4);
-    RM_HIP(rm::launch_stats_gather(c->stream, stats_dev(c), h_nodes, n, h_out, h_totals));
-    RM_HIP(hipStreamSynchronize(c->stream));
-    std::memcpy(out, h_out, size_t(n) * sizeof(rm_node_stats));
-    if (totals) *totals = *h_totals;
-    return RM_OK;
+    return rows_read(c, st.h, st.table.p, sizeof(rm_node_stats) / 8, st.n, nodes, n, out, st.totals.p, totals);
 }
 
 int rm_stats_device(rm_context *c, const rm_node_stats **dev_table, const rm_stats_totals **dev_totals)

@@ -5,8 +5,6 @@
 // into the source lists those calls take.  Everything here sets, clears, reads and generates.
 #include "rm_host.hpp"
 
-#include <unordered_map>
-
 using namespace rmh;
 
 namespace rmh {
@@ -52,17 +50,6 @@ static int traffic_make(rm_context *c)
     return RM_OK;
 }
 
-// the pinned, host-mapped block of a list call: n records (a list update's schedules in, or a list read's out), then the list.
-// The stream is idle when this returns: the caller may overwrite the block
-static int traffic_host_block(rm_context *c, int32_t n, rm_traffic_schedule **h_recs, int32_t **h_nodes)
-{
-    PinnedBlock &h = c->tf.h;
-    RM_TRY(h.ensure(c->stream, size_t(n), [](size_t cap) { return pad64(cap * sizeof(rm_traffic_schedule)) + pad64(cap * 4); }));
-    *h_recs = reinterpret_cast<rm_traffic_schedule *>(h.p);
-    *h_nodes = reinterpret_cast<int32_t *>(h.p + pad64(h.cap * sizeof(rm_traffic_schedule)));
-    return RM_OK;
-}
-
 static int traffic_have(const rm_context *c)
 {
     if (c->tf.n < 0) return fail(RM_ERR_STATE, "no traffic schedules: rm_traffic_set comes first");
@@ -102,17 +89,8 @@ static int traffic_write(rm_context *c, const int32_t *nodes, int32_t n, const r
             RM_HIP(hipMemcpyAsync(tf.sched.p, sched, size_t(n) * sizeof(rm_traffic_schedule), hipMemcpyHostToDevice, c->stream));
             RM_HIP(hipStreamSynchronize(c->stream));
         }
-    } else if (n > 0) {
-        // a list: one small scatter launch that reads it from the host-mapped block, every entry staged with its node's final
-        // record (the last entry of a node wins), so duplicates write equal values
-        rm_traffic_schedule *h_sched;
-        int32_t *h_nodes;
-        RM_TRY(traffic_host_block(c, n, &h_sched, &h_nodes));
-        std::unordered_map<int32_t, int32_t> last;
-        for (int32_t k = 0; k < n; ++k) last[nodes[k]] = k;
-        for (int32_t k = 0; k < n; ++k) h_sched[k] = sched[last[nodes[k]]];
-        std::memcpy(h_nodes, nodes, size_t(n) * 4);
-        RM_HIP(rm::launch_traffic_scatter(c->stream, tf.sched.p, tf.n, h_nodes, n, h_sched));
+    } else if (n > 0) { // a list: every entry staged with its node's final record (the last entry of a node wins)
+        RM_TRY(rows_write<rm_traffic_schedule>(c, tf.h, tf.sched.p, tf.n, nodes, n, sched, rows_final(tf.h, nodes, n, tf.n)));
     }
     return RM_OK;
 }
@@ -151,21 +129,8 @@ int rm_traffic_get(rm_context *c, const int32_t *nodes, int32_t n, rm_traffic_sc
     if (!c || n < 0 || (n > 0 && !out)) return fail(RM_ERR_INVALID, "bad arguments");
     RM_TRY(traffic_have(c));
     RM_TRY(check_node_list(nodes, n, c->tf.n));
-    if (n == 0) return RM_OK;
     RM_HIP(hipSetDevice(c->device));
-    if (!nodes) { // the whole table in node order: one copy on the stream, one synchronisation
-        RM_HIP(hipMemcpyAsync(out, c->tf.sched.p, size_t(n) * sizeof(rm_traffic_schedule), hipMemcpyDeviceToHost, c->stream));
-        RM_HIP(hipStreamSynchronize(c->stream));
-        return RM_OK;
-    }
-    rm_traffic_schedule *h_sched;
-    int32_t *h_nodes;
-    RM_TRY(traffic_host_block(c, n, &h_sched, &h_nodes));
-    std::memcpy(h_nodes, nodes, size_t(n) * 4);
-    RM_HIP(rm::launch_traffic_gather(c->stream, c->tf.sched.p, c->tf.n, h_nodes, n, h_sched));
-    RM_HIP(hipStreamSynchronize(c->stream));
-    std::memcpy(out, h_sched, size_t(n) * sizeof(rm_traffic_schedule));
-    return RM_OK;
+    return rows_read(c, c->tf.h, c->tf.sched.p, sizeof(rm_traffic_schedule) / 8, c->tf.n, nodes, n, out, nullptr, nullptr);
 }
 
 int rm_traffic_clear(rm_context *c)

@@ -898,31 +898,25 @@ hipError_t launch_dense_write(hipStream_t s, const ModelDev &m, const TickDev &t
 hipError_t launch_errmodel(hipStream_t s, const EmDev &em, const TickDev &t);
 hipError_t launch_errmodel_batch(hipStream_t s, const EmDev &em, int n, const TickDev *dev_ticks);
 
-// (rm_stats.hip) the traffic counters' pass over one finished result slot / over the n slots of a batch in one launch, and the
-// gather of listed nodes' records (and the totals) into a host-mapped block
+// (rm_stats.hip) the traffic counters' pass over one finished result slot / over the n slots of a batch in one launch
 hipError_t launch_stats(hipStream_t s, const StatsDev &sd, const TickDev &t);
 hipError_t launch_stats_batch(hipStream_t s, const StatsDev &sd, int n, const TickDev *dev_ticks);
-hipError_t launch_stats_gather(hipStream_t s, const StatsDev &sd, const int32_t *nodes, int n, rm_node_stats *out, rm_stats_totals *totals_out);
 
-// (rm_listen.hip) the listening schedules' pass over one finished result slot / over the n slots of a batch in one launch; the
-// scatter of a list update from a host-mapped block (entry k: sched[k] to node nodes[k]) and the gather of listed nodes' missed counts
+// (rm_listen.hip) the listening schedules' pass over one finished result slot / over the n slots of a batch in one launch
 hipError_t launch_listen(hipStream_t s, const ListenDev &ld, const TickDev &t);
 hipError_t launch_listen_batch(hipStream_t s, const ListenDev &ld, int n, const TickDev *dev_ticks);
-hipError_t launch_listen_scatter(hipStream_t s, rm_listen_schedule *table, int n_nodes, const int32_t *nodes, int n, const rm_listen_schedule *sched);
-hipError_t launch_listen_gather(hipStream_t s, const ListenDev &ld, const int32_t *nodes, int n, uint64_t *out);
 bool host_listen_valid(const rm_listen_schedule &s);
 bool host_listen_at(const rm_listen_schedule &s, int64_t t_us);
 
 // (rm_linkstats.hip) the watched-link statistics' pass over one finished result slot / over the n slots of a batch in one launch;
 // the fill of new tables (every slot empty, every entry cleared; peers == nullptr: the entries alone); the watch rule over n rows
 // (row r: new_peers[r][K] for node nodes[r], or node r with nodes == nullptr -- a slot whose peer changes is written and its entry
-// cleared); the gather of listed nodes' entries and the totals
+// cleared)
 hipError_t launch_linkstats(hipStream_t s, const LinkStatsDev &ld, const TickDev &t);
 hipError_t launch_linkstats_batch(hipStream_t s, const LinkStatsDev &ld, int n, const TickDev *dev_ticks);
 hipError_t launch_linkstats_clear(hipStream_t s, int32_t *peers, rm_link_stats *table, size_t n_entries);
 hipError_t launch_linkstats_scatter(hipStream_t s, int32_t *peer, rm_link_stats *table, int n_nodes, int K, const int32_t *nodes, int n,
                                     const int32_t *new_peers);
-hipError_t launch_linkstats_gather(hipStream_t s, const LinkStatsDev &ld, const int32_t *nodes, int n, rm_link_stats *out, rm_stats_totals *totals_out);
 int64_t host_linkstats_q8(double x);
 
 // (rm_traffic.hip) the traffic generator.  The node table is cut into `units` runs of `chunk`
@@ -946,11 +940,16 @@ struct TrafficGen {
 };
 void traffic_geometry(int n_nodes, int *units, int *chunk);
 hipError_t launch_traffic_generate(hipStream_t s, const TrafficGen &g);
-// the scatter of a list update from a host-mapped block (entry k: sched[k] to node nodes[k]) and the gather of listed nodes' records
-hipError_t launch_traffic_scatter(hipStream_t s, rm_traffic_schedule *table, int n_nodes, const int32_t *nodes, int n, const rm_traffic_schedule *sched);
-hipError_t launch_traffic_gather(hipStream_t s, const rm_traffic_schedule *table, int n_nodes, const int32_t *nodes, int n, rm_traffic_schedule *out);
 bool host_traffic_valid(const rm_traffic_schedule &s);
 int64_t host_traffic_due(const rm_traffic_schedule &s, uint64_t seed, int32_t node, int64_t k);
+
+// (rm_rows.hip) rows of a per-node table (`words` 64-bit words per node index, n_rows of them) through a node list in a host-mapped
+// block: the gather writes row nodes[k] to entry k of `out` (a node outside the table: zeros) and, with totals_out, copies the
+// totals; the scatter writes entry k of `src` to row nodes[k] (a node outside the table: skipped).  One grid rule for both: one lane
+// per word, 256-thread workgroups, 1 .. 64 of them; nothing to move (and no totals asked for): no launch
+hipError_t launch_rows_gather(hipStream_t s, const int64_t *table, int words, int n_rows, const int32_t *nodes, int n, int64_t *out,
+                              const rm_stats_totals *totals, rm_stats_totals *totals_out);
+hipError_t launch_rows_scatter(hipStream_t s, int64_t *table, int words, int n_rows, const int32_t *nodes, int n, const int64_t *src);
 
 // (rm_neighbors.hip) the neighbour query: one wave per queried entry.  list == nullptr: all
 // nodes, entry e is the node at engine position e and its row is the node's (n == n_nodes == n_rx); otherwise entry e is node

@@ -70,27 +70,38 @@ template <typename T> struct DevBuf {
     }
 };
 
-// The pinned, host-mapped block a list call is staged through (node list in; records in or out), counted in list entries.
+size_t pad64(size_t v);
+
+// The pinned, host-mapped block a list call is staged through, counted in bytes, in ONE layout: n rows of row_bytes (records in or
+// out), then one rm_stats_totals (out), then the node list (in).
 struct PinnedBlock {
     char *p = nullptr;
-    size_t cap = 0; // entries the block has room for
-    // room for n entries, grown by half (at least 256 entries); bytes(cap) is the block's size with room for cap entries.  The
-    // stream is idle when this returns: no earlier list call's launch reads or writes the block, the caller may overwrite it
-    template <typename Bytes> int ensure(hipStream_t s, size_t n, Bytes bytes)
+    size_t bytes = 0;
+    size_t o_totals = 0, o_nodes = 0; // where the last ensure laid the totals and the list
+    std::vector<int32_t> last;        // (rows_write: by node index, the last list entry that names the node)
+    // room for n rows of row_bytes, grown by half (at least 7 KiB: 256 entries of the smallest table's list update).  The stream
+    // is idle when this returns, grown or not: no earlier list call's launch reads or writes the block, the caller may overwrite it
+    int ensure(hipStream_t s, size_t n, size_t row_bytes)
     {
         RM_HIP(hipStreamSynchronize(s));
-        if (cap >= n && p) return RM_OK;
+        o_totals = pad64(n * row_bytes);
+        o_nodes = o_totals + pad64(sizeof(rm_stats_totals));
+        const size_t need = o_nodes + pad64(n * 4);
+        if (bytes >= need && p) return RM_OK;
         release();
-        const size_t want = std::max<size_t>(n + n / 2, 256);
-        RM_HIP(hipHostMalloc(reinterpret_cast<void **>(&p), bytes(want), hipHostMallocMapped));
-        cap = want;
+        const size_t want = std::max<size_t>(need + need / 2, 256 * (sizeof(rm_listen_schedule) + 4));
+        RM_HIP(hipHostMalloc(reinterpret_cast<void **>(&p), want, hipHostMallocMapped));
+        bytes = want;
         return RM_OK;
     }
+    char *rows() const { return p; }
+    rm_stats_totals *totals() const { return reinterpret_cast<rm_stats_totals *>(p + o_totals); }
+    int32_t *nodes() const { return reinterpret_cast<int32_t *>(p + o_nodes); }
     void release()
     {
         if (p) (void)hipHostFree(p);
         p = nullptr;
-        cap = 0;
+        bytes = 0;
     }
 };
 
@@ -202,7 +213,7 @@ struct rm_context : TickSlot {
         DevBuf<int32_t> peer, stage;
         DevBuf<rm_link_stats> table;
         DevBuf<rm_stats_totals> totals;
-        PinnedBlock h; // (counted in rows)
+        PinnedBlock h;
         // rm_linkstats_watch_device (rm_api_neighbors.cpp): the rows never pass through the host, so its copy is refreshed from the
         // device's table when somebody next reads it; the validation's per-node marks, its stamp and its pinned flag word
         bool host_stale = false;
@@ -805,6 +816,59 @@ inline int check_node_list(const int32_t *nodes, int32_t n, int32_t n_nodes)
     if (nodes)
         for (int32_t k = 0; k < n; ++k)
             if (nodes[k] < 0 || nodes[k] >= n_nodes) return fail(RM_ERR_INVALID, "node index out of range");
+    return RM_OK;
+}
+// The tables of these calls are rows of `words` 64-bit words per node index (n_rows of them), and a list call moves rows through
+// the table's PinnedBlock with the kernels of rm_rows.hip.
+//
+// A read of n rows into `out`, and of the totals where the table has them (dev_totals) and the caller asks (totals).  Without a
+// list (the whole table in node order) or with n == 0 (the totals alone): copies on the stream, one synchronisation.  With a
+// list: the list staged in the block, one gather launch, one synchronisation, then the copy out of the block
+inline int rows_read(rm_context *c, PinnedBlock &h, const void *table, int words, int32_t n_rows, const int32_t *nodes, int32_t n, void *out,
+                     const rm_stats_totals *dev_totals, rm_stats_totals *totals)
+{
+    const size_t row_bytes = size_t(words) * 8;
+    if (!dev_totals) totals = nullptr;
+    if (!nodes || n == 0) {
+        if (n > 0) RM_HIP(hipMemcpyAsync(out, table, size_t(n) * row_bytes, hipMemcpyDeviceToHost, c->stream));
+        if (totals) RM_HIP(hipMemcpyAsync(totals, dev_totals, sizeof(rm_stats_totals), hipMemcpyDeviceToHost, c->stream));
+        RM_HIP(hipStreamSynchronize(c->stream));
+        return RM_OK;
+    }
+    RM_TRY(h.ensure(c->stream, size_t(n), row_bytes));
+    std::memcpy(h.nodes(), nodes, size_t(n) * 4);
+    RM_HIP(rm::launch_rows_gather(c->stream, static_cast<const int64_t *>(table), words, n_rows, h.nodes(), n, reinterpret_cast<int64_t *>(h.rows()),
+                                  dev_totals, totals ? h.totals() : nullptr));
+    RM_HIP(hipStreamSynchronize(c->stream));
+    std::memcpy(out, h.rows(), size_t(n) * row_bytes);
+    if (totals) *totals = *h.totals();
+    return RM_OK;
+}
+// by list entry, the last entry that names the same node: entry k of a list update is staged from record rows_final(..)[k], so the
+// last entry of a node wins (the list is validated: every node is below n_rows).  Lives in the block until its next list update
+inline const int32_t *rows_final(PinnedBlock &h, const int32_t *nodes, int32_t n, int32_t n_rows)
+{
+    std::vector<int32_t> &v = h.last; // [n_rows] by node, then [n] by entry; only the nodes this list names are written and read
+    v.resize(size_t(n_rows) + size_t(n));
+    for (int32_t k = 0; k < n; ++k) v[size_t(nodes[k])] = k;
+    for (int32_t k = 0; k < n; ++k) v[size_t(n_rows) + size_t(k)] = v[size_t(nodes[k])];
+    return v.data() + n_rows;
+}
+// An update of the rows of a VALIDATED list: entry k staged in the block with row rec_row[k] of `recs` -- its node's FINAL record
+// (rows_final over the caller's records, or the list itself over a host copy the list has been applied to), so duplicates write
+// equal values -- then the list, and one scatter launch that is not waited for.  (The row is the record's type, so that staging
+// a row is a copy of known size: with the size a run-time value, a list update of 100 000 schedules took a third longer)
+template <typename Rec>
+int rows_write(rm_context *c, PinnedBlock &h, Rec *table, int32_t n_rows, const int32_t *nodes, int32_t n, const Rec *recs, const int32_t *rec_row)
+{
+    static_assert(sizeof(Rec) % 8 == 0, "a row is whole 64-bit words");
+    if (n < 1) return RM_OK;
+    RM_TRY(h.ensure(c->stream, size_t(n), sizeof(Rec)));
+    Rec *rows = reinterpret_cast<Rec *>(h.rows());
+    for (int32_t k = 0; k < n; ++k) rows[k] = recs[rec_row[k]];
+    std::memcpy(h.nodes(), nodes, size_t(n) * 4);
+    RM_HIP(rm::launch_rows_scatter(c->stream, reinterpret_cast<int64_t *>(table), int(sizeof(Rec) / 8), n_rows, h.nodes(), n,
+                                   reinterpret_cast<const int64_t *>(rows)));
     return RM_OK;
 }
 // a context made under RM_GRAPH=1 takes none of the extensions; `why` is the clause that names what is refused

@@ -122,22 +122,6 @@ __global__ void __launch_bounds__(256) k_linkstats_scatter(int32_t *__restrict__
     }
 }
 
-// rm_linkstats_read with a list: the listed nodes' entries (one 64-bit word per lane) and the totals into the host-mapped block
-__global__ void __launch_bounds__(256) k_linkstats_gather(const LinkStatsDev ld, const int32_t *__restrict__ nodes, int n, rm_link_stats *__restrict__ out,
-                                                          rm_stats_totals *__restrict__ totals_out)
-{
-    const size_t stride = size_t(gridDim.x) * blockDim.x;
-    const size_t per_row = size_t(ld.K) * 6u;
-    for (size_t e = size_t(blockIdx.x) * blockDim.x + threadIdx.x; e < size_t(n) * per_row; e += stride) {
-        const size_t r = e / per_row;
-        const int32_t node = nodes[r];
-        int64_t v = cleared_word(uint32_t(e % 6u));
-        if (node >= 0 && node < ld.n_nodes) v = reinterpret_cast<const int64_t *>(ld.table + size_t(node) * size_t(ld.K))[e - r * per_row];
-        reinterpret_cast<int64_t *>(out)[e] = v;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) *totals_out = *ld.totals;
-}
-
 static bool linkstats_k_ok(int K) { return K == 1 || K == 2 || K == 4 || K == 8; }
 
 hipError_t launch_linkstats(hipStream_t s, const LinkStatsDev &ld, const TickDev &t)
@@ -169,14 +153,6 @@ hipError_t launch_linkstats_scatter(hipStream_t s, int32_t *peer, rm_link_stats 
     if (!linkstats_k_ok(K)) return hipErrorInvalidValue;
     const int blocks = int(std::max<size_t>(1, std::min<size_t>(1024, (size_t(n) * size_t(K) + 255u) / 256u)));
     RM_KLAUNCH(k_linkstats_scatter, dim3(blocks), dim3(256), 0, s, peer, table, n_nodes, K, nodes, n, new_peers);
-    return hipGetLastError();
-}
-
-hipError_t launch_linkstats_gather(hipStream_t s, const LinkStatsDev &ld, const int32_t *nodes, int n, rm_link_stats *out, rm_stats_totals *totals_out)
-{
-    if (!linkstats_k_ok(ld.K)) return hipErrorInvalidValue;
-    const int blocks = int(std::max<size_t>(1, std::min<size_t>(64, (size_t(std::max(n, 0)) * size_t(ld.K) * 6u + 255u) / 256u)));
-    RM_KLAUNCH(k_linkstats_gather, dim3(blocks), dim3(256), 0, s, ld, nodes, n, out, totals_out);
     return hipGetLastError();
 }
 

@@ -46,30 +46,6 @@ RM_D void listen_body(const ListenDev &ld, const TickDev &t)
 __global__ void __launch_bounds__(256) k_listen(const ListenDev ld, const TickDev t) { listen_body(ld, t); }
 __global__ void __launch_bounds__(256) k_listen_batch(const ListenDev ld, const TickDev *__restrict__ ticks) { listen_body(ld, ticks[blockIdx.y]); }
 
-// rm_listen_set with a list: entry k of the host-mapped block goes to node nodes[k], one 64-bit word per lane.  The host has applied
-// the list to its copy in order and staged every entry with its node's FINAL record, so duplicates write equal values.
-__global__ void __launch_bounds__(256) k_listen_scatter(rm_listen_schedule *__restrict__ table, int n_nodes, const int32_t *__restrict__ nodes, int n,
-                                                        const rm_listen_schedule *__restrict__ sched)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint64_t e = blockIdx.x * blockDim.x + threadIdx.x; e < uint64_t(n) * 3u; e += stride) {
-        const uint64_t k = e / 3u;
-        const int32_t node = nodes[k];
-        if (node < 0 || node >= n_nodes) continue;
-        reinterpret_cast<int64_t *>(table + node)[e - k * 3u] = reinterpret_cast<const int64_t *>(sched)[e];
-    }
-}
-
-// rm_listen_missed_read with a list: the listed nodes' counts into the host-mapped block
-__global__ void __launch_bounds__(256) k_listen_gather(const ListenDev ld, const int32_t *__restrict__ nodes, int n, uint64_t *__restrict__ out)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < uint32_t(n); k += stride) {
-        const int32_t node = nodes[k];
-        out[k] = (node >= 0 && node < ld.n_nodes) ? ld.missed[node] : 0u;
-    }
-}
-
 hipError_t launch_listen(hipStream_t s, const ListenDev &ld, const TickDev &t)
 {
     RM_KLAUNCH(k_listen, dim3(kListenBlocks), dim3(256), 0, s, ld, t);
@@ -80,22 +56,6 @@ hipError_t launch_listen_batch(hipStream_t s, const ListenDev &ld, int n, const 
 {
     if (n < 1 || n > kMaxBatch) return hipErrorInvalidValue;
     RM_KLAUNCH(k_listen_batch, dim3(kListenBlocks, n), dim3(256), 0, s, ld, dev_ticks);
-    return hipGetLastError();
-}
-
-hipError_t launch_listen_scatter(hipStream_t s, rm_listen_schedule *table, int n_nodes, const int32_t *nodes, int n, const rm_listen_schedule *sched)
-{
-    if (n < 1) return hipSuccess;
-    const int blocks = max(1, min(64, n / 85 + 1)); // (256 lanes, three words per entry)
-    RM_KLAUNCH(k_listen_scatter, dim3(blocks), dim3(256), 0, s, table, n_nodes, nodes, n, sched);
-    return hipGetLastError();
-}
-
-hipError_t launch_listen_gather(hipStream_t s, const ListenDev &ld, const int32_t *nodes, int n, uint64_t *out)
-{
-    if (n < 1) return hipSuccess;
-    const int blocks = max(1, min(64, (n + 255) / 256));
-    RM_KLAUNCH(k_listen_gather, dim3(blocks), dim3(256), 0, s, ld, nodes, n, out);
     return hipGetLastError();
 }
 

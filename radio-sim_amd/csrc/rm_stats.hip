@@ -81,20 +81,6 @@ RM_D void stats_body(const StatsDev &sd, const TickDev &t)
 __global__ void __launch_bounds__(256) k_stats(const StatsDev sd, const TickDev t) { stats_body(sd, t); }
 __global__ void __launch_bounds__(256) k_stats_batch(const StatsDev sd, const TickDev *__restrict__ ticks) { stats_body(sd, ticks[blockIdx.y]); }
 
-// rm_stats_read with a list: the listed nodes' records (one 64-bit word per lane) and the totals into the host-mapped block
-__global__ void __launch_bounds__(256) k_stats_gather(const StatsDev sd, const int32_t *__restrict__ nodes, int n, rm_node_stats *__restrict__ out,
-                                                      rm_stats_totals *__restrict__ totals_out)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint64_t e = blockIdx.x * blockDim.x + threadIdx.x; e < uint64_t(n) * 8u; e += stride) {
-        const int32_t node = nodes[e >> 3];
-        uint64_t v = 0;
-        if (node >= 0 && node < sd.n_nodes) v = reinterpret_cast<const uint64_t *>(sd.table + node)[e & 7u];
-        reinterpret_cast<uint64_t *>(out)[e] = v;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) *totals_out = *sd.totals;
-}
-
 hipError_t launch_stats(hipStream_t s, const StatsDev &sd, const TickDev &t)
 {
     RM_KLAUNCH(k_stats, dim3(kStatsBlocks), dim3(256), 0, s, sd, t);
@@ -105,13 +91,6 @@ hipError_t launch_stats_batch(hipStream_t s, const StatsDev &sd, int n, const Ti
 {
     if (n < 1 || n > kMaxBatch) return hipErrorInvalidValue;
     RM_KLAUNCH(k_stats_batch, dim3(kStatsBlocks, n), dim3(256), 0, s, sd, dev_ticks);
-    return hipGetLastError();
-}
-
-hipError_t launch_stats_gather(hipStream_t s, const StatsDev &sd, const int32_t *nodes, int n, rm_node_stats *out, rm_stats_totals *totals_out)
-{
-    const int blocks = max(1, min(64, (n + 31) / 32));
-    RM_KLAUNCH(k_stats_gather, dim3(blocks), dim3(256), 0, s, sd, nodes, n, out, totals_out);
     return hipGetLastError();
 }
 

@@ -145,31 +145,6 @@ __global__ void __launch_bounds__(256) k_traffic_scan(const TrafficGen g)
     for (int p = min(s_total, g.cap) + int(threadIdx.x); p < g.cap; p += 256) row[p] = -1;
 }
 
-// rm_traffic_set with a list: entry k of the host-mapped block goes to node nodes[k], one 64-bit word per lane.  The host has
-// validated the list and staged every entry with its node's FINAL record (the last entry of a node wins), so duplicates write
-// equal values.
-__global__ void __launch_bounds__(256) k_traffic_scatter(rm_traffic_schedule *__restrict__ table, int n_nodes, const int32_t *__restrict__ nodes, int n,
-                                                         const rm_traffic_schedule *__restrict__ sched)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint64_t e = blockIdx.x * blockDim.x + threadIdx.x; e < uint64_t(n) * 4u; e += stride) {
-        const int32_t node = nodes[e >> 2];
-        if (node < 0 || node >= n_nodes) continue;
-        reinterpret_cast<int64_t *>(table + node)[e & 3u] = reinterpret_cast<const int64_t *>(sched)[e];
-    }
-}
-
-// rm_traffic_get with a list: the listed nodes' records into the host-mapped block
-__global__ void __launch_bounds__(256) k_traffic_gather(const rm_traffic_schedule *__restrict__ table, int n_nodes, const int32_t *__restrict__ nodes, int n,
-                                                        rm_traffic_schedule *__restrict__ out)
-{
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint64_t e = blockIdx.x * blockDim.x + threadIdx.x; e < uint64_t(n) * 4u; e += stride) {
-        const int32_t node = nodes[e >> 2];
-        reinterpret_cast<int64_t *>(out)[e] = (node >= 0 && node < n_nodes) ? reinterpret_cast<const int64_t *>(table + node)[e & 3u] : 0;
-    }
-}
-
 hipError_t launch_traffic_generate(hipStream_t s, const TrafficGen &g)
 {
     if (g.n_ticks < 1 || g.n_ticks > kMaxBatch || g.cap < 1 || g.units < 1 || g.chunk < 64 || g.n_nodes < 0) return hipErrorInvalidValue;
@@ -177,22 +152,6 @@ hipError_t launch_traffic_generate(hipStream_t s, const TrafficGen &g)
     RM_KLAUNCH(k_traffic_count, dim3(g.units), dim3(64), 0, s, g);
     RM_KLAUNCH(k_traffic_scan, dim3(g.n_ticks), dim3(256), 0, s, g);
     RM_KLAUNCH(k_traffic_write, dim3(g.units), dim3(64), 0, s, g);
-    return hipGetLastError();
-}
-
-hipError_t launch_traffic_scatter(hipStream_t s, rm_traffic_schedule *table, int n_nodes, const int32_t *nodes, int n, const rm_traffic_schedule *sched)
-{
-    if (n < 1) return hipSuccess;
-    const int blocks = max(1, min(64, n / 64 + 1)); // (256 lanes, four words per entry)
-    RM_KLAUNCH(k_traffic_scatter, dim3(blocks), dim3(256), 0, s, table, n_nodes, nodes, n, sched);
-    return hipGetLastError();
-}
-
-hipError_t launch_traffic_gather(hipStream_t s, const rm_traffic_schedule *table, int n_nodes, const int32_t *nodes, int n, rm_traffic_schedule *out)
-{
-    if (n < 1) return hipSuccess;
-    const int blocks = max(1, min(64, n / 64 + 1));
-    RM_KLAUNCH(k_traffic_gather, dim3(blocks), dim3(256), 0, s, table, n_nodes, nodes, n, out);
     return hipGetLastError();
 }
 

@@ -153,6 +153,14 @@ class Engine:
         e = Engine.error_model(seed=seed)
         return _lib.lib().rm_error_model_draw(C.byref(e), src, start_us, dst)
 
+    # -- what the calls of E11, E13, E14 and E15 that take "a node list, or the whole table" share
+    def _node_list(self, nodes):
+        """(pointer of the int32 list or None for all nodes in node order, n, the index array to keep alive)"""
+        if nodes is None:
+            return None, max(int(self._L.rm_node_count(self._h)), 0), None
+        idx = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+        return idx.ctypes.data, idx.shape[0], idx
+
     # -- per-node traffic counters accumulated on the device (DESIGN.md section 6, E11)
     def stats_enable(self, on=True):
         """rm_stats_enable: count from the next evaluating call (False: stop counting, the table is kept)"""
@@ -168,13 +176,9 @@ class Engine:
         """rm_stats_read: (structured array of NODE_STATS_DTYPE -- the listed nodes in list order, or all in node order --,
         {"ticks_counted": .., "ticks_skipped": ..})"""
         tot = _lib.StatsTotals()
-        if nodes is None:
-            out = np.zeros(max(int(self._L.rm_node_count(self._h)), 0), dtype=_lib.NODE_STATS_DTYPE)
-            check(self._L.rm_stats_read(self._h, None, out.shape[0], out.ctypes.data, C.byref(tot)))
-        else:
-            idx = np.ascontiguousarray(nodes, dtype=np.int32)
-            out = np.zeros(idx.shape[0], dtype=_lib.NODE_STATS_DTYPE)
-            check(self._L.rm_stats_read(self._h, idx.ctypes.data, idx.shape[0], out.ctypes.data, C.byref(tot)))
+        ptr, n, _idx = self._node_list(nodes)
+        out = np.zeros(n, dtype=_lib.NODE_STATS_DTYPE)
+        check(self._L.rm_stats_read(self._h, ptr, n, out.ctypes.data, C.byref(tot)))
         return out, {"ticks_counted": int(tot.ticks_counted), "ticks_skipped": int(tot.ticks_skipped)}
 
     def stats_device(self):
@@ -273,23 +277,16 @@ class Engine:
         """rm_listen_set: sched for all nodes in node order, or for the listed nodes in list order (the last entry of a node wins);
         switches the feature on"""
         tbl = self._listen_table(sched)
-        if nodes is None:
-            check(self._L.rm_listen_set(self._h, None, tbl.shape[0], tbl.ctypes.data))
-        else:
-            idx = np.ascontiguousarray(nodes, dtype=np.int32)
-            if idx.shape[0] != tbl.shape[0]:
-                raise ValueError("one schedule per listed node")
-            check(self._L.rm_listen_set(self._h, idx.ctypes.data, idx.shape[0], tbl.ctypes.data))
+        ptr, n, _idx = self._node_list(nodes)
+        if nodes is not None and n != tbl.shape[0]:
+            raise ValueError("one schedule per listed node")
+        check(self._L.rm_listen_set(self._h, ptr, tbl.shape[0], tbl.ctypes.data))
 
     def listen_get(self, nodes=None):
         """rm_listen_get: structured array of LISTEN_SCHEDULE_DTYPE (the listed nodes in list order, or all in node order)"""
-        if nodes is None:
-            out = np.zeros(max(int(self._L.rm_node_count(self._h)), 0), dtype=_lib.LISTEN_SCHEDULE_DTYPE)
-            check(self._L.rm_listen_get(self._h, None, out.shape[0], out.ctypes.data))
-        else:
-            idx = np.ascontiguousarray(nodes, dtype=np.int32)
-            out = np.zeros(idx.shape[0], dtype=_lib.LISTEN_SCHEDULE_DTYPE)
-            check(self._L.rm_listen_get(self._h, idx.ctypes.data, idx.shape[0], out.ctypes.data))
+        ptr, n, _idx = self._node_list(nodes)
+        out = np.zeros(n, dtype=_lib.LISTEN_SCHEDULE_DTYPE)
+        check(self._L.rm_listen_get(self._h, ptr, n, out.ctypes.data))
         return out
 
     def listen_clear(self):
@@ -300,13 +297,9 @@ class Engine:
 
     def listen_missed(self, nodes=None):
         """rm_listen_missed_read: uint64 per node (the listed nodes in list order, or all in node order)"""
-        if nodes is None:
-            out = np.zeros(max(int(self._L.rm_node_count(self._h)), 0), dtype=np.uint64)
-            check(self._L.rm_listen_missed_read(self._h, None, out.shape[0], out.ctypes.data))
-        else:
-            idx = np.ascontiguousarray(nodes, dtype=np.int32)
-            out = np.zeros(idx.shape[0], dtype=np.uint64)
-            check(self._L.rm_listen_missed_read(self._h, idx.ctypes.data, idx.shape[0], out.ctypes.data))
+        ptr, n, _idx = self._node_list(nodes)
+        out = np.zeros(n, dtype=np.uint64)
+        check(self._L.rm_listen_missed_read(self._h, ptr, n, out.ctypes.data))
         return out
 
     def listen_missed_reset(self):
@@ -335,11 +328,8 @@ class Engine:
 
     def _linkstats_rows(self, nodes):
         """(K, index array or None, rows) of a list call"""
-        K = self.linkstats_enabled()
-        if nodes is None:
-            return K, None, max(int(self._L.rm_node_count(self._h)), 0)
-        idx = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
-        return K, idx, idx.shape[0]
+        _, n, idx = self._node_list(nodes)
+        return self.linkstats_enabled(), idx, n
 
     def linkstats_watch(self, peers, nodes=None):
         """rm_linkstats_watch: peers [n][K] (-1: an empty slot) for all nodes in node order, or for the listed nodes; a slot whose
@@ -413,23 +403,16 @@ class Engine:
         """rm_traffic_set: sched for all nodes in node order, or for the listed nodes in list order (the last entry of a node wins);
         switches the feature on"""
         tbl = self._traffic_table(sched)
-        if nodes is None:
-            check(self._L.rm_traffic_set(self._h, None, tbl.shape[0], tbl.ctypes.data))
-        else:
-            idx = np.ascontiguousarray(nodes, dtype=np.int32)
-            if idx.shape[0] != tbl.shape[0]:
-                raise ValueError("one schedule per listed node")
-            check(self._L.rm_traffic_set(self._h, idx.ctypes.data, idx.shape[0], tbl.ctypes.data))
+        ptr, n, _idx = self._node_list(nodes)
+        if nodes is not None and n != tbl.shape[0]:
+            raise ValueError("one schedule per listed node")
+        check(self._L.rm_traffic_set(self._h, ptr, tbl.shape[0], tbl.ctypes.data))
 
     def traffic_get(self, nodes=None):
         """rm_traffic_get: structured array of TRAFFIC_SCHEDULE_DTYPE (the listed nodes in list order, or all in node order)"""
-        if nodes is None:
-            out = np.zeros(max(int(self._L.rm_node_count(self._h)), 0), dtype=_lib.TRAFFIC_SCHEDULE_DTYPE)
-            check(self._L.rm_traffic_get(self._h, None, out.shape[0], out.ctypes.data))
-        else:
-            idx = np.ascontiguousarray(nodes, dtype=np.int32)
-            out = np.zeros(idx.shape[0], dtype=_lib.TRAFFIC_SCHEDULE_DTYPE)
-            check(self._L.rm_traffic_get(self._h, idx.ctypes.data, idx.shape[0], out.ctypes.data))
+        ptr, n, _idx = self._node_list(nodes)
+        out = np.zeros(n, dtype=_lib.TRAFFIC_SCHEDULE_DTYPE)
+        check(self._L.rm_traffic_get(self._h, ptr, n, out.ctypes.data))
         return out
 
     def traffic_clear(self):

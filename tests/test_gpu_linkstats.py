@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TICK = R.TICK
-LINK_KERNELS = ("k_linkstats", "k_linkstats_batch", "k_linkstats_clear", "k_linkstats_scatter", "k_linkstats_gather")
+LINK_KERNELS = ("k_linkstats", "k_linkstats_batch", "k_linkstats_clear", "k_linkstats_scatter", "k_rows_gather", "k_rows_scatter")
 INVALID, STATE = -1, -5
 
 

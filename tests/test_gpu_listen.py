@@ -27,7 +27,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TICK = R.TICK
-LISTEN_KERNELS = ("k_listen", "k_listen_batch", "k_listen_scatter", "k_listen_gather")
+LISTEN_KERNELS = ("k_listen", "k_listen_batch", "k_rows_gather", "k_rows_scatter")
 INVALID, STATE = -1, -5
 UC_INTERFERED, UC_DELIVERED = 3, 4
 

@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TICK = R.TICK
-STATS_KERNELS = ("k_stats", "k_stats_batch", "k_stats_gather")
+STATS_KERNELS = ("k_stats", "k_stats_batch", "k_rows_gather", "k_rows_scatter")
 INVALID, STATE = -1, -5
 
 

@@ -22,6 +22,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID, CAPACITY, STATE = -1, -4, -5
 TICK = 1000
+TRAFFIC_KERNELS = ("k_traffic", "k_rows_")   # (name prefixes: the generator's kernels, and what a list update or a list read launches)
 
 
 def _bare(rsa, n):
@@ -606,9 +607,9 @@ def test_no_schedule_no_launch_and_the_evaluating_calls_launch_what_they_did(rsa
 
     try:
         plain, order, _ = record(lambda eng: None)
-        assert plain and not [k for k in plain if k.startswith("k_traffic")], order
+        assert plain and not [k for k in plain if k.startswith(TRAFFIC_KERNELS)], order
         on, order_on, seen = record(generated)
-        assert {k: v for k, v in seen.items() if k.startswith("k_traffic")} == {"k_traffic_count": 1, "k_traffic_scan": 1, "k_traffic_write": 1}
+        assert {k: v for k, v in seen.items() if k.startswith(TRAFFIC_KERNELS)} == {"k_traffic_count": 1, "k_traffic_scan": 1, "k_traffic_write": 1}
         assert on == plain and order_on == order, (on, plain)
         off, order_off, _ = record(cleared)
         assert off == plain and order_off == order
