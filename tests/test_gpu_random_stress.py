@@ -9,9 +9,12 @@ from util import configure_engine, oracle_model, to_tx_records, assert_same
 pytestmark = pytest.mark.gpu
 
 
-def _scenario(O, rng):
+def _scenario(O, rng, kind=None):
+    """kind: takes the place of the drawn kind (after the draw: the streams of the callers that do not give one stay where they were)"""
+    force = kind
     n = int(rng.choice([1, 2, 3, 63, 64, 65, 127, 129, 257, 700, 1500]))
     kind = str(rng.choice(["null", "udgm", "udgm_const", "n2n", "logdist", "logdist", "logdist_sinr"]))
+    kind = force or kind
     nd = O.NodeTable(n)
     layout = rng.choice(["uniform", "line", "clustered", "coincident", "3d"])
     side = float(rng.choice([10.0, 200.0, 2000.0]))
@@ -138,6 +141,92 @@ def test_randomized_scenarios_through_batches_and_single_packets(engine, rsa, O,
             assert bool(got.pkt_interference[0]) == bool(cpu.pkt_interference[0]), what
             assert engine.rng_state == state, what
     # (some blocks draw only scenarios without a single heard link: nothing to require of `checked` here)
+
+
+@pytest.mark.parametrize("block", range(int(__import__("os").environ.get("RM_STRESS_BLOCKS", "8"))))
+def test_randomized_sinr_scenarios_through_batches(rsa, O, block):
+    """The awkward tables and parameters with the SINR extension on, through the three batch forms, every tick against the oracle
+    with the frames on the air (E3 / E4); a context of its own per scenario, the three calls far apart in time.
+    * sources cut into up to 5 self-contained ticks (some empty), frames inside their tick: rm_batch_run_sources_device;
+    * one tick of records that keep the scenario's per-packet times, power and channel: rm_batch_run_device;
+    * the same ticks with 8128 us frames, which outlive them: the overlap form.  DESIGN.md section 6 (E7) lists what that form
+      refuses with RM_ERR_STATE before anything runs: links that can draw (a probability strictly between 0 and 1 in the table)
+      and a table that is not kept in spatial order (64 nodes or fewer).  Exactly those scenarios must be refused, every other
+      one must run -- no call is retried tick by tick."""
+    from util import DeviceArray
+    rng = np.random.default_rng(7000 + block)
+    checked = 0
+    for it in range(14):
+        nd, kind, params, matrix, pk = _scenario(O, rng, kind="logdist_sinr")
+        assert kind == "logdist" and params["ld_flags"] == 1
+        if len(pk) * nd.n > 60_000:
+            pk = pk[:40]
+        mdl = oracle_model(O, kind, params, matrix)
+        seed = int(rng.integers(0, 2 ** 31))
+        what = "block %d it %d %s n=%d t=%d" % (block, it, params, nd.n, len(pk))
+        cuts = np.sort(rng.integers(0, len(pk) + 1, int(rng.integers(0, 5))))
+        parts = [p.astype(np.int32) for p in np.split(pk["src"], cuts)]
+        offs = [int(rng.integers(0, 500)) for _ in parts]
+        airs = [int(rng.choice([0, 320, 500])) for _ in parts]
+        eng, dev = rsa.Engine(0), []
+        try:
+            configure_engine(eng, nd, kind, params, matrix)
+
+            def source_batch(t0, starts, air_us):
+                arrs = [DeviceArray(p) if len(p) else None for p in parts]
+                dev.extend(a for a in arrs if a is not None)
+                tb = [t0 + 1000 * b for b in range(len(parts))]
+                eng.batch_run_sources_device(tb, [t + 1000 for t in tb], [a.ptr.value if a is not None else 0 for a in arrs],
+                                             [len(p) for p in parts], [t + s for t, s in zip(tb, starts)], air_us)
+                return tb
+
+            def against_oracle(tb, starts, air_us, state, label):
+                nonlocal checked
+                onair = np.zeros(0, dtype=O.PACKET_DTYPE)
+                for b, p in enumerate(parts):
+                    onair = onair[onair["start_us"] + onair["air_us"] > tb[b]]
+                    new = nd.packets(p, tb[b] + starts[b], air_us[b])
+                    cpu = O.tick(mdl, nd, np.concatenate([onair, new]), first_new=len(onair), rng_state=state)
+                    state = cpu.rng_state
+                    onair = np.concatenate([onair, new])
+                    assert_same(eng.batch_result_copy(b, len(p)), cpu, "%s %s tick %d" % (what, label, b))
+                    checked += cpu.count
+                assert eng.rng_state == state, what
+            # -- self-contained ticks by sources
+            eng.seed(seed)
+            tb = source_batch(0, offs, airs)
+            against_oracle(tb, offs, airs, O.lib().orc_jrandom_seed(seed), "self-contained")
+            # -- one tick of records with the packets' own times, power and channel
+            t0 = 100_000
+            one = pk.copy()
+            one["start_us"] += t0
+            t_end = t0 + int((pk["start_us"] + pk["air_us"]).max()) + 1
+            recs = DeviceArray(to_tx_records(rsa, one))
+            dev.append(recs)
+            eng.seed(seed)
+            eng.batch_run_device([t0], [t_end], [recs.ptr.value], [len(one)])
+            cpu = O.tick(mdl, nd, one, rng_state=O.lib().orc_jrandom_seed(seed))
+            assert_same(eng.batch_result_copy(0, len(one)), cpu, what + " records")
+            assert eng.rng_state == cpu.rng_state, what
+            checked += cpu.count
+            # -- overlapping ticks
+            t0 = 200_000
+            long_airs = [8128] * len(parts)
+            wanted = any(len(p) for p in parts[:-1])        # a frame that is still on the air when a later tick begins
+            draws = bool((((nd.rxprob > 0) & (nd.rxprob < 1)) | ((nd.txprob > 0) & (nd.txprob < 1))).any())
+            eng.seed(seed)
+            if wanted and (draws or nd.n <= 64):
+                with pytest.raises(rsa.RadioMediumError) as err:
+                    source_batch(t0, [0] * len(parts), long_airs)
+                assert err.value.code == -5, what
+            else:
+                tb = source_batch(t0, [0] * len(parts), long_airs)
+                against_oracle(tb, [0] * len(parts), long_airs, O.lib().orc_jrandom_seed(seed), "overlapping")
+        finally:
+            for d in dev:
+                d.free()
+            eng.close()
+    assert checked > 0
 
 
 @pytest.mark.parametrize("block", range(int(__import__("os").environ.get("RM_STRESS_BLOCKS", "8"))))
