@@ -1001,6 +1001,48 @@ int rm_linkstats_watch_device(rm_context *ctx, const int32_t *dev_nodes, int32_t
  * the feature is off. */
 int rm_linkstats_stage_device(rm_context *ctx, int32_t **dev_rows);
 
+/* ---- hop query: hop count and best parent toward a set of roots --------------------------------------------------------
+ * (not reference behaviour.)  A pure function of the node table and the model, on
+ * RM_MODEL_LOGDIST only (with or without RM_LD_SINR; the flag plays no part): whom a node addresses in a collection or a
+ * dissemination tree, without the host seeing a link.
+ * link(j, p, dir) holds iff p is a far end of j's potential links in direction dir exactly as the neighbour query defines them
+ * (RM_NB_HEARD_BY: j transmits and p receives; RM_NB_HEARS: p transmits with its own table txpower and j receives; the table as it
+ * is now, shadowing, enabled, channel and rxprob of the receiving end; a NaN rssi is no link) and rssi >= min_rssi_dbm, rssi being
+ * that link's value of the neighbour query.  min_rssi_dbm = -inf keeps every potential link, +inf none; rssi == min_rssi_dbm is a
+ * link.  direction is the link between a node and its parent, seen from the node: RM_NB_HEARD_BY gives a collection tree (the
+ * node is heard by its parent), RM_NB_HEARS a dissemination tree (the node hears its parent).
+ * hop[r] = 0 for every root r, whatever its radio state; for L = 0, 1, ... an unlabelled node j gets hop[j] = L + 1 iff
+ * link(j, p, dir) for some p with hop[p] = L; a node never labelled has hop -1.  For hop[j] = h >= 1, parent[j] is, among all p
+ * with hop[p] = h - 1 and link(j, p, dir), the first in the neighbour query's order (rssi descending, ties by the smaller node
+ * index), and rssi[j] that link's rssi; roots and unreached nodes have parent -1 and the NaN 0x7FF8000000000000.  children[p] is
+ * the number of nodes whose parent is p.  Totals: reached the nodes with hop >= 0, max_hop the largest hop (-1 without a valid
+ * root), roots the distinct valid roots, reserved 0.  Roots may repeat; n_roots = 0 is RM_OK with nothing reached.
+ * The answer does not depend on the walk, the launch geometry or the table's sort state, and a query changes nothing: no result
+ * slot, not the on-air window, not the generator, none of the tables of E11-E15, not the source-candidate cache, not the
+ * neighbour query's scratch.  parent is by construction a valid K = 1 table of rm_linkstats_watch_device. */
+/* the outputs, [n_nodes] each, by node index: hop is required, the others may be NULL */
+typedef struct rm_hops_out { int32_t *hop; int32_t *parent; double *rssi; int32_t *children; } rm_hops_out;
+typedef struct rm_hops_totals { int32_t reached; int32_t max_hop; int32_t roots; int32_t reserved; } rm_hops_totals;
+/* dev_roots and the arrays dev_out (a host struct) points to are device memory; a root entry outside 0 .. n_nodes - 1 is ignored.
+ * The call waits on the context's stream once per level and returns when the outputs are complete; totals (host) may be NULL.
+ * RM_ERR_STATE, nothing launched: another medium than RM_MODEL_LOGDIST, between rm_tick_begin and rm_tick_flush, a context with a
+ * receiver partition, a context made under RM_GRAPH=1.  RM_ERR_INVALID: NULL ctx, dev_out or hop, an unknown direction, a NaN
+ * min_rssi_dbm, n_roots < 0, n_roots > 0 with NULL roots. */
+int rm_hops_query_device(rm_context *ctx, int32_t direction, double min_rssi_dbm, const int32_t *dev_roots, int32_t n_roots,
+                         const rm_hops_out *dev_out, rm_hops_totals *totals);
+/* the same with host arrays; a root outside the table is RM_ERR_INVALID before anything is launched */
+int rm_hops_query(rm_context *ctx, int32_t direction, double min_rssi_dbm, const int32_t *roots, int32_t n_roots, const rm_hops_out *out,
+                  rm_hops_totals *totals);
+/* want[i] = parent[src[i]] for 0 <= src[i] < n_nodes, else -1 (all device memory, n entries; dev_parent [n_nodes] as the query
+ * wrote it): enqueued on the context's stream without waiting.  Over source rows of cap entries per slot, dev_want has the shape
+ * rm_unicast_query_device takes.  RM_ERR_INVALID: NULL ctx, n < 0, n > 0 with a NULL array. */
+int rm_hops_next_device(rm_context *ctx, const int32_t *dev_parent, const int32_t *dev_src, int32_t n, int32_t *dev_want);
+/* The same rule over an explicit list of candidate links, a pure host function without a device: entry i says that far[i] may be
+ * node[i]'s parent with rssi[i] (NaN rssi entries and entries with node == far are no links).  RM_ERR_INVALID: a NULL out or hop,
+ * negative counts, NULL lists with a positive count, a NaN min_rssi_dbm, an index (node, far, root) outside 0 .. n_nodes - 1. */
+int rm_hops_from_links(int32_t n_nodes, int32_t n_links, const int32_t *node, const int32_t *far, const double *rssi, double min_rssi_dbm,
+                       const int32_t *roots, int32_t n_roots, const rm_hops_out *out, rm_hops_totals *totals);
+
 /* ---- several devices behind one caller --------------------------------------------------------------
  * The reference host is ONE process (Main.java:65-73): a group drives n contexts from one host thread, one
  * per device (an ordinal may repeat: several partitions on one GPU).  Receivers are partitioned over the

@@ -73,6 +73,19 @@ UNICAST_FIELDS = (("status", np.uint8), ("link", np.int32), ("rssi", np.float64)
 # the neighbour query: directions, the largest K
 NB_HEARD_BY, NB_HEARS, NB_MAX_K = 0, 1, 16
 
+
+class HopsOut(C.Structure):
+    """rm_hops_out: the output arrays of the hop query, [n_nodes] each; all but hop may be NULL"""
+    _fields_ = [("hop", C.c_void_p), ("parent", C.c_void_p), ("rssi", C.c_void_p), ("children", C.c_void_p)]
+
+
+class HopsTotals(C.Structure):
+    """rm_hops_totals"""
+    _fields_ = [("reached", C.c_int32), ("max_hop", C.c_int32), ("roots", C.c_int32), ("reserved", C.c_int32)]
+
+
+HOPS_FIELDS = (("hop", np.int32), ("parent", np.int32), ("rssi", np.float64), ("children", np.int32))
+
 NODE_STATS_DTYPE = np.dtype([(name, "<u8") for name, _ in NodeStats._fields_])
 assert NODE_STATS_DTYPE.itemsize == C.sizeof(NodeStats) == 64
 
@@ -383,6 +396,11 @@ SIGNATURES = {
     "rm_neighbors_from_result": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rm_linkstats_watch_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "rm_linkstats_stage_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "rm_hops_query_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.POINTER(HopsOut), C.POINTER(HopsTotals)]),
+    "rm_hops_query": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.POINTER(HopsOut), C.POINTER(HopsTotals)]),
+    "rm_hops_next_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "rm_hops_from_links": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int32,
+                                     C.POINTER(HopsOut), C.POINTER(HopsTotals)]),
     "rm_det_math": (C.c_double, [C.c_int32, C.c_double]),
     "rm_link_hash": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
     "rm_evq_init": (None, [C.c_void_p]),

@@ -125,6 +125,7 @@ void passes_release(rm_context *c)
     traffic_release(c);
     linkstats_release(c);
     neighbors_release(c);
+    hops_release(c);
 }
 
 } // namespace rmh

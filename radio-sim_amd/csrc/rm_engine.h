@@ -966,9 +966,36 @@ struct NbDev {
     int32_t *degree;  // [rows], or nullptr
 };
 hipError_t launch_nb_query(hipStream_t s, const NodesDev &nd, const ModelDev &m, const NbDev &q, int direction, bool scan);
+// k_nb_prep alone (launch_nb_query's RM_NB_HEARS path runs it itself): prep two words zeroed by the caller on the stream
+hipError_t launch_nb_prep(hipStream_t s, const NodesDev &nd, unsigned long long *prep, int32_t *off_list);
 // rm_linkstats_validate's rules over rows in device memory (rm_linkstats_watch_device): *bad becomes 1 if one is broken
 hipError_t launch_nb_watch_check(hipStream_t s, const int32_t *nodes, int n, const int32_t *peers, int n_nodes, int K, uint32_t *mark, uint32_t stamp,
                                  uint32_t *bad);
+
+// (rm_hops.hip) the hop query.  The outputs are [n_nodes] by node index (parent / rssi /
+// children may be nullptr).  queue [n_nodes]: the labelled nodes in the order they were claimed -- the roots first, then level
+// after level, each level a contiguous range; *tail the number of entries (zeroed by the caller on the stream in front of
+// launch_hop_seed).  prep / off_list: what launch_nb_prep left for the HEARS walk.
+struct HopDev {
+    int32_t *hop;
+    int32_t *parent;
+    uint64_t *rssi;
+    int32_t *children;
+    int32_t *queue;
+    uint32_t *tail;
+    const unsigned long long *prep;
+    const int32_t *off_list;
+    double min_rssi;
+};
+// the outputs as "nothing reached", then the roots (device memory, entries outside the table skipped, duplicates claimed once)
+// as level 0: queue[0 .. *tail)
+hipError_t launch_hop_seed(hipStream_t s, const NodesDev &nd, const HopDev &h, const int32_t *roots, int n_roots);
+// one level: a wave per node of queue[lo .. hi), all of hop `level`, claims its unlabelled link ends with level + 1 and appends them
+hipError_t launch_hop_expand(hipStream_t s, const NodesDev &nd, const ModelDev &m, const HopDev &h, int direction, bool scan, int lo, int hi, int level);
+// parent, rssi and children of the nodes of queue[lo .. hi) (reached, not roots), behind the last level
+hipError_t launch_hop_parent(hipStream_t s, const NodesDev &nd, const ModelDev &m, const HopDev &h, int direction, bool scan, int lo, int hi);
+// want[i] = parent[src[i]], -1 for src[i] outside 0 .. n_nodes - 1
+hipError_t launch_hop_next(hipStream_t s, const int32_t *parent, int n_nodes, const int32_t *src, int n, int32_t *want);
 
 // (rm_unicast.hip) the unicast outcome query, one launch: a lane per entry.  n_slots result slots described by dev_slots -- or, with
 // dev_slots == nullptr, the one slot `lone`.  Slots form (dev_prefix: [n_slots + 1] exclusive prefix of the entries per slot; nullptr

@@ -227,6 +227,16 @@ struct rm_context : TickSlot {
         DevBuf<unsigned long long> prep;
         DevBuf<int32_t> off_list;
     } nb;
+    // the hop query (E17; rm_api_hops.cpp, rm_hops.hip): its own prep words and list of radios that are off (E16's are not
+    // touched) -- words[0 .. 1] are k_nb_prep's, the low half of words[2] is the queue's tail; one 32-byte block, zeroed per
+    // query --, the queue of labelled nodes ([n_nodes]: every level's frontier is a range of it), and the pinned word the
+    // tail is copied to once per level.  Nothing is allocated before the first query.
+    struct Hops {
+        DevBuf<unsigned long long> words;
+        DevBuf<int32_t> off_list;
+        DevBuf<int32_t> queue;
+        uint32_t *h_tail = nullptr;
+    } hp;
     // traffic schedules (E15; rm_api_traffic.cpp, rm_traffic.hip): one schedule per node index; the pinned, host-mapped block a list
     // update or a list read is staged through; the generator's scratch (the windows, the units' counts and packets) and the pinned
     // staging of its windows -- two blocks, each rewritten only after its copy has completed
@@ -781,6 +791,10 @@ int linkstats_host_fresh(rm_context *c);
 // ---- rm_api_neighbors.cpp: the neighbour query (E16)
 // rm_destroy
 void neighbors_release(rm_context *c);
+
+// ---- rm_api_hops.cpp: the hop query (E17)
+// rm_destroy
+void hops_release(rm_context *c);
 
 // ---- rm_api_traffic.cpp: traffic schedules (E15)
 // rm_nodes_upload: another node count clears the feature

@@ -3,29 +3,9 @@
 // (part of libradiomedium_hip.so; gfx950 only, -ffp-contract=off, no fast-math; overview at the top of rm_engine.h)
 //
 // Not the source-candidate cache (rm_nbrcache.hip): this is a read-only query over the node table and the model.
-#include "rm_device.hpp"
+#include "rm_nbwalk.hpp" // (nb_value_key, nb_key_value, nb_precedes: shared with the hop query)
 
 namespace rm {
-
-constexpr int kNbWaves = kWavesPerBlock; // queried entries per workgroup: one wave each
-constexpr uint64_t kNbNoRssi = 0x7FF8000000000000ull;
-
-// a txpower as a word whose unsigned order is the values' order (for the one atomicMax of k_nb_prep; it bounds a cut-off, so the
-// two zeros may differ): 0 for a NaN, which no number maps to -- and back, 0 giving -inf: nobody is in reach
-RM_D unsigned long long nb_value_key(const double v)
-{
-    if (v != v) return 0ull;
-    const uint64_t b = f2u(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-RM_D double nb_key_value(const unsigned long long key)
-{
-    if (key == 0ull) return -__builtin_inf();
-    return u2f((key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFull) : ~key);
-}
-
-// THE order of the rule: link a precedes link b
-RM_D bool nb_precedes(const double ra, const int na, const double rb, const int nb) { return ra > rb || (ra == rb && na < nb); }
 
 // A wave's running top-K, entry i in lane i (K <= 16 <= 64): sorted by the rule, `cnt` entries (wave-uniform).  No LDS and no
 // atomics: an insertion is one ballot (how many entries precede the new one) and one shuffle (the rest moves up a lane).
@@ -276,14 +256,21 @@ __global__ void __launch_bounds__(kBlock) k_nb_watch_check(const int32_t *__rest
     if (!ok) *bad = 1u;
 }
 
+hipError_t launch_nb_prep(hipStream_t s, const NodesDev &nd, unsigned long long *prep, int32_t *off_list)
+{
+    // (a few workgroups: the pass reads 9 bytes a node and ends in two atomics per wave)
+    RM_KLAUNCH(k_nb_prep, dim3(max(1, min(cdiv(nd.n, kBlock), 64))), dim3(kBlock), 0, s, nd, prep, off_list);
+    return hipGetLastError();
+}
+
 hipError_t launch_nb_query(hipStream_t s, const NodesDev &nd, const ModelDev &m, const NbDev &q, int direction, bool scan)
 {
     if (q.n < 1) return hipSuccess;
     if (q.K < 1 || q.K > RM_NB_MAX_K || !q.peer) return hipErrorInvalidValue;
     const dim3 grid(cdiv(q.n, kNbWaves)), block(kBlock);
     if (direction == RM_NB_HEARS) {
-        // (a few workgroups: the pass reads 9 bytes a node and ends in two atomics per wave)
-        RM_KLAUNCH(k_nb_prep, dim3(max(1, min(cdiv(nd.n, kBlock), 64))), block, 0, s, nd, q.prep, q.off_list);
+        const hipError_t e = launch_nb_prep(s, nd, q.prep, q.off_list);
+        if (e != hipSuccess) return e;
         if (scan) RM_KLAUNCH((k_nb_query<RM_NB_HEARS, true>), grid, block, 0, s, nd, m, q);
         else RM_KLAUNCH((k_nb_query<RM_NB_HEARS, false>), grid, block, 0, s, nd, m, q);
     } else if (direction == RM_NB_HEARD_BY) {

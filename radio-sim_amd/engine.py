@@ -529,6 +529,59 @@ class Engine:
         check(_lib.lib().rm_neighbors_from_result(C.byref(r), n, int(K), out["peer"].ctypes.data, _ptr(out.get("rssi")), _ptr(out.get("degree"))))
         return out
 
+    # -- hop query: hop count and best parent toward a set of roots
+    @staticmethod
+    def _hops_out(n, fields):
+        """host arrays for n nodes -> ({name: array}, the rm_hops_out over them); fields: the optional outputs asked for (None:
+        all of parent, rssi, children)"""
+        out = {name: np.empty(n, dtype=dt) for name, dt in _lib.HOPS_FIELDS if name == "hop" or fields is None or name in fields}
+        return out, _lib.HopsOut(**{name: a.ctypes.data for name, a in out.items()})
+
+    @staticmethod
+    def _hops_totals(tot):
+        return {"reached": int(tot.reached), "max_hop": int(tot.max_hop), "roots": int(tot.roots)}
+
+    def hops(self, direction, roots, min_rssi_dbm=-np.inf, fields=None):
+        """rm_hops_query: breadth-first levels from the roots over the potential links with rssi >= min_rssi_dbm ->
+        ({"hop": int32[n] (-1: not reached), "parent": int32[n], "rssi": float64[n] (NaN beside a -1), "children": int32[n]},
+        {"reached", "max_hop", "roots"}).  direction is the link between a node and its parent, seen from the node: NB_HEARD_BY a
+        collection tree, NB_HEARS a dissemination tree."""
+        idx = np.ascontiguousarray(roots, dtype=np.int32).reshape(-1)
+        out, st = self._hops_out(max(int(self._L.rm_node_count(self._h)), 0), fields)
+        tot = _lib.HopsTotals()
+        check(self._L.rm_hops_query(self._h, int(direction), float(min_rssi_dbm), _ptr(idx), idx.shape[0], C.byref(st), C.byref(tot)))
+        return out, self._hops_totals(tot)
+
+    def hops_device(self, direction, dev_roots_ptr, n_roots, dev_hop_ptr, dev_parent_ptr=None, dev_rssi_ptr=None, dev_children_ptr=None,
+                    min_rssi_dbm=-np.inf):
+        """rm_hops_query_device: the raw form -- roots and outputs (int32[n], int32[n] or None, float64[n] or None, int32[n] or
+        None) in device memory; waits once per level, complete on return -> {"reached", "max_hop", "roots"}"""
+        st = _lib.HopsOut(hop=dev_hop_ptr, parent=dev_parent_ptr, rssi=dev_rssi_ptr, children=dev_children_ptr)
+        tot = _lib.HopsTotals()
+        check(self._L.rm_hops_query_device(self._h, int(direction), float(min_rssi_dbm), dev_roots_ptr, int(n_roots), C.byref(st), C.byref(tot)))
+        return self._hops_totals(tot)
+
+    def hops_next_device(self, dev_parent_ptr, dev_src_ptr, n, dev_want_ptr):
+        """rm_hops_next_device: want[i] = parent[src[i]] (-1 for a source outside the table), all device memory -- the want list
+        of unicast_query_device over source rows; enqueued without waiting"""
+        check(self._L.rm_hops_next_device(self._h, dev_parent_ptr, dev_src_ptr, int(n), dev_want_ptr))
+
+    @staticmethod
+    def hops_from_links(n_nodes, node, far, rssi, roots, min_rssi_dbm=-np.inf, fields=None):
+        """rm_hops_from_links (pure host function): the same rule over an explicit list of candidate links -- far[i] may be
+        node[i]'s parent with rssi[i] -> what hops returns"""
+        node = np.ascontiguousarray(node, dtype=np.int32).reshape(-1)
+        far = np.ascontiguousarray(far, dtype=np.int32).reshape(-1)
+        rssi = np.ascontiguousarray(rssi, dtype=np.float64).reshape(-1)
+        if not (node.shape == far.shape == rssi.shape):
+            raise ValueError("node, far and rssi have one entry per link")
+        idx = np.ascontiguousarray(roots, dtype=np.int32).reshape(-1)
+        out, st = Engine._hops_out(max(int(n_nodes), 0), fields)
+        tot = _lib.HopsTotals()
+        check(_lib.lib().rm_hops_from_links(int(n_nodes), node.shape[0], _ptr(node), _ptr(far), _ptr(rssi), float(min_rssi_dbm), _ptr(idx),
+                                            idx.shape[0], C.byref(st), C.byref(tot)))
+        return out, Engine._hops_totals(tot)
+
     def linkstats_watch_device(self, dev_peers_ptr, dev_nodes_ptr=None, n=None):
         """rm_linkstats_watch_device: rm_linkstats_watch with rows (int32[n][K] of the enabled K) and list in device memory (None: all
         nodes) -- e.g. the peer block of neighbors_device(NB_HEARS, K); validated on the device, waited for"""

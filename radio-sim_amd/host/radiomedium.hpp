@@ -37,6 +37,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <deque>
+#include <limits>
 #include <memory>
 #include <cstdio>
 #include <stdexcept>
@@ -1015,6 +1016,40 @@ public:
             }
         }
         return rows;
+    }
+    // The hop query (extension E17): hop count and best parent toward a set of roots over the potential links with rssi >= minRssi.
+    // direction is the link between a node and its parent, seen from the node: RM_NB_HEARD_BY a collection tree, RM_NB_HEARS a
+    // dissemination tree.  One row per node in node order; empty rows and lastError on a refusal.
+    struct HopRow {
+        int hop;      // -1: not reached
+        Node *parent; // nullptr for a root and for a node that was not reached
+        double rssi;  // the link to the parent, NaN without one
+        int children;
+    };
+    struct HopTree {
+        std::vector<HopRow> rows;
+        rm_hops_totals totals;
+    };
+    HopTree hops(int direction, const std::vector<const Node *> &roots, double minRssi = -std::numeric_limits<double>::infinity())
+    {
+        lastError.clear();
+        HopTree tree{{}, {0, -1, 0, 0}};
+        if (!simulator || !syncNodes()) return tree;
+        const std::vector<Node *> &all = simulator->getNodes();
+        std::vector<int32_t> idx;
+        for (const Node *nd : roots) idx.push_back(nd ? nd->index : -1);
+        const size_t n = all.size();
+        std::vector<int32_t> hop(n + 1), parent(n + 1), children(n + 1);
+        std::vector<double> rssi(n + 1);
+        const rm_hops_out out{hop.data(), parent.data(), rssi.data(), children.data()};
+        if (rm_hops_query(ctx_, int32_t(direction), minRssi, idx.data(), int32_t(idx.size()), &out, &tree.totals) != RM_OK) {
+            lastError = rm_last_error();
+            tree.totals = {0, -1, 0, 0};
+            return tree;
+        }
+        tree.rows.resize(n);
+        for (size_t j = 0; j < n; ++j) tree.rows[j] = HopRow{hop[j], parent[j] >= 0 ? all[size_t(parent[j])] : nullptr, rssi[j], children[j]};
+        return tree;
     }
     // Topology discovery into the watched links (E16 -> E14) without a link passing through the host: setLinkWatch(K) (K = 1, 2, 4
     // or 8), every node's RM_NB_HEARS row computed into the engine's staging block, taken as the watch rows on the device.  The
