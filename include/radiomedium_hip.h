@@ -1043,6 +1043,63 @@ int rm_hops_next_device(rm_context *ctx, const int32_t *dev_parent, const int32_
 int rm_hops_from_links(int32_t n_nodes, int32_t n_links, const int32_t *node, const int32_t *far, const double *rssi, double min_rssi_dbm,
                        const int32_t *roots, int32_t n_roots, const rm_hops_out *out, rm_hops_totals *totals);
 
+/* ---- route query: minimum-ETX routes toward a set of roots -------------------------------------------------------------
+ * (not reference behaviour.)  A pure function of the node table, the model and the query's
+ * parameters, on RM_MODEL_LOGDIST only (with or without RM_LD_SINR); the context's frame error model plays no part.  Per node: the
+ * least path cost toward any root over the potential links, each link costing its expected transmission count in units of 1/128,
+ * and the parent on such a path.
+ * link(j, p, dir) is the hop query's, rssi >= min_rssi_dbm included.  Its cost, one rounding per operation and no fma:
+ * snr = rssi - 10.0 * det_log10(ld_noise_lin) (what the SINR medium reports as sinr for a heard link with nothing else on the air);
+ * psr = 1.0 for RM_EM_NONE, else rm_error_model_psr's value for (kind, us_per_bit) at (snr, air_us); q = 128.0 / psr,
+ * c = floor(q + 0.5).  The link counts iff psr > 0.0 and c <= (double)max_link_cost (a NaN fails both); its cost is (uint32_t)c, which
+ * lies in 128 .. max_link_cost.
+ * cost[r] = 0 for every root r, whatever its radio state; otherwise cost[j] is the minimum over the counting links of
+ * cost[p] + c(j, p) (the least fixed point); a node never reached has RM_ROUTE_UNREACHED.  parent[j] is, among all p with a
+ * counting link and cost[p] + c(j, p) == cost[j], the first in the neighbour query's order (rssi descending, then the smaller
+ * node index); rssi[j] is that link's rssi, link_cost[j] its c; children[p] is the number of nodes whose parent is p.  Roots and
+ * unreached nodes have parent -1, the NaN 0x7FF8000000000000 and link_cost 0.  Totals: reached the nodes with a cost, roots the
+ * distinct valid roots, max_cost the largest cost (0 when nothing is reached).  Roots may repeat; n_roots = 0 is RM_OK.
+ * With RM_EM_NONE every counting link costs 128: cost = 128 * hop, and parent, rssi and children are the hop query's.
+ * The answer does not depend on the walk, the launch geometry, the order of the relaxations or the table's sort state, and a query
+ * changes nothing the hop query leaves alone, nor the hop query's scratch.  parent is a valid input of rm_hops_next_device and a
+ * valid K = 1 table of rm_linkstats_watch_device. */
+#define RM_ROUTE_UNREACHED UINT64_MAX
+typedef struct rm_routes_params {
+    int32_t direction;      /* RM_NB_HEARD_BY / RM_NB_HEARS: the link between a node and its parent, seen from the node */
+    int32_t kind;           /* RM_EM_NONE or RM_EM_OQPSK_250K */
+    double us_per_bit;      /* finite and > 0 */
+    int64_t air_us;         /* >= 0: the air time of the frame the cost is for */
+    double min_rssi_dbm;    /* not a NaN */
+    uint32_t max_link_cost; /* 128 .. 65535: a link whose cost is above it does not count */
+    uint32_t reserved;      /* 0 */
+} rm_routes_params;
+/* the outputs, [n_nodes] each, by node index: cost is required, the others may be NULL */
+typedef struct rm_routes_out { uint64_t *cost; int32_t *parent; double *rssi; uint32_t *link_cost; int32_t *children; } rm_routes_out;
+typedef struct rm_routes_totals { int32_t reached; int32_t roots; uint64_t max_cost; } rm_routes_totals;
+/* dev_roots and the arrays dev_out (a host struct) points to are device memory; a root entry outside 0 .. n_nodes - 1 is ignored.
+ * The call waits on the context's stream once per round and returns when the outputs are complete; totals (host) may be NULL.
+ * RM_ERR_STATE, nothing launched: as rm_hops_query_device.  RM_ERR_INVALID: NULL ctx, params, dev_out or cost, an unknown direction
+ * or kind, reserved != 0, us_per_bit not finite and > 0, air_us < 0, a NaN min_rssi_dbm, max_link_cost outside 128 .. 65535,
+ * n_roots < 0, n_roots > 0 with NULL roots. */
+int rm_routes_query_device(rm_context *ctx, const rm_routes_params *params, const int32_t *dev_roots, int32_t n_roots,
+                           const rm_routes_out *dev_out, rm_routes_totals *totals);
+/* the same with host arrays; a root outside the table is RM_ERR_INVALID before anything is launched */
+int rm_routes_query(rm_context *ctx, const rm_routes_params *params, const int32_t *roots, int32_t n_roots, const rm_routes_out *out,
+                    rm_routes_totals *totals);
+/* what the context's last completed route query did, for measurements: its relaxation rounds (launches) and the frontier entries
+ * they walked in all (entries / n_nodes is the re-labelling factor); 0 and 0 before the first query.  Either may be NULL. */
+int rm_routes_last_work(rm_context *ctx, int32_t *rounds, uint64_t *entries);
+/* The link cost alone, a pure host function without a device: 1 and *cost when a link of this rssi counts under params at a noise
+ * floor of noise_dbm (ld_noise_lin = det_pow10(noise_dbm / 10), as the model derives it), else 0 -- rssi below min_rssi_dbm or NaN,
+ * psr 0, a cost above the cap, or parameters the query would refuse.  direction is not looked at; cost may be NULL. */
+int rm_routes_link_cost(const rm_routes_params *params, double noise_dbm, double rssi, uint32_t *cost);
+/* The same rule over an explicit list of candidate links, a pure host function without a device, like rm_hops_from_links: entry i
+ * says that far[i] may be node[i]'s parent with rssi[i].  direction is not looked at.  RM_ERR_INVALID: what rm_hops_from_links and
+ * the query's parameter check refuse. */
+int rm_routes_from_links(int32_t n_nodes, int32_t n_links, const int32_t *node, const int32_t *far, const double *rssi,
+                         const rm_routes_params *params, double noise_dbm, const int32_t *roots, int32_t n_roots, const rm_routes_out *out,
+                         rm_routes_totals *totals);
+
 /* ---- several devices behind one caller --------------------------------------------------------------
  * The reference host is ONE process (Main.java:65-73): a group drives n contexts from one host thread, one
  * per device (an ordinal may repeat: several partitions on one GPU).  Receivers are partitioned over the

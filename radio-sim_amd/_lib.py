@@ -86,6 +86,26 @@ class HopsTotals(C.Structure):
 
 HOPS_FIELDS = (("hop", np.int32), ("parent", np.int32), ("rssi", np.float64), ("children", np.int32))
 
+
+class RoutesParams(C.Structure):
+    """rm_routes_params: the parameters of the route query (40 bytes)"""
+    _fields_ = [("direction", C.c_int32), ("kind", C.c_int32), ("us_per_bit", C.c_double), ("air_us", C.c_int64),
+                ("min_rssi_dbm", C.c_double), ("max_link_cost", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RoutesOut(C.Structure):
+    """rm_routes_out: the output arrays of the route query, [n_nodes] each; all but cost may be NULL"""
+    _fields_ = [("cost", C.c_void_p), ("parent", C.c_void_p), ("rssi", C.c_void_p), ("link_cost", C.c_void_p), ("children", C.c_void_p)]
+
+
+class RoutesTotals(C.Structure):
+    """rm_routes_totals"""
+    _fields_ = [("reached", C.c_int32), ("roots", C.c_int32), ("max_cost", C.c_uint64)]
+
+
+ROUTES_FIELDS = (("cost", np.uint64), ("parent", np.int32), ("rssi", np.float64), ("link_cost", np.uint32), ("children", np.int32))
+ROUTE_UNREACHED = 0xFFFFFFFFFFFFFFFF
+
 NODE_STATS_DTYPE = np.dtype([(name, "<u8") for name, _ in NodeStats._fields_])
 assert NODE_STATS_DTYPE.itemsize == C.sizeof(NodeStats) == 64
 
@@ -401,6 +421,12 @@ SIGNATURES = {
     "rm_hops_next_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "rm_hops_from_links": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int32,
                                      C.POINTER(HopsOut), C.POINTER(HopsTotals)]),
+    "rm_routes_query_device": (C.c_int, [C.c_void_p, C.POINTER(RoutesParams), C.c_void_p, C.c_int32, C.POINTER(RoutesOut), C.POINTER(RoutesTotals)]),
+    "rm_routes_query": (C.c_int, [C.c_void_p, C.POINTER(RoutesParams), C.c_void_p, C.c_int32, C.POINTER(RoutesOut), C.POINTER(RoutesTotals)]),
+    "rm_routes_last_work": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
+    "rm_routes_link_cost": (C.c_int, [C.POINTER(RoutesParams), C.c_double, C.c_double, C.POINTER(C.c_uint32)]),
+    "rm_routes_from_links": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RoutesParams), C.c_double, C.c_void_p,
+                                       C.c_int32, C.POINTER(RoutesOut), C.POINTER(RoutesTotals)]),
     "rm_det_math": (C.c_double, [C.c_int32, C.c_double]),
     "rm_link_hash": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
     "rm_evq_init": (None, [C.c_void_p]),

@@ -126,6 +126,7 @@ void passes_release(rm_context *c)
     linkstats_release(c);
     neighbors_release(c);
     hops_release(c);
+    routes_release(c);
 }
 
 } // namespace rmh

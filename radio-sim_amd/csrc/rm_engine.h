@@ -997,6 +997,40 @@ hipError_t launch_hop_parent(hipStream_t s, const NodesDev &nd, const ModelDev &
 // want[i] = parent[src[i]], -1 for src[i] outside 0 .. n_nodes - 1
 hipError_t launch_hop_next(hipStream_t s, const int32_t *parent, int n_nodes, const int32_t *src, int n, int32_t *want);
 
+// (rm_routes.hip) the route query.  The outputs are [n_nodes] by node index (all but cost may
+// be nullptr).  stamp [n_nodes]: the last round a node was queued for; queue[2] [n_nodes] each: round r reads queue[r & 1] and
+// appends to the other; tail[2]: their entry counts.  prep / off_list: what launch_nb_prep left for the HEARS walk.  The link
+// cost's parameters: noise_db = 10 * det_log10(ld_noise_lin), max_cost = double(max_link_cost).
+struct RouteDev {
+    unsigned long long *cost;
+    int32_t *parent;
+    uint64_t *rssi;
+    uint32_t *link_cost;
+    int32_t *children;
+    uint32_t *stamp;
+    int32_t *queue[2];
+    uint32_t *tail; // [2]
+    unsigned long long *sums; // [2]: reached, max_cost (launch_route_totals)
+    const unsigned long long *prep;
+    const int32_t *off_list;
+    double min_rssi;
+    int kind;
+    double us_per_bit;
+    int64_t air_us;
+    double noise_db;
+    double max_cost;
+};
+// the outputs as "nothing reached", the stamps 0, then the roots (device memory, entries outside the table skipped, duplicates
+// claimed once) with cost 0 as frontier 0: queue[0][0 .. tail[0]); tail[] zeroed by the caller on the stream in front of it
+hipError_t launch_route_seed(hipStream_t s, const NodesDev &nd, const RouteDev &r, const int32_t *roots, int n_roots);
+// one round: a wave per node of queue[round & 1][0 .. count) lowers its link ends' costs and appends the lowered ones to the other
+// queue, each at most once; it zeroes tail[round & 1] for the round after
+hipError_t launch_route_relax(hipStream_t s, const NodesDev &nd, const ModelDev &m, const RouteDev &r, int direction, bool scan, int count, int round);
+// parent, rssi, link_cost and children of every reached node that is no root, behind the last round (a wave per table node)
+hipError_t launch_route_parent(hipStream_t s, const NodesDev &nd, const ModelDev &m, const RouteDev &r, int direction, bool scan);
+// sums[0] += the reached nodes, sums[1] = max(sums[1], the largest finite cost); sums zeroed by the caller
+hipError_t launch_route_totals(hipStream_t s, const RouteDev &r, int n);
+
 // (rm_unicast.hip) the unicast outcome query, one launch: a lane per entry.  n_slots result slots described by dev_slots -- or, with
 // dev_slots == nullptr, the one slot `lone`.  Slots form (dev_prefix: [n_slots + 1] exclusive prefix of the entries per slot; nullptr
 // with one slot): entry e is packet e - prefix[b] of slot b.  At form: entry e names (dev_slot[e], dev_pkt[e]).

@@ -237,6 +237,19 @@ struct rm_context : TickSlot {
         DevBuf<int32_t> queue;
         uint32_t *h_tail = nullptr;
     } hp;
+    // the route query (E18; rm_api_routes.cpp, rm_routes.hip): scratch of its own (the hop query's is not touched) -- words[0 .. 1]
+    // are k_nb_prep's, words[2] the two queues' tails, words[3 .. 4] the totals' sums; one block, zeroed per query --, the list of
+    // radios that are off, the per-node round stamps, the two frontier queues ([n_nodes] each), and the pinned words the tail
+    // and the sums are copied to.  Nothing is allocated before the first query.
+    struct Routes {
+        DevBuf<unsigned long long> words;
+        DevBuf<int32_t> off_list;
+        DevBuf<uint32_t> stamp;
+        DevBuf<int32_t> queue; // [2][n_nodes]
+        unsigned long long *h_words = nullptr;
+        int32_t last_rounds = 0;   // the last query's relaxation launches and the frontier entries they walked (rm_routes_last_work)
+        uint64_t last_entries = 0;
+    } rt;
     // traffic schedules (E15; rm_api_traffic.cpp, rm_traffic.hip): one schedule per node index; the pinned, host-mapped block a list
     // update or a list read is staged through; the generator's scratch (the windows, the units' counts and packets) and the pinned
     // staging of its windows -- two blocks, each rewritten only after its copy has completed
@@ -795,6 +808,10 @@ void neighbors_release(rm_context *c);
 // ---- rm_api_hops.cpp: the hop query (E17)
 // rm_destroy
 void hops_release(rm_context *c);
+
+// ---- rm_api_routes.cpp: the route query (E18)
+// rm_destroy
+void routes_release(rm_context *c);
 
 // ---- rm_api_traffic.cpp: traffic schedules (E15)
 // rm_nodes_upload: another node count clears the feature

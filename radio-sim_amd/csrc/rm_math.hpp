@@ -149,6 +149,30 @@ RM_HD double em_psr_oqpsk(double us_per_bit, double sinr_db, int64_t air_us)
     return det_exp2(n * det_log2(1.0 - ber));
 }
 
+// the route query's link cost: ETX in units of 1/128 from the link's rssi alone -- the text the kernels
+// (rm_routes.hip) and rm_routes_link_cost / rm_routes_from_links are both built from.  noise_db = 10 * det_log10(ld_noise_lin),
+// max_cost = double(max_link_cost).  false: the link does not count (psr 0 or NaN, or a cost above the cap).
+// The shortcut is E10's (errmodel_body): y2 < -1022 makes every term of the sum 0, so ber = 0 and psr = det_exp2(n * 0) = 1.
+RM_HD bool route_link_cost(int kind, double us_per_bit, int64_t air_us, double noise_db, double max_cost, double rssi, uint32_t &cost)
+{
+    double psr = 1.0;
+    if (kind == RM_EM_OQPSK_250K) {
+        const double snr = rssi - noise_db;
+        const double s = det_pow10(snr / 10.0);
+        const double y2 = ((20.0 * s) * (1.0 / 2.0 - 1.0)) * 1.4426950408889634;
+        if (!(y2 < -1022.0)) {
+            const double ber = em_ber_oqpsk(s);
+            psr = ber;
+            if (ber == ber) psr = det_exp2((double(air_us) / us_per_bit) * det_log2(1.0 - ber));
+        }
+    }
+    const double q = 128.0 / psr;
+    const double c = floor(q + 0.5);
+    if (!(psr > 0.0) || !(c <= max_cost)) return false;
+    cost = uint32_t(c);
+    return true;
+}
+
 // the link's uniform deviate: a hash of (seed, the frame's start, its source node, the receiver) and of nothing else -- not of
 // packet numbers, ticks, slots or ranks, so a frame's verdict at a receiver is the same however the frame was evaluated
 RM_HD double em_draw(uint64_t seed, int32_t src, int64_t start_us, int32_t dst)

@@ -582,6 +582,70 @@ class Engine:
                                             idx.shape[0], C.byref(st), C.byref(tot)))
         return out, Engine._hops_totals(tot)
 
+    # -- route query: minimum-ETX routes toward a set of roots
+    @staticmethod
+    def routes_params(direction=_lib.NB_HEARD_BY, kind=_lib.EM_OQPSK_250K, us_per_bit=4.0, air_us=4064, min_rssi_dbm=-np.inf,
+                      max_link_cost=1024, reserved=0):
+        """an rm_routes_params"""
+        return _lib.RoutesParams(direction=int(direction), kind=int(kind), us_per_bit=float(us_per_bit), air_us=int(air_us),
+                                 min_rssi_dbm=float(min_rssi_dbm), max_link_cost=int(max_link_cost), reserved=int(reserved))
+
+    @staticmethod
+    def _routes_out(n, fields):
+        out = {name: np.empty(n, dtype=dt) for name, dt in _lib.ROUTES_FIELDS if name == "cost" or fields is None or name in fields}
+        return out, _lib.RoutesOut(**{name: a.ctypes.data for name, a in out.items()})
+
+    @staticmethod
+    def _routes_totals(tot):
+        return {"reached": int(tot.reached), "roots": int(tot.roots), "max_cost": int(tot.max_cost)}
+
+    def routes(self, params, roots, fields=None):
+        """rm_routes_query: least path cost (ETX in units of 1/128) toward the roots over the potential links and the parent on
+        such a path -> ({"cost": uint64[n] (ROUTE_UNREACHED: not reached), "parent": int32[n], "rssi": float64[n] (NaN beside a
+        -1), "link_cost": uint32[n], "children": int32[n]}, {"reached", "roots", "max_cost"}).  params: routes_params(...)"""
+        idx = np.ascontiguousarray(roots, dtype=np.int32).reshape(-1)
+        out, st = self._routes_out(max(int(self._L.rm_node_count(self._h)), 0), fields)
+        tot = _lib.RoutesTotals()
+        check(self._L.rm_routes_query(self._h, C.byref(params), _ptr(idx), idx.shape[0], C.byref(st), C.byref(tot)))
+        return out, self._routes_totals(tot)
+
+    def routes_device(self, params, dev_roots_ptr, n_roots, dev_cost_ptr, dev_parent_ptr=None, dev_rssi_ptr=None, dev_link_cost_ptr=None,
+                      dev_children_ptr=None):
+        """rm_routes_query_device: the raw form -- roots and outputs (uint64[n], int32[n], float64[n], uint32[n], int32[n]; all but
+        the first may be None) in device memory; waits once per round, complete on return -> {"reached", "roots", "max_cost"}"""
+        st = _lib.RoutesOut(cost=dev_cost_ptr, parent=dev_parent_ptr, rssi=dev_rssi_ptr, link_cost=dev_link_cost_ptr, children=dev_children_ptr)
+        tot = _lib.RoutesTotals()
+        check(self._L.rm_routes_query_device(self._h, C.byref(params), dev_roots_ptr, int(n_roots), C.byref(st), C.byref(tot)))
+        return self._routes_totals(tot)
+
+    def routes_last_work(self):
+        """rm_routes_last_work: (relaxation rounds, frontier entries walked in all) of the last completed route query"""
+        rounds, entries = C.c_int32(0), C.c_uint64(0)
+        check(self._L.rm_routes_last_work(self._h, C.byref(rounds), C.byref(entries)))
+        return int(rounds.value), int(entries.value)
+
+    @staticmethod
+    def route_link_cost(params, noise_dbm, rssi):
+        """rm_routes_link_cost (pure host function): the cost of a link of this rssi, or None when it does not count"""
+        c = C.c_uint32(0)
+        return int(c.value) if _lib.lib().rm_routes_link_cost(C.byref(params), float(noise_dbm), float(rssi), C.byref(c)) else None
+
+    @staticmethod
+    def routes_from_links(n_nodes, node, far, rssi, params, noise_dbm, roots, fields=None):
+        """rm_routes_from_links (pure host function): the same rule over an explicit list of candidate links -- far[i] may be
+        node[i]'s parent with rssi[i] -> what routes returns"""
+        node = np.ascontiguousarray(node, dtype=np.int32).reshape(-1)
+        far = np.ascontiguousarray(far, dtype=np.int32).reshape(-1)
+        rssi = np.ascontiguousarray(rssi, dtype=np.float64).reshape(-1)
+        if not (node.shape == far.shape == rssi.shape):
+            raise ValueError("node, far and rssi have one entry per link")
+        idx = np.ascontiguousarray(roots, dtype=np.int32).reshape(-1)
+        out, st = Engine._routes_out(max(int(n_nodes), 0), fields)
+        tot = _lib.RoutesTotals()
+        check(_lib.lib().rm_routes_from_links(int(n_nodes), node.shape[0], _ptr(node), _ptr(far), _ptr(rssi), C.byref(params), float(noise_dbm),
+                                              _ptr(idx), idx.shape[0], C.byref(st), C.byref(tot)))
+        return out, Engine._routes_totals(tot)
+
     def linkstats_watch_device(self, dev_peers_ptr, dev_nodes_ptr=None, n=None):
         """rm_linkstats_watch_device: rm_linkstats_watch with rows (int32[n][K] of the enabled K) and list in device memory (None: all
         nodes) -- e.g. the peer block of neighbors_device(NB_HEARS, K); validated on the device, waited for"""

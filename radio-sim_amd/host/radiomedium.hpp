@@ -1051,6 +1051,49 @@ public:
         for (size_t j = 0; j < n; ++j) tree.rows[j] = HopRow{hop[j], parent[j] >= 0 ? all[size_t(parent[j])] : nullptr, rssi[j], children[j]};
         return tree;
     }
+    // The route query (extension E18): least path cost (ETX in units of 1/128) toward a set of roots over the potential links and
+    // the parent on such a path.  params.direction is the link between a node and its parent, seen from the node.  One row per node
+    // in node order; empty rows and lastError on a refusal.
+    struct RouteRow {
+        uint64_t cost; // RM_ROUTE_UNREACHED: not reached
+        Node *parent;  // nullptr for a root and for a node that was not reached
+        double rssi;   // the link to the parent, NaN without one
+        uint32_t linkCost;
+        int children;
+    };
+    struct RouteTree {
+        std::vector<RouteRow> rows;
+        rm_routes_totals totals;
+    };
+    static rm_routes_params routeParams(int direction, int kind = RM_EM_OQPSK_250K, double usPerBit = 4.0, int64_t airUs = 4064,
+                                        double minRssi = -std::numeric_limits<double>::infinity(), uint32_t maxLinkCost = 1024)
+    {
+        return rm_routes_params{int32_t(direction), int32_t(kind), usPerBit, airUs, minRssi, maxLinkCost, 0};
+    }
+    RouteTree routes(const rm_routes_params &params, const std::vector<const Node *> &roots)
+    {
+        lastError.clear();
+        RouteTree tree{{}, {0, 0, 0}};
+        if (!simulator || !syncNodes()) return tree;
+        const std::vector<Node *> &all = simulator->getNodes();
+        std::vector<int32_t> idx;
+        for (const Node *nd : roots) idx.push_back(nd ? nd->index : -1);
+        const size_t n = all.size();
+        std::vector<uint64_t> cost(n + 1);
+        std::vector<int32_t> parent(n + 1), children(n + 1);
+        std::vector<uint32_t> linkCost(n + 1);
+        std::vector<double> rssi(n + 1);
+        const rm_routes_out out{cost.data(), parent.data(), rssi.data(), linkCost.data(), children.data()};
+        if (rm_routes_query(ctx_, &params, idx.data(), int32_t(idx.size()), &out, &tree.totals) != RM_OK) {
+            lastError = rm_last_error();
+            tree.totals = {0, 0, 0};
+            return tree;
+        }
+        tree.rows.resize(n);
+        for (size_t j = 0; j < n; ++j)
+            tree.rows[j] = RouteRow{cost[j], parent[j] >= 0 ? all[size_t(parent[j])] : nullptr, rssi[j], linkCost[j], children[j]};
+        return tree;
+    }
     // Topology discovery into the watched links (E16 -> E14) without a link passing through the host: setLinkWatch(K) (K = 1, 2, 4
     // or 8), every node's RM_NB_HEARS row computed into the engine's staging block, taken as the watch rows on the device.  The
     // mirror then reads the rows back once, so that they survive apply() like rows set by watchLinks.  false and lastError on a refusal.
