@@ -378,7 +378,10 @@ int rm_batch_result_view(rm_context *ctx, int32_t n_slots, rm_host_result *out, 
  * own pair of HIP events (hipExtLaunchKernelGGL), which take the start and the end of THAT dispatch -- the interval a
  * rocprofv3 kernel trace reports for it, without the launch gap before it and without whatever other contexts have in
  * flight.  rm_profile_read returns the number of sampled sequences and the summed kernel milliseconds per stage,
- * rm_profile_kernels the same per kernel, under the name rocprofv3 prints (template arguments as the launch site spells them). */
+ * rm_profile_kernels the same per kernel, under the name rocprofv3 prints (template arguments as the launch site spells them).
+ * The launches of rm_events_process and rm_node_info are sequences of their own, sampled while the count of evaluated ticks is
+ * a multiple of every_n (they do not move it on): k_ev_append_select tells a drain that took the last tick's append into its
+ * first launch from one that found it done (k_ev_select; k_ev_append, where rm_node_info had to flush it). */
 enum rm_profile_stage {
     RM_STAGE_FILTER = 0,  /* k_filter (or k_tick_prep + k_filter_wg): all (frame, receiver) pairs, conservative */
     RM_STAGE_EXACT = 1,   /* k_exact: the reference's fp64 arithmetic on the candidates */
@@ -1197,10 +1200,29 @@ int rm_dist_tick_run_sources_device(rm_context *ctx, int64_t t_begin_us, int64_t
  * rm_node_info gives the per-node fields of a time-step message (net/JSONClientConnection.java:331-341):
  * Transciever.getRSSI (:52-61), getReceivingState (:67-78: 0 listening, 1 transmitting, 2 receiving,
  * 3 disabled) and the wireless channel, from the device-resident radio state; nodes == NULL: nodes 0..n-1.
- * On a receiver partition (rm_set_partition) a context keeps the events of its own nodes only. */
+ * On a receiver partition (rm_set_partition) a context keeps the events of its own nodes only.
+ *
+ * What the two capacities of rm_events_enable bound (each is rounded up to a power of two, 64 at least; 0: 2^16 packets,
+ * 2^21 links).  The pending packets and their heard links live in two rings, and a ring gives room back from its head only:
+ *   - a hand-over of a tick of n records (padding records included) with L heard links is refused as a whole if
+ *     occupied packets + n > max_pending_packets or occupied links + L > max_pending_links, occupied as the last drain left
+ *     it plus what was handed over since; a tick that fills a ring exactly is taken.  A refused tick keeps its packet numbers
+ *     (rm_events_next_packet moves on) but leaves no events; the next drain -- and only that one -- returns RM_ERR_CAPACITY,
+ *     with its view filled as ever from the packets that are in the rings, which take the next ticks again;
+ *   - a packet is finished by the drain that fires its last event (t1 = max(start, current time) + air time < time_us; a
+ *     packet of the constant-loss medium by the first drain after its hand-over; a padding record is no packet and is finished
+ *     as it is stored);
+ *   - a drain first moves the head up to the oldest packet, this tick's included, that was not finished BEFORE this drain (to
+ *     the tail if there is none), then fires.  So what a drain finishes is released by the NEXT drain, and only up to the
+ *     oldest packet still on the air: one long frame at the head holds every packet handed in after it, finished or not,
+ *     and their links.
+ * pending_packets is the occupied part of the packet ring after that move, oldest_packet the number of the packet at its
+ * head.  To size the rings: the records (links) of every tick handed in while the longest frame is on the air, plus those of
+ * the tick before and of one more drain. */
 typedef struct rm_delivery_view {
     uint32_t count;            /* deliveries of this drain */
-    uint32_t pending_packets;  /* packets with events still queued */
+    uint32_t pending_packets;  /* packets in the ring when this drain began to fire: from the oldest one that had events queued
+                                * then to the newest, finished ones in between included (the rule above) */
     int64_t oldest_packet;     /* number of the oldest of them (== rm_events_next_packet: none): every packet
                                 * below it has fired its last event and may be forgotten by the host */
     const int64_t *packet;     /* NULL since ABI version 3: the packet numbers come once per run (below) */

@@ -78,7 +78,7 @@ def inputs(O, name):
 
 
 SCENARIOS = ("udgm_lone", "transmit", "logdist_batch", "big_batch", "sinr_lone", "sinr_batch", "sinr_overlap", "overflow",
-             "gathered", "gathered_spatial", "gathered_overlap", "events")
+             "gathered", "gathered_spatial", "gathered_overlap", "events", "events_rings")
 WORLD = 3
 MOVE_TICK = 3       # sinr_lone: nodes 0..4 move 3 m before this tick
 CAP_SMALL, CAP_LARGE = 1 << 16, 1 << 22   # (tick 3: ~75 k heard links; the others a few hundred)
@@ -104,6 +104,8 @@ def run_scenario(name, rsa, O, res, tag):
     from util import DeviceArray, to_tx_records
     if name == "events":
         return run_events(rsa, O)
+    if name == "events_rings":
+        return run_events_rings(rsa, O)
     keep = []
     if name.startswith("gathered"):
         return run_gathered(name, rsa, O, res, tag)
@@ -246,6 +248,26 @@ def run_events(rsa, O):
         s = Session(O, rsa, eng, 100 + n, kind, params, n=n, **kw)
         if run_plan(s, plan) <= 0:
             raise AssertionError("the reception stage delivered nothing")
+    return engines
+
+
+def run_events_rings(rsa, O):
+    """the reception stage on rings of 64 packets and a few thousand links (tests/events_ring_ref.py's scenes): a session that
+    wraps both rings several times, lone ticks and batches mixed, and one whose packet ring refuses ticks (named by source indices:
+    the lone ticks whose append RM_EV_FUSE keeps for the drain's first launch, or not) -- against the oracle's
+    replay and the host model of the rings, as tests/test_gpu_events_rings.py holds them under the defaults"""
+    import events_ring_ref as R
+    from test_gpu_events_batch import Session, run_plan
+    engines = []
+    for (seed, kind, params, kw), plan, conditions in (
+            (R.WRAP["udgm_draws"], R.MIXED_PLAN, lambda rep: R.wrap_conditions(rep, "udgm_draws")),
+            (R.OVERFLOW["packets_sources"], ("lone",) * R.OVERFLOW_TICKS, lambda rep: R.overflow_conditions(rep, "packets", "packets"))):
+        eng = rsa.Engine(0)
+        engines.append(eng)
+        s = Session(O, rsa, eng, seed, kind, params, **kw)
+        if run_plan(s, plan) <= 0:
+            raise AssertionError("the reception stage delivered nothing")
+        conditions(s.rings.report())
     return engines
 
 

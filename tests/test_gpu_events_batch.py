@@ -5,9 +5,11 @@ capacity reports."""
 import numpy as np
 import pytest
 
-from util import DeviceArray, KINDS, configure_engine, oracle_model, random_nodes, to_tx_records
+from events_ring_ref import Traffic
+from util import DeviceArray, KINDS, configure_engine, random_nodes, to_tx_records
 
 pytestmark = pytest.mark.gpu
+ERR_CAPACITY = -4
 
 
 # ---------------------------------------------------------------- helpers (after tests/test_gpu_events.py)
@@ -61,59 +63,25 @@ def check_nodes(eng, sim, nodes, what, own=None):
     np.testing.assert_array_equal(shadow[1], got_state, err_msg=what + " incremental state")
 
 
-class Session:
-    """One engine and the oracle's serial replay of the same Simulator: ticks go in as a batch (handed over with
-    rm_events_process_batch), as lone ticks (rm_tick_* + rm_events_process) or not at all (a plain drain)."""
+class Session(Traffic):
+    """One engine and the oracle's serial replay of the same Simulator (events_ring_ref.Traffic: the seeded ticks and the oracle's
+    side): ticks go in as a batch (handed over with rm_events_process_batch), as lone ticks (rm_tick_* + rm_events_process) or not
+    at all (a plain drain).  capacity=(packets, links): the rings' sizes (the default: rm_events_enable's own); every drain's
+    return code, pending_packets and oldest_packet are then held to the host model of the rings as well.
+    info_between: rm_node_info between every lone tick and its drain (the tick's append then runs on its own)."""
 
-    def __init__(self, O, rsa, eng, seed, kind, params, n=1500, per_tick=30, tick_styles=(1000,), aligned=False,
-                 hex_lengths=(0, 2, 20, 64, 254), matrix=None, sinr=False, own=None, draws=True, min_per_tick=0):
-        self.O, self.rsa, self.eng, self.kind, self.own, self.sinr = O, rsa, eng, kind, own, sinr
-        self.rng = rng = np.random.default_rng(seed)
-        self.n, self.per_tick, self.tick_styles, self.aligned, self.hex_lengths = n, per_tick, tick_styles, aligned, hex_lengths
-        self.min_per_tick = min_per_tick
-        side = 50.0 * np.sqrt(np.pi * n / 20.0)
-        self.nodes = nodes = random_nodes(O, n, side, seed)
-        if draws:
-            nodes.rxprob[rng.choice(n, n // 5, replace=False)] = 0.6
-            nodes.txprob[rng.choice(n, n // 20, replace=False)] = 0.5
-        nodes.enabled[rng.choice(n, n // 50, replace=False)] = 0
-        configure_engine(eng, nodes, kind, params, matrix)
+    def __init__(self, O, rsa, eng, seed, kind, params, matrix=None, own=None, capacity=None, info_between=False, **kw):
+        Traffic.__init__(self, O, seed, kind, params, matrix=matrix, own=own, capacity=capacity, **kw)
+        self.rsa, self.eng, self.info_between = rsa, eng, info_between
+        configure_engine(eng, self.nodes, kind, params, matrix)
         if own is not None:
             eng.set_partition(*own)
         eng.seed(seed)
         eng._batch_reported = None
-        eng.events_enable()
+        eng.events_enable(*(capacity or ()))
         eng.set_time(0)
-        self.mdl = oracle_model(O, kind, params, matrix)
-        self.state = O.lib().orc_jrandom_seed(seed)
-        self.sim = O.Sim(n)
-        self.now, self.base, self.delivered = 0, 0, 0
-        self.onair = np.zeros(0, dtype=O.PACKET_DTYPE)
         self.keep = []
-
-    def _packets(self, t_end):
-        rng, n = self.rng, self.n
-        t = int(rng.integers(self.min_per_tick, self.per_tick + 1))
-        src = np.sort(rng.choice(n, t, replace=False)).astype(np.int32)
-        if self.sinr:   # one start, one air time per tick (the frames are named by source indices)
-            return src, self.nodes.packets(src, self.now, 32 * int(rng.choice(self.hex_lengths)))
-        pk = self.nodes.packets(src, 0, 0)
-        pk["start_us"] = self.now if self.aligned else rng.integers(self.now - 50, t_end, t)   # a start before "now" is clamped
-        pk["air_us"] = 32 * rng.choice(self.hex_lengths, t)
-        return src, pk
-
-    def _oracle_tick(self, pk):
-        O = self.O
-        if self.sinr:
-            self.onair = self.onair[self.onair["start_us"] + self.onair["air_us"] > self.now]
-            want = O.tick(self.mdl, self.nodes, np.concatenate([self.onair, pk]), first_new=len(self.onair), rng_state=self.state)
-            self.onair = np.concatenate([self.onair, pk])
-        else:
-            want = O.tick(self.mdl, self.nodes, pk, rng_state=self.state)
-        self.state = want.rng_state
-        imm = self.sim.medium_calls(want, pk, pkt_base=self.base, const_loss=(self.kind == "udgm_const"))
-        self.base += len(pk)
-        return imm
+        self.views = []               # (with capacities) every drain's (packets, destinations, rssi, pending, oldest)
 
     def batch(self, k, what):
         """k ticks through one rm_batch_run_* call, handed over in one rm_events_process_batch call"""
@@ -122,27 +90,40 @@ class Session:
         t0, ends, srcs, pks = self.now, [], [], []
         begins = []
         for b in range(k):
-            t_end = self.now + int(self.rng.choice(self.tick_styles))
-            src, pk = self._packets(t_end)
+            t_end, src, pk = self._next_tick()
             begins.append(self.now)
             ends.append(t_end)
             srcs.append(src)
             pks.append(pk)
             self.now = t_end
         self.now = t0
-        if self.sinr:
+        if self.by_sources:
             arrs = [DeviceArray(s) if len(s) else None for s in srcs]
             eng.batch_run_sources_device(begins, ends, [a.ptr.value if a is not None else 0 for a in arrs], [len(s) for s in srcs],
                                          begins, [int(p["air_us"][0]) if len(p) else 32 for p in pks])
         else:
             arrs = [DeviceArray(to_tx_records(self.rsa, p)) if len(p) else None for p in pks]
             eng.batch_run_device(begins, ends, [a.ptr.value if a is not None else 0 for a in arrs], [len(p) for p in pks])
-        views = eng.events_process_batch(ends)
+        if self.rings is None:
+            rc, views = 0, eng.events_process_batch(ends)
+        else:   # (the raw call, as in drain: every view is filled, and the first reporting drain's code comes back)
+            import ctypes as C
+            raw = (self.rsa._lib.DeliveryView * k)()
+            t = np.ascontiguousarray(ends, dtype=np.int64)
+            rc = eng._L.rm_events_process_batch(eng._h, k, t.ctypes.data, raw)
+            assert rc in (0, ERR_CAPACITY), "%s: return code %d" % (what, rc)
+            eng.oldest_pending_packets = [raw[b].oldest_packet for b in range(k)]
+            views = [eng._delivery_tuple(raw[b], True, False) for b in range(k)]
         assert len(views) == k
+        reported = []
         for b in range(k):
             imm = self._oracle_tick(pks[b])
-            self.delivered += same_drain(views[b], oracle_drain(O, self.sim, ends[b], imm, self.own), "%s batch tick %d" % (what, b))
+            what_b = "%s batch tick %d" % (what, b)
+            self.delivered += same_drain(views[b], oracle_drain(O, self.sim, ends[b], imm, self.own), what_b)
+            reported.append(self._same_rings(None, views[b][3], eng.oldest_pending_packets[b], ends[b], views[b], what_b))
             self.now = ends[b]
+        assert rc == (ERR_CAPACITY if any(reported) else 0), "%s: return code %d, drains that report a dropped tick: %s" % (
+            what, rc, [b for b in range(k) if reported[b]])
         assert eng.events_next_packet() == self.base
         check_nodes(eng, self.sim, self.nodes, what + " after the batch", self.own)
         for a in arrs:
@@ -151,30 +132,59 @@ class Session:
 
     def lone(self, what):
         eng = self.eng
-        t_end = self.now + int(self.rng.choice(self.tick_styles))
-        src, pk = self._packets(t_end)
-        if self.sinr:
+        assert eng.events_next_packet() == self.base
+        t_end, src, pk = self._next_tick()
+        if self.by_sources:
             dev = DeviceArray(src) if len(src) else None
             eng.tick_run_sources_device(self.now, t_end, dev.ptr.value if dev is not None else 0, len(src), self.now,
                                         int(pk["air_us"][0]) if len(pk) else 32)
         else:
             dev = None
             eng.tick(to_tx_records(self.rsa, pk), self.now, t_end)
+        if self.info_between:
+            eng.node_info()
         imm = self._oracle_tick(pk)
+        assert eng.events_next_packet() == self.base
         self.drain(t_end, what, imm)
         if dev is not None:
             dev.free()
 
+    def _same_rings(self, rc, pending, oldest, t, got, what):
+        """(with capacities) the drain's return code, pending_packets and oldest_packet against the host model of the rings;
+        -> does the drain report a dropped tick"""
+        want = self._model_drain(t)
+        if want is None:
+            return False
+        if rc is not None:   # (a batch returns one code for all its drains)
+            assert rc == (ERR_CAPACITY if want[2] else 0), "%s: return code %d, a dropped tick to report: %s" % (what, rc, want[2])
+        assert (pending, oldest) == want[:2], "%s: (pending_packets, oldest_packet) %s, the model of the rings %s" % (
+            what, (pending, oldest), want[:2])
+        self.views.append(tuple(got[:3]) + (pending, oldest))
+        return want[2]
+
     def drain(self, t, what, imm=()):
-        got = self.eng.events_process(t)
+        eng = self.eng
+        if self.rings is None:
+            rc, got = 0, eng.events_process(t)
+        else:   # the ABI fills the view before it returns RM_ERR_CAPACITY (Engine.events_process raises instead): the raw call
+            import ctypes as C
+            v = self.rsa._lib.DeliveryView()
+            rc = eng._L.rm_events_process(eng._h, int(t), C.byref(v))
+            assert rc in (0, ERR_CAPACITY), "%s: return code %d" % (what, rc)
+            eng.oldest_pending_packet = v.oldest_packet
+            got = eng._delivery_tuple(v, True, False)
         self.delivered += same_drain(got, oracle_drain(self.O, self.sim, t, imm, self.own), what)
-        check_nodes(self.eng, self.sim, self.nodes, what, self.own)
+        self._same_rings(rc, got[3], eng.oldest_pending_packet, t, got, what)
+        check_nodes(eng, self.sim, self.nodes, what, self.own)
         self.now = t
 
     def finish(self):
         self.drain(self.now + 10 ** 7, "final drain")
         assert self.sim.pending == 0
         assert self.eng.events_process(self.now + 1)[3] == 0
+        if self.rings is not None:
+            assert self.rings.drain(self.now + 1)[:2] == (0, self.base) and self.eng.oldest_pending_packet == self.base
+        assert self.eng.events_next_packet() == self.base
         self.sim.close()
         self.eng.events_disable()
         return self.delivered

@@ -67,14 +67,15 @@ def row(env, scenarios, proof=None, present=(), absent=(), shape=False, covered_
 # arguments) that must / must not be among its launches (proofs: several such triples).  shape: "launch shape only" (the value changes a grid or a run length).
 VARIANTS = [
     row("", ["udgm_lone", "transmit", "logdist_batch", "big_batch", "sinr_lone", "sinr_batch", "sinr_overlap", "overflow", "gathered",
-             "gathered_spatial", "gathered_overlap", "events"],
+             "gathered_spatial", "gathered_overlap", "events", "events_rings"],
         proofs=[("udgm_lone", ["k_tick_frames"], ["k_filter", "k_exact"]),
                 ("sinr_lone", ["k_tick_frames_scan", "k_sinr_scan"], ["k_filter", "k_frames_cand", "k_tick_frames_sinr"]),
                 ("logdist_batch", ["k_exact_batch", "k_filter_wg_batch"], ["k_tick_frames_batch", "k_near_lists"]),
                 ("big_batch", ["k_near_lists"], []),
                 ("sinr_batch", ["k_sinr_acc_batch"], ["k_sinr_batch"]),
                 ("gathered", ["k_rank_frames"], []),
-                ("transmit", [], ["k_tick_frames"])],
+                ("transmit", [], ["k_tick_frames"]),
+                ("events_rings", ["k_ev_append_select"], [])],
         note="the defaults: every scenario; the baseline the selection proofs of the other rows differ from"),
     # ---- the filter's form
     row("RM_FILTER=wg", ["logdist_batch", "sinr_lone", "gathered"], proof="logdist_batch", present=["k_filter_wg_batch"], absent=["k_filter"]),
@@ -152,10 +153,11 @@ VARIANTS = [
     row("RM_RESORT_AFTER=0", ["sinr_lone"], note="tick 3's move sorts the table again"),
     row("RM_GRAPH=1", ["udgm_lone", "logdist_batch", "sinr_lone"]),
     # ---- the reception stage
-    row("RM_EV_FUSE=0", ["events"]),
-    row("RM_EV_SHARE=0", ["events"]),
-    row("RM_EV_SHARE=1", ["events"]),
-    row("RM_EV_EMIT_LDS=0", ["events"]),
+    # (events_rings: each of the four reads the link pool through its own copy of the wrap arithmetic)
+    row("RM_EV_FUSE=0", ["events", "events_rings"], proof="events_rings", present=["k_ev_select"], absent=["k_ev_append_select"]),
+    row("RM_EV_SHARE=0", ["events", "events_rings"]),
+    row("RM_EV_SHARE=1", ["events", "events_rings"]),
+    row("RM_EV_EMIT_LDS=0", ["events", "events_rings"]),
 ]
 
 # settings the table must hold beyond tools/knob_sweep.sh's K array (the sweep's own are read from the script)
@@ -309,7 +311,7 @@ def check_scenario(O, sc, tag, res, what):
     """the links of one scenario's run (tag: the scenario, or its profiled rerun) against the oracle"""
     sys.path.insert(0, os.path.join(ROOT, "tests", "multi"))
     import variant_worker as W
-    if sc == "events":
+    if sc in ("events", "events_rings"):
         return 0    # (compared against the oracle's event replay in the child: a mismatch is the scenario's error)
     heard = 0
     if sc.startswith("gathered"):
@@ -357,7 +359,7 @@ def _check_row(O, r, res, report):
         heard += check_scenario(O, sc, sc, res, "%s, %s" % (what, sc))
         if sc in [p[0] for p in r["proofs"]]:
             heard += check_scenario(O, sc, sc + ".prof", res, "%s, %s (profiled)" % (what, sc))
-    assert heard > 0 or r["scenarios"] == ["events"], what + ": nothing heard"
+    assert heard > 0 or set(r["scenarios"]) <= {"events", "events_rings"}, what + ": nothing heard"
     for sc, present, absent in r["proofs"]:
         names = {k.split("<")[0].strip() for k in report["kernels"].get(sc, [])}
         for k in present:
