@@ -230,7 +230,8 @@ typedef struct rm_host_result {
 int rm_tick_flush_view(rm_context *ctx, rm_host_result *out);
 
 /* A medium in which a frame is heard by a large share of all nodes -- the reference's default NullRadioMedium (every same-channel
- * node: NullRadioMedium.java:62-73), a lossless N2N matrix, a unit disc over a small field -- is evaluated in node order, and
+ * node: NullRadioMedium.java:62-73), a unit disc over a small field (not the N2N matrix: its ticks take the general path) -- is
+ * evaluated in node order, and
  * what its tick leaves IS its result: per (packet, chunk of 1024 consecutive nodes) cell sixteen 64-bit lane masks -- bit l
  * of mask k set: node rx_first + 1024 * chunk + 64 * k + l heard the packet -- and the cell's count.  A heard link's rssi is
  * its packet's transmit power, its verdict its packet's (pkt_interference): nothing else distinguishes links of such a medium,

@@ -408,8 +408,9 @@ int launch_tick(rm_context *c, TickSlot &ts, const TickPlan &plan, bool em_pass)
         return RM_OK;
     };
     if (!sinr && rm::dense_tick_applies(t, cfg, m, nd, !part_spatial(c))) {
-        // a medium in which a frame is heard by a large share of the nodes (the reference's default Null medium, a lossless
-        // matrix, a range over most of the field): node-order evaluation and ordered compaction, rm_dense.hip
+        // a medium in which a frame is heard by a large share of the nodes (the reference's default Null medium, a range over
+        // most of the field): node-order evaluation and ordered compaction, rm_dense.hip.  (Not the N2N matrix, lossless or
+        // not: maybe_draws is true for every N2N table, and a tick that may draw is refused there.)
         const size_t cells = size_t(rm::dense_tick_cells(nd, t));
         RM_HIP(ts.d_cnt.ensure(std::max<size_t>(cells, 1)));
         RM_HIP(ts.d_off.ensure(std::max<size_t>(cells, 1)));

@@ -1,6 +1,9 @@
 // rm_dense.hip -- the tick of a medium in which a frame is heard by a large share of all nodes: the reference's DEFAULT
-// medium (NullRadioMedium.java:47-77: every same-channel node hears everything), an N2N matrix without loss, a unit-disc
-// range that covers most of the field (part of libradiomedium_hip.so; gfx950 only, -ffp-contract=off, no fast-math)
+// medium (NullRadioMedium.java:47-77: every same-channel node hears everything), a unit-disc range that covers most of
+// the field (part of libradiomedium_hip.so; gfx950 only, -ffp-contract=off, no fast-math)
+// (The N2N matrix has an instance here, k_dense_count<RM_MODEL_N2N>, and NO route to it: maybe_draws (rm_api_context.cpp) answers
+// true for every N2N table, whatever its matrix and probabilities hold, so such a tick is planned with the draw kernels and
+// dense_tick_applies refuses it -- cfg.stochastic -- before it reads the knob.  A matrix of zeros and ones takes the general path.)
 //
 // Everything the other paths are built around -- a conservative cull, a candidate list, ranking a frame's few dozen heard
 // links by node index -- has nothing to do here: there is nothing to cull, and the output IS the node table, frame by
@@ -299,8 +302,9 @@ k_dense_write(const ModelDev m, const TickDev t, const uint32_t *cell_cnt, const
 }
 
 // Is this tick one for the dense form?  No draws, no SINR, the whole node table or an index range of it as receivers, and
-// a medium in which a frame reaches a large share of them: no geometry at all (Null, N2N), or a unit disc that covers
-// at least a sixteenth of the table's bounding square and more nodes than a frame's fixed segment holds.
+// a medium in which a frame reaches a large share of them: no geometry at all (Null), or a unit disc that covers
+// at least a sixteenth of the table's bounding square and more nodes than a frame's fixed segment holds.  (An N2N tick never
+// gets past the first test: it is always planned as one that may draw.  The N2N case below is kept for the day it is not.)
 bool dense_tick_applies(const TickDev &t, const LaunchCfg &cfg, const ModelDev &m, const NodesDev &nd, bool whole_or_range)
 {
     const char *e_knob = getenv("RM_DENSE_TICK"); // 0: never, 1: whenever the configuration allows it (read per tick: tests switch it)

@@ -1,11 +1,11 @@
 """Media in which a frame is heard by a large share of the nodes -- the reference's default NullRadioMedium
 (NullRadioMedium.java:47-77: every same-channel node with its radio on hears every frame), a unit disc that covers the
-field, a lossless N2N matrix: the tick takes the dense form (rm_dense.hip: node-order evaluation, ordered compaction).
+field: the tick takes the dense form (rm_dense.hip: node-order evaluation, ordered compaction).
 Whole ticks against the oracle, and against the culled paths (RM_DENSE_TICK=0) the same ticks took before."""
 import numpy as np
 import pytest
 
-from util import KINDS, DeviceArray, assert_same, configure_engine, oracle_model, to_tx_records
+from util import KINDS, DenseMasks, DeviceArray, assert_same, configure_engine, oracle_model, to_tx_records
 
 pytestmark = pytest.mark.gpu
 
@@ -154,16 +154,11 @@ def test_the_masks_are_the_result_and_the_records_come_on_request(rsa, O, kind, 
         eng.tick_run_sources_device(0, 1000, d.ptr.value, t, 0, 8128)
         heard, dropped = eng.result_count()            # the totals do not wait for the records
         assert heard == cpu.count and not dropped
-        r = eng.result_dense()
-        assert r.n_packets == t and r.chunks == -(-n // 1024) and r.rx_first == 0
-        masks = DeviceArray.read(r.cell_mask, np.uint64, t * r.chunks * 16).reshape(t, r.chunks * 16)
-        counts = DeviceArray.read(r.cell_count, np.uint32, t * r.chunks).reshape(t, r.chunks)
-        off = DeviceArray.read(r.pkt_offset, np.uint32, t + 1)
-        bits = np.unpackbits(masks.view(np.uint8).reshape(t, -1), axis=1, bitorder="little")[:, :n]
-        np.testing.assert_array_equal(bits.sum(axis=1), np.bincount(cpu.pkt, minlength=t))
-        np.testing.assert_array_equal(counts.sum(axis=1), np.bincount(cpu.pkt, minlength=t))
-        np.testing.assert_array_equal(off, np.concatenate([[0], np.cumsum(np.bincount(cpu.pkt, minlength=t))]))
-        q, j = np.nonzero(bits)
+        m = DenseMasks(eng, t, 0, n)                   # (n_packets == t, chunks == ceil(n / 1024), rx_first == 0: checked there)
+        np.testing.assert_array_equal(m.heard.sum(axis=1), np.bincount(cpu.pkt, minlength=t))
+        np.testing.assert_array_equal(m.counts.sum(axis=1), np.bincount(cpu.pkt, minlength=t))
+        np.testing.assert_array_equal(m.pkt_offset, np.concatenate([[0], np.cumsum(np.bincount(cpu.pkt, minlength=t))]))
+        q, j = m.links()
         np.testing.assert_array_equal(q, cpu.pkt)
         np.testing.assert_array_equal(j, cpu.dst)
         lazy = eng.result_copy(t, cap=1 << 22)         # ... and now the records

@@ -117,3 +117,29 @@ class DeviceArray:
         if self.ptr:
             self._hip.hipFree(self.ptr)
             self.ptr = None
+
+
+class DenseMasks:
+    """rm_result_dense of the last tick, decoded on the host: `heard` bool [packet][receiver of the partition], the cells' counts,
+    the packets' offsets, the tick's total and the Tx-failure flags.  `first`, `span`: the receivers' index range (the whole table:
+    0, n).  Holds the result to its documented shape on the way: n_packets, rx_first and chunks = ceil(span / 1024); no bit beyond
+    the range's last node in the last chunk -- which is every bit outside an index partition --; a cell's count is its masks'."""
+
+    def __init__(self, eng, n_packets, first, span):
+        r = eng.result_dense()
+        chunks = -(-span // 1024)
+        assert (r.n_packets, r.chunks, r.rx_first) == (n_packets, chunks, first), (r.n_packets, r.chunks, r.rx_first)
+        masks = DeviceArray.read(r.cell_mask, np.uint64, n_packets * chunks * 16).reshape(n_packets, chunks * 16)
+        self.counts = DeviceArray.read(r.cell_count, np.uint32, n_packets * chunks).reshape(n_packets, chunks)
+        self.pkt_offset = DeviceArray.read(r.pkt_offset, np.uint32, n_packets + 1)
+        self.total = int(DeviceArray.read(r.count, np.uint32, 1)[0])
+        self.pkt_interference = DeviceArray.read(r.pkt_interference, np.uint8, n_packets)
+        bits = np.unpackbits(masks.view(np.uint8).reshape(n_packets, -1), axis=1, bitorder="little")
+        assert not bits[:, span:].any(), "mask bits beyond the receivers' index range"
+        np.testing.assert_array_equal(self.counts, bits.reshape(n_packets, chunks, 1024).sum(axis=2), err_msg="cell counts")
+        self.heard = bits[:, :span].astype(bool)
+
+    def links(self, first=0):
+        """(pkt, dst) of the set bits, packet-major, receivers ascending: the order of the records"""
+        q, j = np.nonzero(self.heard)
+        return q, j + first
