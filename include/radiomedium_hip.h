@@ -1104,6 +1104,114 @@ int rm_routes_from_links(int32_t n_nodes, int32_t n_links, const int32_t *node, 
                          const rm_routes_params *params, double noise_dbm, const int32_t *roots, int32_t n_roots, const rm_routes_out *out,
                          rm_routes_totals *totals);
 
+/* ---- forwarding queues: multi-hop packet relay on the device ------------------------------------------------------------------
+ * (not reference behaviour.)  Per-node packet queues in device memory and the calls that move
+ * packets along a next-hop table from one evaluated tick to the next.  No evaluating call changes: every call here reads a FINISHED
+ * result, as the unicast query does, or only the feature's own tables.  Off by default; then nothing is allocated or launched.
+ * Memory when on: n_nodes * (24 * queue_slots + 164) bytes -- per node a 128-byte row, the packets, 12 bytes of scratch and one
+ * 24-byte record per packet number of an advance or inject list (sized for n_nodes entries at enable; a longer list grows it).  All integers are exact, and no state depends on launch
+ * geometry or on the order in which atomics land.
+ *
+ * State per node j: next[j] (>= 0 a next hop, RM_FWD_NO_ROUTE: every node's value after enable, RM_FWD_SINK), up to queue_slots
+ * packets {origin, hops, birth_us, enq_us}, tries, ready_us (both 0 at first) and the counters of rm_fwd_node.  Queue order is
+ * ascending (enq_us, birth_us, origin, hops); the head is the first packet in it; slot positions are not observable through the
+ * host calls.  j is SENDABLE AT t iff its queue is not empty, ready_us <= t and head.enq_us <= t.  A non-empty queue implies
+ * next[j] >= 0.
+ *
+ * rm_fwd_set_next*: next[j] = parent[j]; an entry outside 0 .. n_nodes - 1 or equal to j becomes -1; then every valid entry of the
+ * roots list becomes RM_FWD_SINK -- the parent array and the root list of a hop or route query go in as they lie in device memory.
+ * Then the queues are settled: at a node whose next is now SINK every queued packet arrives at time_us (latency time_us - birth_us,
+ * hops unchanged); at a node whose next is now -1 every queued packet is dropped as dropped_no_route; tries = 0 at both kinds.
+ *
+ * rm_fwd_inject*: an entry that is negative or outside the table is padding; every other occurrence of node j generates a packet:
+ * next[j] SINK: it arrives at once with 0 hops and latency 0; -1: dropped_no_route; queue full: dropped_full; else
+ * {j, 0, time_us, time_us} is pushed.  Duplicates are packets of their own.  A row of rm_traffic_generate_device with n = cap is a
+ * valid argument.
+ *
+ * rm_fwd_sources*: the nodes sendable at time_us in ascending node index, padded with -1 up to cap; *count is the true number,
+ * and with count > cap the list holds the first cap.  A ready dev_src of rm_tick_run_sources_device, of the gated tick and of a
+ * batch row.  enabled, txprob and channel play no part.
+ *
+ * The device forms are enqueued on the context's stream and not waited for; the scratch is sized at enable for lists of up to
+ * n_nodes entries, and only an inject or candidate list longer than that makes its call wait for the stream once, to grow it.
+ * rm_fwd_enable on a context without nodes is RM_ERR_STATE.
+ * rm_fwd_advance*: enqueued on the context's stream, not waited for.  Reads result slot `slot` of the last evaluating call under the
+ * unicast query's state rules (slot 0 is also the last lone tick).  A slot that overflowed its link capacity or was dropped
+ * (RM_UC_LOST's condition): nothing changes but skipped_slots++.  Otherwise, for packet numbers p = 0 .. P - 1 -- with a candidate
+ * list P = min(n_cand, n_new) and the candidate j is cand[p] (the list handed to the evaluating call: a gated tick keeps packet
+ * numbers in their places); with dev_cand NULL P = n_new and j = recs[p].src -- and t_end = recs[p].start_us + recs[p].air_us:
+ *  1. j outside the table: nothing.  2. j also at a lower p of this slot: stray++.  3. j not sendable at recs[p].start_us, judged on
+ *  the state at the start of the call: stray++.  4. otherwise j PARTICIPATES: attempts[j]++, w = next[j], and the attempt is
+ *  deferred if recs[p].src != j; failed if the unicast status of (slot, p, w) is not RM_UC_DELIVERED; acked if it is and w is a sink
+ *  or w ACCEPTS; failed and rejected[w]++ if it is and w rejects.  5. With A[w] the participants of this call whose frame was
+ *  delivered at w, a relay w accepts iff len_start[w] + A[w] <= queue_slots (len_start: at the start of the call): all of them or
+ *  none; w's own pop in the same call does not make room.  6. acked: j's head (the head at the start of the call) is popped,
+ *  tries = 0, ready_us = t_end, acked[j]++; at a sink the packet's origin o gets arrived[o]++, latency_us_sum[o] += t_end - birth_us,
+ *  latency_us_max[o] raised to it, hops_sum[o] += hops + 1; else if hops + 1 > max_hops it is dropped as dropped_ttl AT w; else
+ *  {origin, hops + 1, birth_us, t_end} is pushed at w and queue_max[w] is raised to len_start[w] + the packets pushed at w in this
+ *  call.  7. failed / deferred: failed[j]++ or deferred[j]++, tries++; if tries > max_retries the head is popped as dropped_retries,
+ *  tries = 0, ready_us = t_end; else ready_us = t_end + r * backoff_unit_us with BE = min(min_be + tries - 1, max_be), r = 0 for
+ *  BE = 0, else h2 >> (64 - BE), h1 = mix64(mix64(mix64(seed + 0x9E3779B97F4A7C15) ^ (uint64_t)(uint32_t)j) ^ (uint64_t)start_us),
+ *  h2 = mix64(h1 ^ (uint64_t)tries) (mix64: the hash of the link draws).
+ * Every drop also does lost[origin]++ and dropped[node where it was dropped]++.  A batch: one advance per slot, ascending.
+ * Identities: generated = arrived + the four dropped_* + in_flight; attempts = acked + failed + deferred per node.
+ *
+ * RM_ERR_STATE, nothing launched: the feature is off; for advance what rm_unicast_query refuses (no evaluated result, a receiver
+ * partition, a gathered / rm_dist_* / rm_group_* form, RM_GRAPH=1); rm_fwd_enable on a context made under RM_GRAPH=1.
+ * RM_ERR_INVALID, nothing launched: bad parameters, NULL arguments, negative counts or times, cap < 1, slot outside the last call's
+ * slots, a host roots / inject entry >= n_nodes.  rm_node_update, rm_nodes_move, rm_set_model and rm_nodes_upload with the same
+ * node count keep everything; rm_nodes_upload with another node count switches the feature off. */
+#define RM_FWD_NO_ROUTE (-1)
+#define RM_FWD_SINK (-2)
+typedef struct rm_fwd_params {
+    int32_t queue_slots;     /* 1, 2, 4, 8 or 16 */
+    int32_t max_retries;     /* 0 .. 15 */
+    int32_t min_be, max_be;  /* 0 <= min_be <= max_be <= 8 */
+    int32_t max_hops;        /* 1 .. 255 */
+    int32_t reserved;        /* 0 */
+    int64_t backoff_unit_us; /* 0 .. 2^32 */
+    uint64_t seed;
+} rm_fwd_params; /* 40 bytes */
+typedef struct rm_fwd_packet { int32_t origin; int32_t hops; int64_t birth_us; int64_t enq_us; } rm_fwd_packet; /* 24 bytes */
+typedef struct rm_fwd_node { /* 128 bytes: the table's row */
+    uint64_t generated, arrived, lost, latency_us_sum, latency_us_max, hops_sum;  /* as origin */
+    uint64_t attempts, acked, failed, deferred, rejected, dropped;               /* as relay */
+    int64_t ready_us;
+    int32_t next, queue_len, queue_max, tries;
+    uint32_t slot_mask;  /* the device table only (rm_fwd_read gives 0): bit s set = slot s of the node's packets is occupied */
+    uint32_t reserved;
+} rm_fwd_node;
+typedef struct rm_fwd_totals {
+    uint64_t generated, arrived, dropped_retries, dropped_no_route, dropped_full, dropped_ttl, in_flight, stray, skipped_slots,
+        latency_us_sum, hops_sum;
+} rm_fwd_totals; /* 88 bytes */
+void rm_fwd_defaults(rm_fwd_params *p); /* 8 slots, 3 retries, BE 3 .. 5, 64 hops, 320 us, seed 0 */
+/* pure host functions, no device: RM_OK or RM_ERR_INVALID; *delay_us = r * backoff_unit_us for tries >= 1, node >= 0, start_us >= 0 */
+int rm_fwd_validate(const rm_fwd_params *p);
+int rm_fwd_backoff(const rm_fwd_params *p, int32_t node, int64_t start_us, int32_t tries, int64_t *delay_us);
+/* enable (again: with new parameters, everything cleared, next -1 everywhere), release, state */
+int rm_fwd_enable(rm_context *ctx, const rm_fwd_params *p);
+int rm_fwd_disable(rm_context *ctx);
+int rm_fwd_enabled(const rm_context *ctx);
+int rm_fwd_get_params(const rm_context *ctx, rm_fwd_params *out); /* the enabled parameters: queue_slots sizes rm_fwd_queue_read's out */
+/* clears counters, totals and queues (tries, ready_us 0); keeps next and the parameters */
+int rm_fwd_reset(rm_context *ctx);
+int rm_fwd_set_next_device(rm_context *ctx, const int32_t *dev_parent /* [n_nodes] */, const int32_t *dev_roots, int32_t n_roots, int64_t time_us);
+int rm_fwd_set_next(rm_context *ctx, const int32_t *parent /* [n_nodes] */, const int32_t *roots, int32_t n_roots, int64_t time_us);
+int rm_fwd_inject_device(rm_context *ctx, const int32_t *dev_src, int32_t n, int64_t time_us);
+int rm_fwd_inject(rm_context *ctx, const int32_t *src, int32_t n, int64_t time_us);
+int rm_fwd_sources_device(rm_context *ctx, int64_t time_us, int32_t cap, int32_t *dev_src /* [cap] */, int32_t *dev_count);
+int rm_fwd_sources(rm_context *ctx, int64_t time_us, int32_t cap, int32_t *src /* [cap] */, int32_t *count); /* synchronises */
+int rm_fwd_advance_device(rm_context *ctx, int32_t slot, const int32_t *dev_cand /* or NULL */, int32_t n_cand);
+int rm_fwd_advance(rm_context *ctx, int32_t slot, const int32_t *cand /* or NULL */, int32_t n_cand); /* uploads the list */
+/* n rows (nodes NULL: all, n = n_nodes) and the totals (may be NULL; out may be NULL with n = 0); synchronises */
+int rm_fwd_read(rm_context *ctx, const int32_t *nodes, int32_t n, rm_fwd_node *out, rm_fwd_totals *totals);
+/* the listed nodes' packets in queue order, queue_slots entries per node (unused ones zeroed), and their number; synchronises */
+int rm_fwd_queue_read(rm_context *ctx, const int32_t *nodes, int32_t n, rm_fwd_packet *out /* [n][queue_slots] */, int32_t *len /* [n] */);
+/* the tables in device memory (valid until disable, another enable or another node count); any pointer may be NULL */
+int rm_fwd_device(rm_context *ctx, const rm_fwd_node **dev_node, const rm_fwd_packet **dev_packets /* [n_nodes][queue_slots] */,
+                  const rm_fwd_totals **dev_totals);
+
 /* ---- several devices behind one caller --------------------------------------------------------------
  * The reference host is ONE process (Main.java:65-73): a group drives n contexts from one host thread, one
  * per device (an ordinal may repeat: several partitions on one GPU).  Receivers are partitioned over the

@@ -106,6 +106,23 @@ class RoutesTotals(C.Structure):
 ROUTES_FIELDS = (("cost", np.uint64), ("parent", np.int32), ("rssi", np.float64), ("link_cost", np.uint32), ("children", np.int32))
 ROUTE_UNREACHED = 0xFFFFFFFFFFFFFFFF
 
+
+class FwdParams(C.Structure):
+    """rm_fwd_params: the forwarding queues' parameters (40 bytes)"""
+    _fields_ = [("queue_slots", C.c_int32), ("max_retries", C.c_int32), ("min_be", C.c_int32), ("max_be", C.c_int32),
+                ("max_hops", C.c_int32), ("reserved", C.c_int32), ("backoff_unit_us", C.c_int64), ("seed", C.c_uint64)]
+
+
+FWD_NO_ROUTE, FWD_SINK = -1, -2
+FWD_NODE_DTYPE = np.dtype([(f, "<u8") for f in ("generated", "arrived", "lost", "latency_us_sum", "latency_us_max", "hops_sum", "attempts",
+                                                "acked", "failed", "deferred", "rejected", "dropped")] +
+                          [("ready_us", "<i8"), ("next", "<i4"), ("queue_len", "<i4"), ("queue_max", "<i4"), ("tries", "<i4"),
+                           ("slot_mask", "<u4"), ("reserved", "<u4")])
+FWD_PACKET_DTYPE = np.dtype([("origin", "<i4"), ("hops", "<i4"), ("birth_us", "<i8"), ("enq_us", "<i8")])
+FWD_TOTALS_DTYPE = np.dtype([(f, "<u8") for f in ("generated", "arrived", "dropped_retries", "dropped_no_route", "dropped_full", "dropped_ttl",
+                                                  "in_flight", "stray", "skipped_slots", "latency_us_sum", "hops_sum")])
+assert C.sizeof(FwdParams) == 40 and FWD_NODE_DTYPE.itemsize == 128 and FWD_PACKET_DTYPE.itemsize == 24 and FWD_TOTALS_DTYPE.itemsize == 88
+
 NODE_STATS_DTYPE = np.dtype([(name, "<u8") for name, _ in NodeStats._fields_])
 assert NODE_STATS_DTYPE.itemsize == C.sizeof(NodeStats) == 64
 
@@ -427,6 +444,25 @@ SIGNATURES = {
     "rm_routes_link_cost": (C.c_int, [C.POINTER(RoutesParams), C.c_double, C.c_double, C.POINTER(C.c_uint32)]),
     "rm_routes_from_links": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RoutesParams), C.c_double, C.c_void_p,
                                        C.c_int32, C.POINTER(RoutesOut), C.POINTER(RoutesTotals)]),
+    "rm_fwd_defaults": (None, [C.POINTER(FwdParams)]),
+    "rm_fwd_validate": (C.c_int, [C.POINTER(FwdParams)]),
+    "rm_fwd_backoff": (C.c_int, [C.POINTER(FwdParams), C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    "rm_fwd_enable": (C.c_int, [C.c_void_p, C.POINTER(FwdParams)]),
+    "rm_fwd_disable": (C.c_int, [C.c_void_p]),
+    "rm_fwd_enabled": (C.c_int, [C.c_void_p]),
+    "rm_fwd_get_params": (C.c_int, [C.c_void_p, C.POINTER(FwdParams)]),
+    "rm_fwd_reset": (C.c_int, [C.c_void_p]),
+    "rm_fwd_set_next_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64]),
+    "rm_fwd_set_next": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64]),
+    "rm_fwd_inject_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64]),
+    "rm_fwd_inject": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64]),
+    "rm_fwd_sources_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rm_fwd_sources": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
+    "rm_fwd_advance_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "rm_fwd_advance": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "rm_fwd_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rm_fwd_queue_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rm_fwd_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "rm_det_math": (C.c_double, [C.c_int32, C.c_double]),
     "rm_link_hash": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
     "rm_evq_init": (None, [C.c_void_p]),

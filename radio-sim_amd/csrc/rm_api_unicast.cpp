@@ -18,6 +18,10 @@ constexpr int64_t kUcMaxEntries = int64_t(1) << 27;
 size_t uc_prefix_off() { return pad64(sizeof(rm::UcSlot) * RM_MAX_BATCH); }
 size_t uc_desc_bytes() { return uc_prefix_off() + pad64(sizeof(uint32_t) * (RM_MAX_BATCH + 1)); }
 
+} // namespace
+
+namespace rmh {
+
 // what every form refuses with RM_ERR_STATE: nothing launched, nothing changed
 int uc_check_state(rm_context *c)
 {
@@ -34,11 +38,19 @@ int uc_check_state(rm_context *c)
     return RM_OK;
 }
 
+} // namespace rmh
+
+namespace {
+
 int uc_check_out(const rm_unicast_out *out)
 {
     if (!out) return fail(RM_ERR_INVALID, "the output table is NULL");
     return RM_OK;
 }
+
+} // namespace
+
+namespace rmh {
 
 // the slot's compact arrays (written now if the tick left them for later), described for the kernel
 int uc_describe(rm_context *c, TickSlot &ts, rm::UcSlot *d)
@@ -92,6 +104,10 @@ int uc_slots(rm_context *c, bool all, const uint32_t *prefix, int n_prefix, rm::
     *dev_slots = reinterpret_cast<const rm::UcSlot *>(u.d_desc.p);
     return RM_OK;
 }
+
+} // namespace rmh
+
+namespace {
 
 // the slots form's checks behind the state: the prefix of n_pkt (n_slots + 1 words) and the number of entries
 int uc_check_slots(rm_context *c, int32_t n_slots, const int32_t *n_pkt, std::vector<uint32_t> &prefix, int64_t *total)

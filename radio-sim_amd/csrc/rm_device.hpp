@@ -860,4 +860,41 @@ RM_D U128 wave_sum_u128(const U128 acc)
     return u128_add(sum, part);
 }
 
+// ---- a finished result slot's answer about (packet p, wanted node w): the unicast query's status (E12) and the link's index.  What
+// rm_unicast.hip writes out per entry and what the forwarding queues' advance (rm_fwd.hip) decides an attempt by
+RM_D bool uc_lost(const UcSlot &s) { return s.out_count[1] != 0u || (s.stage_count && s.stage_count[1] != 0u); }
+
+RM_D int uc_find(const UcSlot &s, int p, int w, int n_nodes, int32_t &link)
+{
+    int status = RM_UC_NONE;
+    link = -1;
+    if (w >= 0 && p >= 0 && p < s.n_new && s.out_count && s.recs) {
+        if (uc_lost(s)) {
+            status = RM_UC_LOST; // the traffic counters' skip condition (rm_stats.hip)
+        } else {
+            const int32_t src = s.recs[p].src;
+            if (src < 0 || src >= n_nodes) {
+                status = RM_UC_NOT_SENT;
+            } else {
+                status = RM_UC_UNHEARD;
+                if (s.pkt_offset && s.dst && s.verdict) {
+                    const uint32_t n = min(s.out_count[0], s.out_count[2]); // (never past the links that were stored)
+                    const uint32_t end = min(s.pkt_offset[p + 1], n);
+                    uint32_t lo = min(s.pkt_offset[p], end), hi = end;
+                    while (lo < hi) { // lower bound of w in dst[lo, hi)
+                        const uint32_t mid = lo + ((hi - lo) >> 1);
+                        if (s.dst[mid] < w) lo = mid + 1;
+                        else hi = mid;
+                    }
+                    if (lo < end && s.dst[lo] == w) {
+                        link = int32_t(lo);
+                        status = s.verdict[lo] == uint8_t(RM_DELIVERED) ? RM_UC_DELIVERED : RM_UC_INTERFERED;
+                    }
+                }
+            }
+        }
+    }
+    return status;
+}
+
 } // namespace rm

@@ -1039,6 +1039,38 @@ hipError_t launch_unicast_slots(hipStream_t s, const UcSlot *dev_slots, const Uc
 hipError_t launch_unicast_at(hipStream_t s, const UcSlot *dev_slots, const UcSlot &lone, int n_slots, int64_t n, int n_nodes,
                              const int32_t *slot, const int32_t *pkt, const int32_t *want, const rm_unicast_out &out);
 
+// (rm_fwd.hip) the forwarding queues.  node / pk / totals are the context's tables; claim
+// ([n_nodes], INT32_MAX at rest), acc and pushed ([n_nodes], 0 at rest) are per-node scratch that every call leaves as it found it;
+// act holds one record per packet number of the running advance or inject (the decisions one launch leaves for the next).
+struct FwdAct {
+    int32_t j, w;      // the candidate (-1: none in the table) and its next hop
+    int32_t state;     // kFwd*
+    int32_t head;      // the slot of j's head at the start of the call
+    int32_t push;      // the slot of w the packet goes to
+    int32_t qmax;      // what queue_max[w] is raised to
+};
+struct FwdDev {
+    rm_fwd_node *node;
+    rm_fwd_packet *pk; // [n_nodes][Q]
+    rm_fwd_totals *totals;
+    int32_t *claim, *acc, *pushed;
+    FwdAct *act;
+    int n_nodes, Q;
+    int max_retries, min_be, max_be, max_hops;
+    int64_t unit_us;
+    uint64_t seed;
+};
+// every row zero with next -1 (keep_next: as it is), the scratch at rest, the totals zero
+hipError_t launch_fwd_init(hipStream_t s, const FwdDev &f, bool keep_next);
+hipError_t launch_fwd_set_next(hipStream_t s, const FwdDev &f, const int32_t *parent, const int32_t *roots, int n_roots, int64_t time_us);
+// act: room for n records
+hipError_t launch_fwd_inject(hipStream_t s, const FwdDev &f, const int32_t *src, int n, int64_t time_us);
+// unit_count: [units] words of scratch, units and chunk from traffic_geometry(n_nodes)
+hipError_t launch_fwd_sources(hipStream_t s, const FwdDev &f, int64_t time_us, int cap, int units, int chunk, int32_t *unit_count, int32_t *out_src,
+                              int32_t *out_count);
+// packet numbers 0 .. P - 1 of the slot described by `slot` (cand: nullptr or [P]); act: room for P records
+hipError_t launch_fwd_advance(hipStream_t s, const FwdDev &f, const UcSlot &slot, const int32_t *cand, int P);
+
 // reception stage (rm_events.hip)
 hipError_t launch_ev_append(hipStream_t s, const EvDev &e, const EvLinkSrc &ls, const rm_tx_record *tx, int n_new, int64_t now,
                             int immediate, const uint32_t *dropped_flag);

@@ -277,6 +277,21 @@ struct rm_context : TickSlot {
         hipEvent_t h_ev[2] = {nullptr, nullptr};
         int gen = 0;
     } uc;
+    // forwarding queues (E19; rm_api_fwd.cpp, rm_fwd.hip): the parameters, the tables by node index (the rows, the packets
+    // [n][queue_slots], the totals), the per-node scratch every call leaves at rest, the per-packet-number records of an advance or
+    // an inject, the source list's unit counts, the host forms' lists in device memory, and the pinned, host-mapped block a list
+    // read is staged through.  Nothing is allocated before rm_fwd_enable.
+    struct Fwd {
+        bool on = false;
+        int32_t n = -1; // the node count the tables were made for; -1: off
+        rm_fwd_params p{};
+        DevBuf<rm_fwd_node> node;
+        DevBuf<rm_fwd_packet> pk;
+        DevBuf<rm_fwd_totals> totals;
+        DevBuf<int32_t> claim, acc, pushed, unit_count, stage;
+        DevBuf<rm::FwdAct> act;
+        PinnedBlock h;
+    } fw;
     double base_rssi = -100.0; // AbstractRadioMedium.java:38
 
     // host mirror of the node table (Simulator.getNodes() snapshot)
@@ -916,6 +931,18 @@ inline void uc_ran(rm_context *c, int slots, bool gathered)
     c->uc.slots = slots;
     c->uc.gathered = gathered;
 }
+// what every form refuses with RM_ERR_STATE: nothing launched, nothing changed
+int uc_check_state(rm_context *c);
+// the slot's compact arrays (written now if the tick left them for later), described for the kernel
+int uc_describe(rm_context *c, TickSlot &ts, rm::UcSlot *d);
+// the descriptors of all slots of the last call for the kernel (rm_api_unicast.cpp says how they travel)
+int uc_slots(rm_context *c, bool all, const uint32_t *prefix, int n_prefix, rm::UcSlot *lone, const rm::UcSlot **dev_slots, const uint32_t **dev_prefix);
+
+// ---- rm_api_fwd.cpp: forwarding queues (E19)
+// rm_nodes_upload: another node count switches the feature off
+int fwd_nodes_changed(rm_context *c);
+// rm_destroy
+void fwd_release(rm_context *c);
 
 // ---- rm_api_comm.cpp
 int comm_all_gather(rm_context *c, const void *mine, void *all, size_t bytes);

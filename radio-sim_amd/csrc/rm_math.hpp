@@ -208,6 +208,30 @@ RM_HD int64_t linkstats_q8(double x)
     return int64_t(floor(x * 256.0 + 0.5));
 }
 
+// the forwarding queues' backoff: what the parameters may hold, and the backoff factor r of a node's
+// `tries`-th failed attempt in a row at a frame that began at start_us -- the text the advance (rm_fwd.hip), rm_fwd_backoff and
+// rm_fwd_validate are built from.  64-bit integers only.
+RM_HD bool fwd_valid(const rm_fwd_params &p)
+{
+    const int q = p.queue_slots;
+    if (!(q == 1 || q == 2 || q == 4 || q == 8 || q == 16)) return false;
+    if (p.max_retries < 0 || p.max_retries > 15) return false;
+    if (p.max_be < 0 || p.max_be > 8 || p.min_be < 0 || p.min_be > p.max_be) return false;
+    if (p.max_hops < 1 || p.max_hops > 255) return false;
+    return p.backoff_unit_us >= 0 && p.backoff_unit_us <= (int64_t(1) << 32) && p.reserved == 0;
+}
+
+RM_HD uint32_t fwd_backoff_factor(const uint64_t seed, const int32_t min_be, const int32_t max_be, const int32_t node, const int64_t start_us,
+                                  const int32_t tries)
+{
+    const int64_t grown = int64_t(min_be) + int64_t(tries) - 1;
+    const int be = int(grown < int64_t(max_be) ? grown : int64_t(max_be));
+    if (be <= 0) return 0u;
+    const uint64_t h1 = mix64(mix64(mix64(seed + 0x9E3779B97F4A7C15ull) ^ uint64_t(uint32_t(node))) ^ uint64_t(start_us));
+    const uint64_t h2 = mix64(h1 ^ uint64_t(tries));
+    return uint32_t(h2 >> (64 - be));
+}
+
 // the traffic schedule: what a record may hold, a packet's due time, and the number of a node's packets
 // due before a time -- the text the generator (rm_traffic.hip), rm_traffic_due and rm_traffic_validate are all built from.
 // 64-bit integers only.

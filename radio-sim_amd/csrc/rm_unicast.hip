@@ -20,38 +20,13 @@ RM_D double uc_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
 // entry e: packet p of the slot described by s (have: there is such a slot), wanted node w
 RM_D void uc_entry(const UcSlot &s, bool have, int p, int w, int n_nodes, uint64_t e, const rm_unicast_out &o)
 {
-    int status = RM_UC_NONE;
     int32_t link = -1, reply = -1;
     double rssi = uc_nan(), sinr = uc_nan();
-    if (have && w >= 0 && p >= 0 && p < s.n_new && s.out_count && s.recs) {
-        if (s.out_count[1] != 0u || (s.stage_count && s.stage_count[1] != 0u)) {
-            status = RM_UC_LOST; // the traffic counters' skip condition (rm_stats.hip)
-        } else {
-            const int32_t src = s.recs[p].src;
-            if (src < 0 || src >= n_nodes) {
-                status = RM_UC_NOT_SENT;
-            } else {
-                status = RM_UC_UNHEARD;
-                if (s.pkt_offset && s.dst && s.verdict) {
-                    const uint32_t n = min(s.out_count[0], s.out_count[2]); // (never past the links that were stored)
-                    const uint32_t end = min(s.pkt_offset[p + 1], n);
-                    uint32_t lo = min(s.pkt_offset[p], end), hi = end;
-                    while (lo < hi) { // lower bound of w in dst[lo, hi)
-                        const uint32_t mid = lo + ((hi - lo) >> 1);
-                        if (s.dst[mid] < w) lo = mid + 1;
-                        else hi = mid;
-                    }
-                    if (lo < end && s.dst[lo] == w) {
-                        link = int32_t(lo);
-                        const bool delivered = s.verdict[lo] == uint8_t(RM_DELIVERED);
-                        status = delivered ? RM_UC_DELIVERED : RM_UC_INTERFERED;
-                        if (delivered) reply = w;
-                        if (s.rssi) rssi = s.rssi[lo];
-                        if (s.sinr) sinr = s.sinr[lo];
-                    }
-                }
-            }
-        }
+    const int status = have ? uc_find(s, p, w, n_nodes, link) : int(RM_UC_NONE); // (the search: rm_device.hpp)
+    if (link >= 0) {
+        if (status == RM_UC_DELIVERED) reply = w;
+        if (s.rssi) rssi = s.rssi[link];
+        if (s.sinr) sinr = s.sinr[link];
     }
     if (o.status) o.status[e] = uint8_t(status);
     if (o.link) o.link[e] = link;

@@ -662,6 +662,119 @@ class Engine:
         check(self._L.rm_linkstats_stage_device(self._h, C.byref(p)))
         return p.value
 
+    # -- forwarding queues: multi-hop packet relay on the device
+    @staticmethod
+    def fwd_params(**kw):
+        """rm_fwd_defaults with the given fields replaced: queue_slots, max_retries, min_be, max_be, max_hops, backoff_unit_us, seed"""
+        p = _lib.FwdParams()
+        _lib.lib().rm_fwd_defaults(C.byref(p))
+        for k, v in kw.items():
+            if k not in dict(_lib.FwdParams._fields_):
+                raise TypeError("rm_fwd_params has no field " + k)
+            setattr(p, k, int(v) & (2 ** 64 - 1) if k == "seed" else int(v))
+        return p
+
+    @staticmethod
+    def fwd_validate(params):
+        """rm_fwd_validate (pure host): the return code of the validation rm_fwd_enable runs (0: accepted)"""
+        return int(_lib.lib().rm_fwd_validate(C.byref(params)))
+
+    @staticmethod
+    def fwd_backoff(params, node, start_us, tries):
+        """rm_fwd_backoff (pure host): the delay in us behind a frame's end after the node's `tries`-th failed attempt in a row"""
+        d = C.c_int64()
+        check(_lib.lib().rm_fwd_backoff(C.byref(params), int(node), int(start_us), int(tries), C.byref(d)))
+        return d.value
+
+    def fwd_enable(self, params=None, **kw):
+        """rm_fwd_enable: the queues made (again: cleared, every next -1) with `params` or fwd_params(**kw)"""
+        p = params if params is not None else self.fwd_params(**kw)
+        check(self._L.rm_fwd_enable(self._h, C.byref(p)))
+
+    def fwd_get_params(self):
+        """rm_fwd_get_params: the enabled parameters"""
+        p = _lib.FwdParams()
+        check(self._L.rm_fwd_get_params(self._h, C.byref(p)))
+        return p
+
+    def fwd_disable(self):
+        check(self._L.rm_fwd_disable(self._h))
+
+    def fwd_enabled(self):
+        return bool(self._L.rm_fwd_enabled(self._h))
+
+    def fwd_reset(self):
+        """rm_fwd_reset: counters, totals and queues cleared; next and the parameters kept"""
+        check(self._L.rm_fwd_reset(self._h))
+
+    def fwd_set_next(self, parent, roots, time_us):
+        """rm_fwd_set_next: next = parent (int32[n_nodes]; outside the table or itself: no route), the roots sinks; queues settled"""
+        par = np.ascontiguousarray(parent, dtype=np.int32).reshape(-1)
+        if par.shape[0] != max(int(self._L.rm_node_count(self._h)), 0):
+            raise ValueError("one parent per node")
+        idx = np.ascontiguousarray(roots, dtype=np.int32).reshape(-1)
+        check(self._L.rm_fwd_set_next(self._h, par.ctypes.data, _ptr(idx) if idx.shape[0] else None, idx.shape[0], int(time_us)))
+
+    def fwd_set_next_device(self, dev_parent_ptr, dev_roots_ptr, n_roots, time_us):
+        """The raw form: a hop or route query's parent array and root list as they lie in device memory; not waited for"""
+        check(self._L.rm_fwd_set_next_device(self._h, dev_parent_ptr, dev_roots_ptr, int(n_roots), int(time_us)))
+
+    def fwd_inject(self, src, time_us):
+        """rm_fwd_inject: one new packet per entry at its node (negative: padding)"""
+        idx = np.ascontiguousarray(src, dtype=np.int32).reshape(-1)
+        check(self._L.rm_fwd_inject(self._h, _ptr(idx) if idx.shape[0] else None, idx.shape[0], int(time_us)))
+
+    def fwd_inject_device(self, dev_src_ptr, n, time_us):
+        check(self._L.rm_fwd_inject_device(self._h, dev_src_ptr, int(n), int(time_us)))
+
+    def fwd_sources(self, time_us, cap):
+        """rm_fwd_sources: -> (int32[cap], the nodes sendable at time_us ascending, padded with -1; their true number)"""
+        out = np.empty(max(int(cap), 0), dtype=np.int32)
+        count = C.c_int32()
+        check(self._L.rm_fwd_sources(self._h, int(time_us), int(cap), out.ctypes.data if out.shape[0] else None, C.byref(count)))
+        return out, count.value
+
+    def fwd_sources_device(self, time_us, cap, dev_src_ptr, dev_count_ptr):
+        """The raw form: int32[cap] and one int32 in device memory, a ready source list of the device ticks; not waited for"""
+        check(self._L.rm_fwd_sources_device(self._h, int(time_us), int(cap), dev_src_ptr, dev_count_ptr))
+
+    def fwd_advance(self, slot=0, cand=None):
+        """rm_fwd_advance: result slot `slot` of the last evaluating call moves the queues; cand: the candidate list handed to that
+        call (a gated tick), None: the frames' own sources"""
+        if cand is None:
+            check(self._L.rm_fwd_advance(self._h, int(slot), None, 0))
+            return
+        idx = np.ascontiguousarray(cand, dtype=np.int32).reshape(-1)
+        keep = idx if idx.shape[0] else np.zeros(1, dtype=np.int32)
+        check(self._L.rm_fwd_advance(self._h, int(slot), keep.ctypes.data, idx.shape[0]))
+
+    def fwd_advance_device(self, slot, dev_cand_ptr, n_cand):
+        check(self._L.rm_fwd_advance_device(self._h, int(slot), dev_cand_ptr, int(n_cand)))
+
+    def fwd_read(self, nodes=None):
+        """rm_fwd_read: (structured array of FWD_NODE_DTYPE -- the listed nodes in list order, or all --, the totals as a dict)"""
+        ptr, n, _idx = self._node_list(nodes)
+        out = np.zeros(n, dtype=_lib.FWD_NODE_DTYPE)
+        tot = np.zeros(1, dtype=_lib.FWD_TOTALS_DTYPE)
+        check(self._L.rm_fwd_read(self._h, ptr, n, out.ctypes.data if n else None, tot.ctypes.data))
+        return out, {k: int(tot[k][0]) for k in tot.dtype.names}
+
+    def fwd_queue_read(self, nodes=None):
+        """rm_fwd_queue_read: (FWD_PACKET_DTYPE[n][queue_slots] in queue order, int32[n] the queues' lengths); queue_slots is
+        the enabled parameters' (rm_fwd_get_params)"""
+        q = int(self.fwd_get_params().queue_slots)
+        ptr, n, _idx = self._node_list(nodes)
+        out = np.zeros((n, q), dtype=_lib.FWD_PACKET_DTYPE)
+        ln = np.zeros(n, dtype=np.int32)
+        check(self._L.rm_fwd_queue_read(self._h, ptr, n, out.ctypes.data if n else None, ln.ctypes.data if n else None))
+        return out, ln
+
+    def fwd_device(self):
+        """rm_fwd_device: device pointers (rows [n_nodes] of 128 bytes, packets [n_nodes][queue_slots] of 24 bytes, totals)"""
+        a, b, t = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(self._L.rm_fwd_device(self._h, C.byref(a), C.byref(b), C.byref(t)))
+        return a.value, b.value, t.value
+
     # -- java.util.Random
     def seed(self, seed):
         check(self._L.rm_seed(self._h, seed))

@@ -745,6 +745,114 @@ public:
         }
         return out;
     }
+    // Forwarding queues (extension E19): per-node packet queues and a next-hop table on the device; packets move one hop per
+    // evaluated tick.  setForwarding(&params) makes the queues (nullptr: releases them); setNextHops gives every node its next hop
+    // (parents[i] for node i of Simulator.getNodes(), nullptr: no route) and makes the listed nodes sinks; forwardInject puts one
+    // new packet at every listed node; forwardSources gives the nodes with a packet to send at `time` in node order (at most cap;
+    // *count: their true number); forwardAdvance reads the LAST evaluated tick -- the tick mode's flush -- and moves the queues:
+    // without candidates every frame's own source made the attempt, with them candidates[k] is packet k's.  The state is the
+    // device's: it survives apply(), and a node table of another size switches the feature off (setForwarding again starts from
+    // nothing).  false (or an empty list) and lastError on a refusal.
+    static rm_fwd_params forwardingDefaults()
+    {
+        rm_fwd_params p;
+        rm_fwd_defaults(&p);
+        return p;
+    }
+    bool setForwarding(const rm_fwd_params *params)
+    {
+        lastError.clear();
+        if (params && !syncNodes()) return false; // the device mirrors the node table first: the tables have its size
+        if ((params ? rm_fwd_enable(ctx_, params) : rm_fwd_disable(ctx_)) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        return true;
+    }
+    bool getForwarding() const { return rm_fwd_enabled(ctx_) != 0; }
+    bool setNextHops(const std::vector<const Node *> &parents, const std::vector<const Node *> &sinks, int64_t time)
+    {
+        lastError.clear();
+        if (!simulator || !syncNodes()) return false;
+        if (parents.size() != simulator->getNodes().size()) {
+            lastError = "setNextHops: one parent (or nullptr) per node";
+            return false;
+        }
+        std::vector<int32_t> par, roots;
+        for (const Node *nd : parents) par.push_back(nd ? nd->index : -1);
+        for (const Node *nd : sinks) roots.push_back(nd ? nd->index : -1);
+        par.push_back(-1); // (never an empty array)
+        if (rm_fwd_set_next(ctx_, par.data(), roots.empty() ? nullptr : roots.data(), int32_t(roots.size()), time) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        return true;
+    }
+    bool forwardInject(const std::vector<const Node *> &sources, int64_t time)
+    {
+        lastError.clear();
+        if (!syncNodes()) return false;
+        std::vector<int32_t> src;
+        for (const Node *nd : sources) src.push_back(nd ? nd->index : -1);
+        if (rm_fwd_inject(ctx_, src.empty() ? nullptr : src.data(), int32_t(src.size()), time) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        return true;
+    }
+    std::vector<Node *> forwardSources(int64_t time, int32_t cap, int32_t *count = nullptr)
+    {
+        lastError.clear();
+        std::vector<Node *> out;
+        if (count) *count = 0;
+        if (!simulator || !syncNodes()) return out;
+        std::vector<int32_t> src(size_t(cap > 0 ? cap : 0) + 1);
+        int32_t n = 0;
+        if (rm_fwd_sources(ctx_, time, cap, src.data(), &n) != RM_OK) {
+            lastError = rm_last_error();
+            return out;
+        }
+        const std::vector<Node *> &nodes = simulator->getNodes();
+        for (int32_t k = 0; k < std::min(n, cap); ++k) out.push_back(nodes[size_t(src[size_t(k)])]);
+        if (count) *count = n;
+        return out;
+    }
+    bool forwardAdvance(const std::vector<const Node *> *candidates = nullptr)
+    {
+        lastError.clear();
+        std::vector<int32_t> cand;
+        if (candidates)
+            for (const Node *nd : *candidates) cand.push_back(nd ? nd->index : -1);
+        cand.push_back(-1); // (never an empty array; not counted)
+        if (rm_fwd_advance(ctx_, 0, candidates ? cand.data() : nullptr, candidates ? int32_t(candidates->size()) : 0) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        return true;
+    }
+    // the node's row; totals (may be nullptr); queue (may be nullptr): its packets in queue order
+    bool getForwardStatistics(const Node &node, rm_fwd_node *out, rm_fwd_totals *totals = nullptr, std::vector<rm_fwd_packet> *queue = nullptr)
+    {
+        lastError.clear();
+        const int32_t i = node.index;
+        rm_fwd_params p;
+        if (!out || !syncNodes()) return false;
+        if (rm_fwd_get_params(ctx_, &p) != RM_OK || rm_fwd_read(ctx_, &i, 1, out, totals) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        if (queue) {
+            int32_t len = 0;
+            queue->assign(size_t(p.queue_slots), rm_fwd_packet{});
+            if (rm_fwd_queue_read(ctx_, &i, 1, queue->data(), &len) != RM_OK) {
+                lastError = rm_last_error();
+                queue->clear();
+                return false;
+            }
+            queue->resize(size_t(len));
+        }
+        return true;
+    }
     // Did a frame reach the node it was addressed to (extension E12)?  One entry per packet of the LAST evaluated tick -- the tick
     // mode's flush, or transmitIfClear() -- in packet order: destinations[k] is packet k's intended receiver (nullptr: not asked).
     // status is RM_UC_*; link the index of the heard link in the tick's result (-1 without one); rssi and sinr as the result has
