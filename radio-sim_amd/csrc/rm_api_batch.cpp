@@ -43,22 +43,145 @@ bool rank_frames_wanted(rm_context *c)
     return part_count(c) != c->n && part_count(c) > 0;
 }
 
+NcRegistry<NcPoolMem> &nc_registry()
+{
+    static NcRegistry<NcPoolMem> r;
+    return r;
+}
+
 void nbr_cache_report(rm_context *c)
 {
     if (!g_clock.on || !c->nc.ctr.p) return;
-    unsigned long long v[3] = {0, 0, 0};
+    unsigned long long v[3] = {0, 0, 0}, pool_used = 0;
     if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(v, c->nc.ctr.p, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return;
+    int refs = 0;
+    uint32_t pool_epoch = 0;
+    uint64_t pool_epochs = 0;
+    size_t pool_len = 0;
+    if (c->nc.pool) {
+        nc_registry().look(c->nc.pool, &refs, &pool_epoch, &pool_epochs);
+        pool_len = c->nc.pool->mem.arena_len;
+        if (hipMemcpy(&pool_used, c->nc.pool->mem.bump.p, sizeof(pool_used), hipMemcpyDeviceToHost) != hipSuccess) return;
+    }
     std::fprintf(stderr, "rm source cache (launch sequences: %llu heard form, %llu candidates form; the last one: %s): %llu frames served from a list, "
-                         "%llu swept (%.1f %% hits); %llu arena entries of %zu handed out in the last epoch (%u epochs)\n",
+                         "%llu swept (%.1f %% hits); candidates form: %llu arena entries of %zu handed out in the last epoch (%u epochs); "
+                         "heard form: pool %p, %llu arena entries of %zu handed out in its epoch %u (%llu epochs), %d contexts attached\n",
                  c->nc.batches[1], c->nc.batches[0], c->nc.form == 1 ? "heard" : "candidates",
-                 v[1], v[2], (v[1] + v[2]) ? 100.0 * double(v[1]) / double(v[1] + v[2]) : 0.0, v[0], c->nc.arena.n, c->nc.epoch);
+                 v[1], v[2], (v[1] + v[2]) ? 100.0 * double(v[1]) / double(v[1] + v[2]) : 0.0, v[0], c->nc.arena.n, c->nc.arena.n ? c->nc.epoch : 0u,
+                 (void *)c->nc.pool, pool_used, pool_len, pool_epoch, (unsigned long long)pool_epochs, refs);
+}
+
+// ---- the pool of heard lists a context is attached to (rm_ncpool.hpp holds the rules; here is what they cost on the device)
+static void nc_pool_free(NcPool<NcPoolMem> *p)
+{
+    NcPoolMem &m = p->mem;
+    m.entry.release(); m.bump.release(); m.arena.release(); m.arena_rssi.release(); m.arena_verdict.release();
+    if (m.reset_ev) (void)hipEventDestroy(m.reset_ev);
+    delete p;
+}
+
+static uint64_t key_bits(double v)
+{
+    uint64_t b;
+    std::memcpy(&b, &v, sizeof(b));
+    return b;
+}
+
+// everything a finished heard record depends on (NcPoolKey): the device, the table -- digest and the host's columns --, the medium
+static NcPoolKey nc_pool_key(const rm_context *c)
+{
+    NcPoolKey k;
+    k.device = c->device;
+    k.n = c->n;
+    k.digest = c->table_digest;
+    const rm_model_params &p = c->params;
+    k.medium = {uint64_t(uint32_t(p.kind)), uint64_t(uint32_t(p.flags)), key_bits(p.udgm_success_ratio_tx), key_bits(p.udgm_success_ratio_rx),
+                key_bits(p.udgm_transmission_range), key_bits(p.udgm_interference_range), key_bits(p.const_range), key_bits(p.ld_pl0_db),
+                key_bits(p.ld_exponent), key_bits(p.ld_d0), key_bits(p.ld_sigma_db), key_bits(p.ld_clip), p.ld_seed, key_bits(p.ld_sensitivity_dbm),
+                key_bits(p.ld_noise_dbm), key_bits(p.ld_capture_db), key_bits(p.ld_ifloor_dbm)};
+    const size_t n = size_t(std::max(c->n, 0));
+    k.table.resize(n * (6 * sizeof(double) + 2 * sizeof(int32_t) + 1));
+    unsigned char *w = k.table.data();
+    auto put = [&](const void *col, size_t bytes) {
+        if (bytes) std::memcpy(w, col, bytes);
+        w += bytes;
+    };
+    for (const std::vector<double> *col : {&c->x, &c->y, &c->z, &c->txpower, &c->txprob, &c->rxprob}) put(col->data(), n * sizeof(double));
+    put(c->channel.data(), n * sizeof(int32_t));
+    put(c->int_id.data(), n * sizeof(int32_t));
+    put(c->enabled.data(), n);
+    return k;
+}
+
+void nbr_cache_detach(rm_context *c)
+{
+    NcPool<NcPoolMem> *p = c->nc.pool;
+    c->nc.pool = nullptr;
+    if (p && nc_registry().detach(p)) nc_pool_free(p);
+}
+
+// The context's pool for a heard-form batch: the one it is attached to, as long as nothing a record depends on has changed
+// since; else, by the registry's rules, the same pool in a new epoch (the context is alone in it) or another pool.  Resets go
+// to the context's stream with the pool's event behind them, under the registry's mutex: a context that joins waits for it.
+static int nc_pool_for(rm_context *c, size_t nodes, size_t arena)
+{
+    rm_context::NbrCache &nc = c->nc;
+    if (nc.pool && nc.pool_seen == nc.change) return RM_OK;
+    hipStream_t s = c->stream;
+    if (nc.pool && (nc.pool->key.n != c->n || nc.pool->mem.arena_len != arena)) { // (a table of another size: the pool's memory does not fit it)
+        RM_HIP(hipStreamSynchronize(s));
+        nbr_cache_detach(c);
+    }
+    hipError_t err = hipSuccess;
+    auto epoch = [&](NcPool<NcPoolMem> &p, bool zero) {
+        NcPoolMem &m = p.mem;
+        if (zero && err == hipSuccess) err = hipMemsetAsync(m.entry.p, 0, m.entry.n * sizeof(unsigned long long), s);
+        if (err == hipSuccess) err = hipMemsetAsync(m.bump.p, 0, sizeof(unsigned long long), s);
+        if (err == hipSuccess) err = hipEventRecord(m.reset_ev, s);
+    };
+    NcPoolKey key = nc_pool_key(c);
+    if (nc.pool) {
+        const auto what = nc_registry().changed(nc.pool, key, epoch);
+        RM_HIP(err);
+        if (what != NcRegistry<NcPoolMem>::kLeft) {
+            nc.pool_seen = nc.change;
+            return RM_OK;
+        }
+        // left a pool others go on with: this stream's launch sequences still read and fill it, and the last of the others frees it
+        nc.pool = nullptr;
+        RM_HIP(hipStreamSynchronize(s));
+    }
+    auto make = [&](NcPool<NcPoolMem> &p) {
+        NcPoolMem &m = p.mem;
+        err = m.entry.ensure(nodes);
+        if (err == hipSuccess) err = m.bump.ensure(1);
+        if (err == hipSuccess) err = m.arena.ensure(arena);
+        if (err == hipSuccess) err = m.arena_rssi.ensure(arena);
+        if (err == hipSuccess) err = m.arena_verdict.ensure(arena);
+        if (err == hipSuccess) err = hipEventCreateWithFlags(&m.reset_ev, hipEventDisableTiming);
+        m.arena_len = arena;
+        if (err == hipSuccess) return true;
+        m.entry.release(); m.bump.release(); m.arena.release(); m.arena_rssi.release(); m.arena_verdict.release();
+        if (m.reset_ev) (void)hipEventDestroy(m.reset_ev);
+        m.reset_ev = nullptr;
+        return false;
+    };
+    bool joined = false;
+    NcPool<NcPoolMem> *p = nc_registry().attach(std::move(key), make, epoch, &joined);
+    RM_HIP(err);
+    if (!p) return fail(RM_ERR_HIP, "the pool of heard lists could not be made");
+    nc.pool = p;
+    nc.pool_seen = nc.change;
+    if (joined) RM_HIP(hipStreamWaitEvent(s, p->mem.reset_ev, 0));
+    return RM_OK;
 }
 
 // The source candidate cache (rm::NbrCacheDev) for the batch in `ticks`, or nothing.  It serves batches whose frames are named
 // by source indices (records built from the node table) over the WHOLE sorted table of a geometric medium without the SINR
 // extension; partitions, gathered batches, caller-supplied records and everything that is not the plain four-stage sequence keep
 // the sweep as it is.
-// The form (rm::NbrCacheDev): heard -- finished records per source -- where no draw can happen in the batch, candidates otherwise.
+// The form (rm::NbrCacheDev): heard -- finished records per source, in a pool shared with the device's other contexts on an equal
+// table and medium -- where no draw can happen in the batch, candidates -- private to the context -- otherwise.
 static int plan_nbr_cache(rm_context *c, rm::TickDev *ticks, const TickPlan *plans, int n)
 {
     const rm::LaunchCfg &cfg = plans[0].cfg;
@@ -74,14 +197,11 @@ static int plan_nbr_cache(rm_context *c, rm::TickDev *ticks, const TickPlan *pla
     rm_context::NbrCache &nc = c->nc;
     hipStream_t s = c->stream;
     const size_t nodes = size_t(c->n);
-    // the arena: 96 entries per node (the bench shape keeps some 50 per source), half a gigabyte at most
-    const size_t arena = std::min<size_t>(nodes * 96, size_t(1) << 27);
+    // the arena: 96 entries per node (the bench shape keeps some 50 per source), 2^27 at most (the entry's offset field)
+    const size_t arena = std::min<size_t>(nodes * 96, size_t(rm::kNcArenaMax));
     const int form = cfg.stochastic ? 0 : 1;
     if (nc.nodes != c->n || !nc.state.p) {
         RM_HIP(nc.state.ensure(nodes));
-        RM_HIP(nc.off.ensure(nodes));
-        RM_HIP(nc.len.ensure(nodes));
-        RM_HIP(nc.arena.ensure(arena));
         if (!nc.ctr.p) {
             RM_HIP(nc.ctr.ensure(3));
             RM_HIP(hipMemsetAsync(nc.ctr.p, 0, 3 * sizeof(unsigned long long), s));
@@ -90,20 +210,23 @@ static int plan_nbr_cache(rm_context *c, rm::TickDev *ticks, const TickPlan *pla
         nc.epoch = 0x7FFFFFFFu; // (the state words are zeroed below)
         nc.seen = 0;
     }
-    if (form == 1) { // 13 bytes per entry instead of 4
-        RM_HIP(nc.arena_rssi.ensure(arena));
-        RM_HIP(nc.arena_verdict.ensure(arena));
-    }
-    if (nc.seen != nc.change || nc.form != form) { // a new epoch: every list is stale (another form reads the arena differently)
-        nc.seen = nc.change;
-        nc.form = form;
-        if (nc.epoch >= 0x7FFFFFFEu) {
-            RM_HIP(hipMemsetAsync(nc.state.p, 0, nc.state.n * sizeof(uint32_t), s));
-            nc.epoch = 0;
+    if (form == 1) {
+        RM_TRY(nc_pool_for(c, nodes, arena));
+    } else {
+        RM_HIP(nc.off.ensure(nodes));
+        RM_HIP(nc.len.ensure(nodes));
+        RM_HIP(nc.arena.ensure(arena));
+        if (nc.seen != nc.change || nc.form != 0) { // a new epoch of the private lists: every one is stale (a heard batch in between: as before there was a pool)
+            nc.seen = nc.change;
+            if (nc.epoch >= 0x7FFFFFFEu) {
+                RM_HIP(hipMemsetAsync(nc.state.p, 0, nc.state.n * sizeof(uint32_t), s));
+                nc.epoch = 0;
+            }
+            nc.epoch++;
+            RM_HIP(hipMemsetAsync(nc.ctr.p, 0, sizeof(unsigned long long), s));
         }
-        nc.epoch++;
-        RM_HIP(hipMemsetAsync(nc.ctr.p, 0, sizeof(unsigned long long), s));
     }
+    nc.form = form;
     const size_t per = size_t(std::max(max_cnt, 1));
     RM_HIP(nc.tick_cnt.ensure(size_t(n) * 4));
     RM_HIP(nc.hit.ensure(size_t(n) * per));
@@ -112,17 +235,23 @@ static int plan_nbr_cache(rm_context *c, rm::TickDev *ticks, const TickPlan *pla
     RM_HIP(nc.cur.ensure(size_t(n) * per));
     // (tick_cnt: zeroed by the descriptor kernels, k_store_ticks / k_fetch_ticks)
     nc.batches[form]++;
+    const NcPoolMem *pm = form == 1 ? &nc.pool->mem : nullptr;
     for (int b = 0; b < n; ++b) {
         rm::NbrCacheDev &d = ticks[b].nc;
         d.state = nc.state.p;
-        d.off = nc.off.p;
-        d.len = nc.len.p;
-        d.arena = nc.arena.p;
-        d.arena_rssi = form == 1 ? nc.arena_rssi.p : nullptr;
-        d.arena_verdict = form == 1 ? nc.arena_verdict.p : nullptr;
+        if (pm) {
+            d.entry = pm->entry.p;
+            d.bump = pm->bump.p;
+        } else {
+            d.off = nc.off.p;
+            d.len = nc.len.p;
+        }
+        d.arena = pm ? pm->arena.p : nc.arena.p;
+        d.arena_rssi = pm ? pm->arena_rssi.p : nullptr;
+        d.arena_verdict = pm ? pm->arena_verdict.p : nullptr;
         d.ctr = nc.ctr.p;
-        d.arena_len = uint32_t(arena);
-        d.word = (nc.epoch << 1) | 1u;
+        d.arena_len = uint32_t(pm ? pm->arena_len : arena);
+        d.word = pm ? ((nc.pool->epoch << 1) | 1u) : ((nc.epoch << 1) | 1u);
         d.tick_cnt = nc.tick_cnt.p + size_t(b) * 4;
         d.hit = nc.hit.p + size_t(b) * per;
         d.fill = nc.fill.p + size_t(b) * per;

@@ -307,8 +307,9 @@ void rm_destroy(rm_context *c)
     c->d_bbox_z.release(); c->d_wg_box_xy.release(); c->d_wg_box_z.release(); c->d_grp_chmask.release(); c->d_wg_chmask.release();
     c->d_n2n.release(); c->d_shadow_tbl.release(); c->d_air.release(); c->d_air_alt.release(); c->d_cull_ring.release(); c->d_rng.release(); c->d_ticks.release(); c->d_near_list.release(); c->d_near_cnt.release();
     nbr_cache_report(c);
+    nbr_cache_detach(c);
     c->nc.state.release(); c->nc.off.release(); c->nc.len.release(); c->nc.tick_cnt.release(); c->nc.cur.release(); c->nc.arena.release();
-    c->nc.fill.release(); c->nc.unserved.release(); c->nc.hit.release(); c->nc.ctr.release(); c->nc.arena_rssi.release(); c->nc.arena_verdict.release();
+    c->nc.fill.release(); c->nc.unserved.release(); c->nc.hit.release(); c->nc.ctr.release();
     c->air.pool.release(); c->air.head.release(); c->air.tail.release(); c->air.mark.release(); c->air.bad.release();
     {
         rm_context::Overlap &o = c->ov;

@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "../../include/radiomedium_hip.h"
+#include "rm_ncpool.hpp"
 
 namespace rm {
 
@@ -376,9 +377,12 @@ struct OvDev {
 // SOURCE NODE only, so a context keeps a list per source from one launch sequence to the next: the pre-pass (k_tick_prep_batch)
 // takes a frame whose source has a valid list out of the sweep and notes the list's place in hit[]; the frames that were swept
 // claim and fill lists for their sources (k_nc_claim_batch, k_nc_fill_batch).
-// A list is valid in one EPOCH of the context: the host moves on to a new epoch whenever the receiver table or the
-// pre-filter is rebuilt (any change of a node, the medium, the partition or the engine order).
-// What a list holds is the cache's FORM, chosen per launch sequence by the host (a change of form begins a new epoch):
+// A list is valid in one EPOCH: the host moves on to a new epoch whenever the receiver table or the pre-filter is rebuilt (any
+// change of a node, the medium, the partition or the engine order).  The candidates form's epochs are the context's own.  The
+// heard form's lists lie in a POOL that every context of the device with an equal table and medium is attached to
+// (rm_ncpool.hpp): its epochs are the pool's, and a pool begins one only while a single context is attached.
+// What a list holds is the cache's FORM, chosen per launch sequence by the host (a candidates batch behind a heard one begins a new epoch
+// of the private lists; the pool's lists outlive a candidates batch as long as nothing they depend on has changed):
 //  candidates: a list holds the engine positions that passed the sweep; the exact and reorder stages evaluate and rank them as
 //      if the sweep had appended them.  Links that draw need this form: their verdicts are pending, their records carry a_prob.
 //  heard (arena_rssi != nullptr): where no draw can happen, a frame's FINISHED records -- receiver node index, rssi, verdict, in
@@ -386,14 +390,31 @@ struct OvDev {
 //      start_us nor air_us enters).  A list holds those records in three parallel columns; a hit frame skips the exact stage and
 //      the ranking altogether: k_nc_expand_batch puts its list's length into cursor[], k_reorder_served_batch copies the columns
 //      to the frame's place in the ordered records, and the lists are filled from the ordered records behind the reorder stage.
+//      A node's state word and its list's place are ONE 64-bit entry (rm::nc_entry_pack), because another context's pre-pass
+//      may read it at any time from another stream.  Only kernel boundaries order anything: the claim (compare-and-swap to
+//      "claimed in this epoch, not valid") keeps everybody else off the source, the fill writes the records, and
+//      k_nc_publish_batch, a launch of its own behind the fill, stores the valid entry.  Whoever reads a valid entry reads
+//      the records in a LATER kernel of its own stream (k_reorder_served_batch), which begins with an acquire.
 constexpr uint32_t kNcListCap = 1024; // entries per list at most: a source with more stays uncached
+static_assert(kNcListCap < (1u << kNcLenBits), "a list's length fits its entry");
+constexpr int32_t kNcFillEmpty = -2;  // NbrCacheDev::fill of a claimed list that has no entries (heard form: published, never filled)
 struct NbrCacheDev {
     uint32_t *state;           // [n] per node: (epoch << 1) | 1 the list is valid in `epoch`; (epoch << 1) claimed in `epoch`, no list
-    uint32_t *off, *len;       // [n] the node's list in the arena
+                               // (candidates form; nullptr: no cache at all, in either form)
+    // (the descriptor stays its size -- five of them are one kernel's arguments, k_store_ticks --: each form's words share their place)
+    union {
+        uint32_t *off;             // [n] candidates form: the node's list in the arena ...
+        unsigned long long *entry; // [n] heard form: the pool's entry per node -- state word, offset and length in one (rm_ncpool.hpp)
+    };
+    union {
+        uint32_t *len;             // [n] ... and its length
+        unsigned long long *bump;  // [1] heard form: the pool's arena entries handed out in its epoch (candidates form: ctr[0])
+    };
     int32_t *arena;            // engine positions (candidates) / receiver node indices (heard), handed out by a bump allocator
     double *arena_rssi;        // heard form: the records' rssi ... (nullptr: the candidates form)
     uint8_t *arena_verdict;    // ... and verdict, by the same index
-    unsigned long long *ctr;   // [0] arena entries handed out, [1] frames served from a list, [2] frames swept (since the context was made)
+    unsigned long long *ctr;   // the context's: [0] candidates form: arena entries handed out in the epoch, [1] frames served from a list,
+                               // [2] frames swept (since the context was made)
     uint32_t arena_len;
     uint32_t word;             // (epoch << 1) | 1 of the running launch sequence
     // per tick of the running launch sequence
@@ -403,7 +424,7 @@ struct NbrCacheDev {
     int32_t *unserved;         // [n_cnt] heard form: the n_un frames without a hit, in whatever order the pre-pass's waves arrived.
                                // A tick without any hit ([2] == 0) has no list: its consumers take position k for frame k.
     int32_t *fill;             // [n_cnt] offset of the list a frame's candidates / records are copied to, -1: none.  Candidates form:
-                               // by frame; heard form: by position in unserved[]
+                               // by frame; heard form: by position in unserved[], and kNcFillEmpty: a list without entries was accepted
     uint32_t *cur;             // [n_cnt] per frame: candidates copied so far (candidates form)
 };
 

@@ -327,7 +327,17 @@ RM_D void tick_prep_body(const NodesDev &nd, const ModelDev &m, const TickDev &t
     tx_prefilter(m, tx, f, thr64);
     if (t.nc.state != nullptr) { // (block-uniform) the source candidate cache: a frame whose source has a valid list is not swept
         uint2 h = make_uint2(0u, 0u);
-        if (tx.src >= 0 && t.nc.state[tx.src] == t.nc.word) h = make_uint2(t.nc.len[tx.src] + 1u, t.nc.off[tx.src]);
+        if (t.nc.arena_rssi != nullptr) {
+            // heard form (block-uniform): the pool's entry, which another context's publish kernel may be storing right now on another
+            // stream.  ONE 8-byte load: a value that is not the newest is an older one -- a miss, or a valid entry with its final
+            // offset and length, whose records were written back before the kernel that stored it began (rm_engine.h).
+            if (tx.src >= 0) {
+                const uint64_t en = __hip_atomic_load(&t.nc.entry[tx.src], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (nc_entry_word(en) == t.nc.word) h = make_uint2(nc_entry_len(en) + 1u, nc_entry_off(en));
+            }
+        } else if (tx.src >= 0 && t.nc.state[tx.src] == t.nc.word) {
+            h = make_uint2(t.nc.len[tx.src] + 1u, t.nc.off[tx.src]);
+        }
         t.nc.hit[e] = h;
         const bool swept = h.x == 0u && f.w >= 0.f;
         if (h.x) f.w = -1.f; // (never near: the near-frame lists and phase A drop it)

@@ -105,6 +105,18 @@ struct PinnedBlock {
     }
 };
 
+// what a pool of heard lists (rm_ncpool.hpp) owns on its device: one entry per node, the three columns of the arena, the arena's
+// bump counter, and the event behind the last epoch's resets -- a context that joins makes its stream wait for it
+struct NcPoolMem {
+    DevBuf<unsigned long long> entry, bump;
+    DevBuf<int32_t> arena;
+    DevBuf<double> arena_rssi;
+    DevBuf<uint8_t> arena_verdict;
+    size_t arena_len = 0;
+    hipEvent_t reset_ev = nullptr;
+};
+NcRegistry<NcPoolMem> &nc_registry();
+
 } // namespace rmh
 
 using rmh::DevBuf;
@@ -564,20 +576,23 @@ struct rm_context : TickSlot {
     // the source candidate cache of the batched sweep (rm::NbrCacheDev): per node a state word and its list's place
     // in the arena; per tick of the running batch its counters and per-frame words.  `change` moves (prepare_nodes) whenever the
     // receiver table or the pre-filter is rebuilt; a batch that finds it moved begins a new epoch on the device: every list is
-    // stale, the arena is handed out from its start again.  So does a batch that takes another FORM of the cache than the one
-    // before (heard: draw-free batches keep finished records, arena_rssi / arena_verdict beside the arena; candidates otherwise).
+    // stale, the arena is handed out from its start again.  So does a batch of the candidates FORM behind one of the heard form
+    // (heard: draw-free batches keep finished records; candidates otherwise).
+    // The heard form's per-source part -- entries, arena columns, bump counter -- is not the context's: it lies in a pool
+    // (rmh::NcPoolMem, rm_ncpool.hpp) shared with every context of the device whose table and medium are equal, attached to by
+    // the first heard-form batch and left in rm_destroy.  `pool_seen` is the value of `change` the attachment was made or last
+    // confirmed at.  The candidates form below stays private: its lists hold engine positions.
     struct NbrCache {
         DevBuf<uint32_t> state, off, len, tick_cnt, cur;
-        DevBuf<int32_t> arena, fill, unserved;
-        DevBuf<double> arena_rssi;     // (heard form only: allocated by the first batch that takes it)
-        DevBuf<uint8_t> arena_verdict;
+        DevBuf<int32_t> arena, fill, unserved;   // (arena, off, len: allocated by the first batch of the candidates form)
         DevBuf<uint2> hit;
         DevBuf<unsigned long long> ctr;
-        uint64_t change = 1, seen = 0;
+        uint64_t change = 1, seen = 0, pool_seen = 0;
         uint32_t epoch = 0;
         int nodes = -1;
         int form = -1;                 // of the last batch: 0 candidates, 1 heard
         unsigned long long batches[2] = {0, 0}; // launch sequences per form (nbr_cache_report)
+        rmh::NcPool<rmh::NcPoolMem> *pool = nullptr;
     } nc;
     // larger batches: k_fetch_ticks reads them from pinned, host-mapped memory (two staging buffers, each
     // guarded by an event: it is rewritten only after the kernel that read it has completed)
@@ -957,6 +972,7 @@ TickSlot *slot_of(rm_context *c, int32_t slot);
 int launch_batch(rm_context *c, TickSlot *const *slots, const TickPlan *plans, int n, const rm::ModelDev *m_override = nullptr,
                  int (*after_sweep)(rm_context *, void *) = nullptr, void *after_arg = nullptr, const rm::RankFramesArgs *rank_frames = nullptr);
 // a rank's frame list for tick `t` of a batch of gathered source indices (plan and slot prepared; n_pub gathered slots)
+void nbr_cache_detach(rm_context *c);  // rm_destroy, behind its stream synchronize: leave the pool of heard lists; the last context frees it
 void nbr_cache_report(rm_context *c); // RM_HOST_TIMING=1: what the source candidate cache served, in which form, and what was swept (stderr)
 bool rank_frames_wanted(rm_context *c);
 int plan_rank_frames(rm_context *c, TickSlot &ts, rm::TickDev &t, int n_pub);

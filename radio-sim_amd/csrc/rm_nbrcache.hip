@@ -1,4 +1,4 @@
-// rm_nbrcache.hip -- the source cache of the batched sweep (NbrCacheDev): claim, fill, expand
+// rm_nbrcache.hip -- the source cache of the batched sweep (NbrCacheDev): claim, fill, publish, expand
 // (part of libradiomedium_hip.so; gfx950 only, -ffp-contract=off, no fast-math; overview at the top of rm_engine.h)
 #include "rm_device.hpp"
 
@@ -6,8 +6,10 @@ namespace rm {
 
 // ============================================================================ the source cache (NbrCacheDev)
 // Three kernels, in both forms of the cache: claim (a swept frame's source gets a list), fill (the list's entries), expand (a
-// frame the pre-pass took out of the sweep gets what its source's list holds).  A list written here is read by LATER launch
-// sequences only (the pre-pass of this one has run), so the order of the stream is all the ordering there is.
+// frame the pre-pass took out of the sweep gets what its source's list holds).  A candidates list written here is read by LATER
+// launch sequences of the same context only (the pre-pass of this one has run), so the order of the stream is all the ordering
+// there is.  A heard list lies in a pool that several contexts, each on its stream, read and fill: a fourth kernel, publish,
+// makes it valid behind the fill (rm_engine.h: NbrCacheDev).
 // Heard form (t.nc.arena_rssi != nullptr, block-uniform in every kernel below): expand alone runs before the exact stage and
 // only hands the hit frames' list lengths to the reorder stage's scan; claim and fill run BEHIND the reorder stage (and
 // k_reorder_served_batch, rm_reorder.hip) and take the swept frames' finished records from the ordered arrays.
@@ -52,8 +54,17 @@ __global__ void __launch_bounds__(256) k_nc_claim_batch(const TickDev *__restric
     if (e < n_eval && !dropped && (heard || t.nc.hit[e].x == 0u)) {
         s = t.p_src[e];
         if (s >= 0) {
-            const uint32_t st = t.nc.state[s];
-            if ((st >> 1) != (t.nc.word >> 1) && atomicCAS(&t.nc.state[s], st, t.nc.word & ~1u) == st) {
+            bool won;
+            if (heard) {
+                // the pool's entry: "claimed in this epoch, not valid" keeps every context off the source, this one's later launch
+                // sequences included, until k_nc_publish_batch stores the valid entry behind the fill
+                const unsigned long long en = __hip_atomic_load(&t.nc.entry[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                won = (nc_entry_word(en) >> 1) != (t.nc.word >> 1) && atomicCAS(&t.nc.entry[s], en, (unsigned long long)nc_entry_pack(t.nc.word & ~1u, 0u, 0u)) == en;
+            } else {
+                const uint32_t st = t.nc.state[s];
+                won = (st >> 1) != (t.nc.word >> 1) && atomicCAS(&t.nc.state[s], st, t.nc.word & ~1u) == st;
+            }
+            if (won) {
                 cnt = heard ? t.cursor[e - t.cnt_base] : t.cand_tot[e - t.cnt_base]; // (heard: the frame's final heard count)
                 mine = cnt <= kNcListCap;
             }
@@ -65,21 +76,28 @@ __global__ void __launch_bounds__(256) k_nc_claim_batch(const TickDev *__restric
     const uint32_t wave_total = uint32_t(__shfl(int(inc), 63));
     unsigned long long o = 0;
     if (wave_total) {
-        if (lane == 0) o = atomicAdd(&t.nc.ctr[0], (unsigned long long)wave_total);
+        if (lane == 0) o = atomicAdd(heard ? t.nc.bump : &t.nc.ctr[0], (unsigned long long)wave_total);
         o = (unsigned long long)uint32_t(__shfl(int(uint32_t(o)), 0)) | ((unsigned long long)uint32_t(__shfl(int(uint32_t(o >> 32)), 0)) << 32);
         o += inc - want;
     }
     int32_t fill = -1;
     if (mine && o + cnt <= (unsigned long long)t.nc.arena_len) {
-        t.nc.off[s] = uint32_t(o);
-        t.nc.len[s] = cnt;
-        t.nc.state[s] = t.nc.word; // (this thread owns the word; read by later launch sequences only)
-        if (cnt) fill = int32_t(o);
+        if (heard) {
+            // (nothing becomes valid here: the records are not in the arena yet, and another stream may look at any time)
+            fill = cnt ? int32_t(o) : kNcFillEmpty;
+        } else {
+            t.nc.off[s] = uint32_t(o);
+            t.nc.len[s] = cnt;
+            t.nc.state[s] = t.nc.word; // (this thread owns the word; read by later launch sequences of this context only)
+            if (cnt) fill = int32_t(o);
+        }
     }
     if (k >= n_walk) return;
     t.nc.fill[k] = fill;
     if (!heard) t.nc.cur[e] = 0u; // (candidates copied so far: the heard form's fill does not count)
-    const uint64_t fm = ballot64(fill >= 0);
+    // (heard form: the accepted lists without entries count as well -- a tick of nothing else still has them to publish; the fill
+    // finds no record to copy for them)
+    const uint64_t fm = ballot64(fill != -1);
     if (fm && int(threadIdx.x & 63) == __ffsll((long long)fm) - 1) atomicAdd(&t.nc.tick_cnt[1], uint32_t(__popcll(fm)));
 }
 
@@ -152,6 +170,30 @@ __global__ void __launch_bounds__(256) k_nc_fill_batch(const TickDev *__restrict
     }
 }
 
+// heard form: the lists claimed in this launch sequence become valid -- a launch of its own behind the fill, so that the fill's
+// records are written back before any entry says so.  One thread per position of the claim's walk: fill[k] tells an accepted
+// list (its offset, or kNcFillEmpty) from a frame that claimed nothing; the entry -- valid bit, offset, length -- is one
+// agent-scope store, which a pre-pass on another stream sees whole or not at all.  A tick that claimed nothing returns at once.
+__global__ void __launch_bounds__(256) k_nc_publish_batch(const TickDev *__restrict__ ticks)
+{
+    const TickDev &t = ticks[blockIdx.z];
+    if (t.nc.state == nullptr || t.nc.arena_rssi == nullptr || uniform_u(t.nc.tick_cnt[1]) == 0u) return;
+    const int n_eval = t.n_active - t.first_eval;
+    const bool listed = uniform_u(t.nc.tick_cnt[2]) != 0u;
+    const int n_walk = listed ? min(int(uniform_u(t.nc.tick_cnt[3])), n_eval) : n_eval;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_walk) return;
+    const int32_t fo = t.nc.fill[k];
+    if (fo == -1) return;
+    const int e = listed ? t.nc.unserved[k] : k;
+    if (e < 0 || e >= n_eval) return;
+    const int s = t.p_src[e];
+    if (s < 0) return;
+    // (an empty list lies nowhere: offset 0, so that the arena's very end needs no 28th bit)
+    const uint32_t len = fo >= 0 ? t.cursor[e - t.cnt_base] : 0u;
+    __hip_atomic_store(&t.nc.entry[s], (unsigned long long)nc_entry_pack(t.nc.word, fo >= 0 ? uint32_t(fo) : 0u, len), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // what the frames that the pre-pass took out of the sweep get from their sources' lists
 // Heard form: one thread per frame: the list's length goes into cursor[] -- the frame's heard count for the reorder stage's scan.
 // Candidates form: one wave per 64 frames: the list of each hit frame goes into one of the tick's shards as a run of (frame,
@@ -217,6 +259,7 @@ hipError_t launch_nbr_cache_batch(hipStream_t s, const TickDev *ticks, int n, co
     } else if (heard) {
         RM_KLAUNCH(k_nc_claim_batch, dim3(cdiv(max_eval, 256), 1, n), dim3(256), 0, s, b);
         RM_KLAUNCH(k_nc_fill_batch, dim3(cdiv(max_eval, kBlock), 1, n), dim3(kBlock), 0, s, b);
+        RM_KLAUNCH(k_nc_publish_batch, dim3(cdiv(max_eval, 256), 1, n), dim3(256), 0, s, b);
     } else if (!behind_reorder) {
         RM_KLAUNCH(k_nc_claim_batch, dim3(cdiv(max_eval, 256), 1, n), dim3(256), 0, s, b);
         RM_KLAUNCH(k_nc_fill_batch, dim3(1, shards, n), dim3(256), 0, s, b);
