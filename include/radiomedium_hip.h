@@ -1212,6 +1212,96 @@ int rm_fwd_queue_read(rm_context *ctx, const int32_t *nodes, int32_t n, rm_fwd_p
 int rm_fwd_device(rm_context *ctx, const rm_fwd_node **dev_node, const rm_fwd_packet **dev_packets /* [n_nodes][queue_slots] */,
                   const rm_fwd_totals **dev_totals);
 
+/* ---- dissemination floods: Trickle-timed broadcast relay on the device ---------------------------------------------------------
+ * (not reference behaviour.)  One-to-all dissemination under Trickle's suppression rule
+ * (RFC 6206, one data version): per-node flood state in device memory and the calls that move it from one evaluated tick to the
+ * next.  No evaluating call changes: every call here reads a FINISHED result, as the unicast query does, or only the feature's own
+ * table.  Off by default; then nothing is allocated or launched.  Memory when on: n_nodes * 84 bytes (a 64-byte row, 16 bytes of
+ * scratch, one word per packet number of an advance or seed list, sized for n_nodes entries at enable; a longer list grows it).
+ * All integers are exact, and no state depends on launch geometry or on the order in which atomics land.
+ *
+ * State per node j (rm_flood_node): first_us (-1: j does not have the data), start_us and fire_us of its running interval (-1:
+ * nothing scheduled), rssi_bits (the bits of the first link's rssi, 0 at a seed), parent (-1 at a seed and without the data),
+ * hop (-1 without the data), interval m, c, and the counters sent, suppressed, heard, deferred.
+ * Schedule: a node that got the data at first_us has intervals of length I_m = imin_us << min(m, doublings) that start at
+ * s_m = first_us + sum of I_i over i < m; it fires at f_m = s_m + I_m / 2 + r, r = (h * (I_m / 2)) >> 64 (the 128-bit product),
+ * h = mix64(mix64(mix64(mix64(seed + 0x9E3779B97F4A7C15) ^ (uint64_t)(uint32_t)j) ^ (uint64_t)first_us) ^ (uint64_t)m) (mix64: the
+ * hash of the link draws).  With m == max_intervals the node is done: start_us = fire_us = -1.  j is DUE AT t iff it has the
+ * data, m < max_intervals and fire_us <= t.  rm_flood_fire is this rule as a pure host function.
+ *
+ * rm_flood_seed*: a valid entry that does not have the data gets first_us = time_us, hop 0, parent -1, m 0, c 0 and its schedule
+ * (seeds++, covered++); entries outside the table and nodes that have the data, duplicates included, change nothing.
+ *
+ * rm_flood_sources*: one walk over the nodes.  A node due at time_us with redundancy k > 0 and c >= k is SUPPRESSED: suppressed++,
+ * m++, c = 0, the next schedule; nothing else happens to it in this call, even if the new fire_us <= time_us.  Every other due
+ * node is listed in ascending node index, padded with -1 up to cap; *count is the true number, and with count > cap the list
+ * holds the first cap.  A listed node's state does not change: it stays due until an advance sees it transmit.  A ready dev_src
+ * of rm_tick_run_sources_device, of the gated tick and of a batch row.
+ *
+ * rm_flood_advance*: slot, state rules and candidate list as rm_fwd_advance*.  A slot that overflowed its link capacity or was
+ * dropped: nothing changes but skipped_slots++.  All judgments are on the state at the start of the call.
+ *  Transmitters, packet numbers p = 0 .. P - 1 with candidate j: j outside the table or without the data: nothing (foreign
+ *  traffic); a later occurrence of j: stray++; j not due at recs[p].start_us: stray++; recs[p].src != j (a gate deferred it):
+ *  deferred[j]++ and j stays due; otherwise j SENT: sent[j]++, m++, c = 0, the next schedule.
+ *  Receivers, every link of the slot with verdict RM_DELIVERED, of packet p (any p < n_new) to node d in the table, whose
+ *  s = recs[p].src is in the table and has the data, t_end = recs[p].start_us + recs[p].air_us: heard[d]++.  If d has the data,
+ *  does not send in this call and t_end >= start_us[d]: c[d]++.  If d does not have the data and hop[s] + 1 <= max_hops: among
+ *  all such links of this slot at d the one with the least (t_end, p) wins and d gets first_us = t_end, parent = s,
+ *  hop = hop[s] + 1, rssi_bits, m = 0, c = 0 and its schedule (covered++); the other copies count in heard only.
+ * Identities: covered = seeds + first receptions = the nodes with first_us >= 0; the sums of the per-node sent / suppressed /
+ * heard / deferred are the totals; interval = sent + suppressed per node.  max_hop and last_first_us are the maxima over the
+ * covered nodes (0 when there is none).
+ *
+ * rm_flood_tree_device gathers parent (and hop, unless NULL) into contiguous arrays: dev_parent is a valid argument of
+ * rm_fwd_set_next_device (with the seed list as roots), of rm_hops_next_device and of a K = 1 rm_linkstats_watch_device.
+ *
+ * The device forms are enqueued on the context's stream and not waited for.  RM_ERR_STATE, nothing launched: the feature is off;
+ * for advance what rm_unicast_query refuses (no evaluated result, a receiver partition, a gathered / rm_dist_* / rm_group_* form,
+ * RM_GRAPH=1); rm_flood_enable on a context made under RM_GRAPH=1 or without nodes.  RM_ERR_INVALID, nothing launched: bad
+ * parameters, NULL arguments, negative counts or times, cap < 1, slot outside the last call's slots, a host list entry >= n_nodes.
+ * rm_nodes_upload with another node count switches the feature off; the same count, rm_node_update, rm_nodes_move and
+ * rm_set_model keep everything.  Out of scope: several data versions and Trickle's inconsistency reset, payload lengths,
+ * partitions and the multi-rank forms. */
+typedef struct rm_flood_params {
+    int64_t imin_us;       /* 2 .. 2^32 */
+    int32_t doublings;     /* 0 .. 16 */
+    int32_t max_intervals; /* 1 .. 64 */
+    int32_t redundancy;    /* 0 .. 255; 0: never suppress */
+    int32_t max_hops;      /* 1 .. 65535 */
+    uint64_t seed;
+} rm_flood_params; /* 32 bytes */
+typedef struct rm_flood_node { /* 64 bytes: the table's row */
+    int64_t first_us, start_us, fire_us;
+    uint64_t rssi_bits;
+    int32_t parent, hop, interval, c;
+    uint32_t sent, suppressed, heard, deferred;
+} rm_flood_node;
+typedef struct rm_flood_totals {
+    uint64_t covered, seeds, sent, suppressed, heard, deferred, stray, skipped_slots, max_hop, last_first_us;
+} rm_flood_totals; /* 80 bytes */
+void rm_flood_defaults(rm_flood_params *p); /* 8000 us, 4 doublings, 8 intervals, k = 2, 255 hops, seed 0 */
+/* pure host functions, no device: RM_OK or RM_ERR_INVALID; node >= 0, first_us >= 0, 0 <= m <= max_intervals */
+int rm_flood_validate(const rm_flood_params *p);
+int rm_flood_fire(const rm_flood_params *p, int32_t node, int64_t first_us, int32_t m, int64_t *start_us, int64_t *fire_us);
+/* enable (again: with new parameters, everything cleared), release, state */
+int rm_flood_enable(rm_context *ctx, const rm_flood_params *p);
+int rm_flood_disable(rm_context *ctx);
+int rm_flood_enabled(const rm_context *ctx);
+int rm_flood_get_params(const rm_context *ctx, rm_flood_params *out);
+int rm_flood_reset(rm_context *ctx); /* nobody has the data, counters and totals zero; keeps the parameters */
+int rm_flood_seed_device(rm_context *ctx, const int32_t *dev_nodes, int32_t n, int64_t time_us);
+int rm_flood_seed(rm_context *ctx, const int32_t *nodes, int32_t n, int64_t time_us);
+int rm_flood_sources_device(rm_context *ctx, int64_t time_us, int32_t cap, int32_t *dev_src /* [cap] */, int32_t *dev_count);
+int rm_flood_sources(rm_context *ctx, int64_t time_us, int32_t cap, int32_t *src /* [cap] */, int32_t *count); /* synchronises */
+int rm_flood_advance_device(rm_context *ctx, int32_t slot, const int32_t *dev_cand /* or NULL */, int32_t n_cand);
+int rm_flood_advance(rm_context *ctx, int32_t slot, const int32_t *cand /* or NULL */, int32_t n_cand); /* uploads the list */
+/* n rows (nodes NULL: all, n = n_nodes) and the totals (may be NULL; out may be NULL with n = 0); synchronises */
+int rm_flood_read(rm_context *ctx, const int32_t *nodes, int32_t n, rm_flood_node *out, rm_flood_totals *totals);
+/* the table in device memory (valid until disable, another enable or another node count); either pointer may be NULL */
+int rm_flood_device(rm_context *ctx, const rm_flood_node **dev_node, const rm_flood_totals **dev_totals);
+/* the measured tree: parent and hop by node index, int32[n_nodes] each, in device memory (dev_hop may be NULL); not waited for */
+int rm_flood_tree_device(rm_context *ctx, int32_t *dev_parent, int32_t *dev_hop);
+
 /* ---- several devices behind one caller --------------------------------------------------------------
  * The reference host is ONE process (Main.java:65-73): a group drives n contexts from one host thread, one
  * per device (an ordinal may repeat: several partitions on one GPU).  Receivers are partitioned over the

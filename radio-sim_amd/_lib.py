@@ -123,6 +123,18 @@ FWD_TOTALS_DTYPE = np.dtype([(f, "<u8") for f in ("generated", "arrived", "dropp
                                                   "in_flight", "stray", "skipped_slots", "latency_us_sum", "hops_sum")])
 assert C.sizeof(FwdParams) == 40 and FWD_NODE_DTYPE.itemsize == 128 and FWD_PACKET_DTYPE.itemsize == 24 and FWD_TOTALS_DTYPE.itemsize == 88
 
+class FloodParams(C.Structure):
+    """rm_flood_params: the dissemination floods' parameters (32 bytes)"""
+    _fields_ = [("imin_us", C.c_int64), ("doublings", C.c_int32), ("max_intervals", C.c_int32), ("redundancy", C.c_int32),
+                ("max_hops", C.c_int32), ("seed", C.c_uint64)]
+
+
+FLOOD_NODE_DTYPE = np.dtype([("first_us", "<i8"), ("start_us", "<i8"), ("fire_us", "<i8"), ("rssi_bits", "<u8"), ("parent", "<i4"), ("hop", "<i4"),
+                             ("interval", "<i4"), ("c", "<i4"), ("sent", "<u4"), ("suppressed", "<u4"), ("heard", "<u4"), ("deferred", "<u4")])
+FLOOD_TOTALS_DTYPE = np.dtype([(f, "<u8") for f in ("covered", "seeds", "sent", "suppressed", "heard", "deferred", "stray", "skipped_slots",
+                                                    "max_hop", "last_first_us")])
+assert C.sizeof(FloodParams) == 32 and FLOOD_NODE_DTYPE.itemsize == 64 and FLOOD_TOTALS_DTYPE.itemsize == 80
+
 NODE_STATS_DTYPE = np.dtype([(name, "<u8") for name, _ in NodeStats._fields_])
 assert NODE_STATS_DTYPE.itemsize == C.sizeof(NodeStats) == 64
 
@@ -463,6 +475,23 @@ SIGNATURES = {
     "rm_fwd_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "rm_fwd_queue_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "rm_fwd_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "rm_flood_defaults": (None, [C.POINTER(FloodParams)]),
+    "rm_flood_validate": (C.c_int, [C.POINTER(FloodParams)]),
+    "rm_flood_fire": (C.c_int, [C.POINTER(FloodParams), C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "rm_flood_enable": (C.c_int, [C.c_void_p, C.POINTER(FloodParams)]),
+    "rm_flood_disable": (C.c_int, [C.c_void_p]),
+    "rm_flood_enabled": (C.c_int, [C.c_void_p]),
+    "rm_flood_get_params": (C.c_int, [C.c_void_p, C.POINTER(FloodParams)]),
+    "rm_flood_reset": (C.c_int, [C.c_void_p]),
+    "rm_flood_seed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64]),
+    "rm_flood_seed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64]),
+    "rm_flood_sources_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rm_flood_sources": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
+    "rm_flood_advance_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "rm_flood_advance": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "rm_flood_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rm_flood_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "rm_flood_tree_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rm_det_math": (C.c_double, [C.c_int32, C.c_double]),
     "rm_link_hash": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
     "rm_evq_init": (None, [C.c_void_p]),

@@ -116,6 +116,7 @@ int passes_nodes_changed(rm_context *c)
     RM_TRY(listen_nodes_changed(c));
     RM_TRY(traffic_nodes_changed(c));
     RM_TRY(fwd_nodes_changed(c));
+    RM_TRY(flood_nodes_changed(c));
     return linkstats_nodes_changed(c);
 }
 
@@ -129,6 +130,7 @@ void passes_release(rm_context *c)
     hops_release(c);
     routes_release(c);
     fwd_release(c);
+    flood_release(c);
 }
 
 } // namespace rmh

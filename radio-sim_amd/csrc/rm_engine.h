@@ -1092,6 +1092,31 @@ hipError_t launch_fwd_sources(hipStream_t s, const FwdDev &f, int64_t time_us, i
 // packet numbers 0 .. P - 1 of the slot described by `slot` (cand: nullptr or [P]); act: room for P records
 hipError_t launch_fwd_advance(hipStream_t s, const FwdDev &f, const UcSlot &slot, const int32_t *cand, int P);
 
+// (rm_flood.hip) the dissemination floods.  node / totals are the context's table; claim and
+// pmin ([n_nodes], INT32_MAX at rest) and tmin ([n_nodes], INT64_MAX at rest) are per-node scratch that every call leaves as it found
+// it; act holds one word per entry of the running advance or seed list (the candidate in the table with the data, or -1).
+struct FloodDev {
+    rm_flood_node *node;
+    rm_flood_totals *totals;
+    int32_t *claim, *pmin;
+    int64_t *tmin;
+    int32_t *act;
+    int n_nodes;
+    int doublings, max_intervals, redundancy, max_hops;
+    int64_t imin_us;
+    uint64_t seed;
+};
+// every row at rest (nobody has the data), the scratch at rest, the totals zero
+hipError_t launch_flood_init(hipStream_t s, const FloodDev &f);
+// act: room for n words
+hipError_t launch_flood_seed(hipStream_t s, const FloodDev &f, const int32_t *nodes, int n, int64_t time_us);
+// unit_count: [units] words of scratch, units and chunk from traffic_geometry(n_nodes)
+hipError_t launch_flood_sources(hipStream_t s, const FloodDev &f, int64_t time_us, int cap, int units, int chunk, int32_t *unit_count,
+                                int32_t *out_src, int32_t *out_count);
+// packet numbers 0 .. P - 1 of the slot described by `slot` (cand: nullptr or [P]) and all of the slot's links; act: room for P words
+hipError_t launch_flood_advance(hipStream_t s, const FloodDev &f, const UcSlot &slot, const int32_t *cand, int P);
+hipError_t launch_flood_tree(hipStream_t s, const FloodDev &f, int32_t *parent, int32_t *hop);
+
 // reception stage (rm_events.hip)
 hipError_t launch_ev_append(hipStream_t s, const EvDev &e, const EvLinkSrc &ls, const rm_tx_record *tx, int n_new, int64_t now,
                             int immediate, const uint32_t *dropped_flag);

@@ -304,6 +304,20 @@ struct rm_context : TickSlot {
         DevBuf<rm::FwdAct> act;
         PinnedBlock h;
     } fw;
+    // dissemination floods (E20; rm_api_flood.cpp, rm_flood.hip): the parameters, the table by node index and its totals, the
+    // per-node scratch every call leaves at rest, one word per entry of an advance or seed list, the source list's unit counts,
+    // the host forms' lists in device memory, and the pinned, host-mapped block a list read is staged through.  Nothing is
+    // allocated before rm_flood_enable.
+    struct Flood {
+        bool on = false;
+        int32_t n = -1; // the node count the table was made for; -1: off
+        rm_flood_params p{};
+        DevBuf<rm_flood_node> node;
+        DevBuf<rm_flood_totals> totals;
+        DevBuf<int32_t> claim, pmin, act, unit_count, stage;
+        DevBuf<int64_t> tmin;
+        PinnedBlock h;
+    } fl;
     double base_rssi = -100.0; // AbstractRadioMedium.java:38
 
     // host mirror of the node table (Simulator.getNodes() snapshot)
@@ -958,6 +972,12 @@ int uc_slots(rm_context *c, bool all, const uint32_t *prefix, int n_prefix, rm::
 int fwd_nodes_changed(rm_context *c);
 // rm_destroy
 void fwd_release(rm_context *c);
+
+// ---- rm_api_flood.cpp: dissemination floods (E20)
+// rm_nodes_upload: another node count switches the feature off
+int flood_nodes_changed(rm_context *c);
+// rm_destroy
+void flood_release(rm_context *c);
 
 // ---- rm_api_comm.cpp
 int comm_all_gather(rm_context *c, const void *mine, void *all, size_t bytes);

@@ -232,6 +232,34 @@ RM_HD uint32_t fwd_backoff_factor(const uint64_t seed, const int32_t min_be, con
     return uint32_t(h2 >> (64 - be));
 }
 
+// the floods' Trickle schedule: what the parameters may hold, and interval m of a node that got the data
+// at first_us -- where it starts and when the node fires in it; m >= max_intervals: done, both -1.  The text the kernels
+// (rm_flood.hip), rm_flood_fire and rm_flood_validate are built from.  64-bit integers only.
+RM_HD bool flood_valid(const rm_flood_params &p)
+{
+    if (p.imin_us < 2 || p.imin_us > (int64_t(1) << 32)) return false;
+    if (p.doublings < 0 || p.doublings > 16 || p.max_intervals < 1 || p.max_intervals > 64) return false;
+    return p.redundancy >= 0 && p.redundancy <= 255 && p.max_hops >= 1 && p.max_hops <= 65535;
+}
+
+RM_HD void flood_fire(const int64_t imin_us, const int32_t doublings, const int32_t max_intervals, const uint64_t seed, const int32_t node,
+                      const int64_t first_us, const int32_t m, int64_t &start_us, int64_t &fire_us)
+{
+    if (m < 0 || m >= max_intervals) {
+        start_us = fire_us = -1;
+        return;
+    }
+    // the sum of I_i over i < m: the doubling ones are imin * (2^g - 1), g = min(m, D); the rest have the largest length
+    const int g = m < doublings ? m : doublings;
+    const int64_t len = imin_us << g; // (at most 2^48)
+    const int64_t before = imin_us * ((int64_t(1) << g) - 1) + int64_t(m - g) * len;
+    const uint64_t half = uint64_t(len >> 1);
+    uint64_t h = mix64(mix64(mix64(seed + 0x9E3779B97F4A7C15ull) ^ uint64_t(uint32_t(node))) ^ uint64_t(first_us));
+    h = mix64(h ^ uint64_t(m));
+    start_us = first_us + before;
+    fire_us = start_us + int64_t(half) + int64_t(uint64_t((static_cast<unsigned __int128>(h) * half) >> 64)); // (one text for host and device)
+}
+
 // the traffic schedule: what a record may hold, a packet's due time, and the number of a node's packets
 // due before a time -- the text the generator (rm_traffic.hip), rm_traffic_due and rm_traffic_validate are all built from.
 // 64-bit integers only.

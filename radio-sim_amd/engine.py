@@ -775,6 +775,100 @@ class Engine:
         check(self._L.rm_fwd_device(self._h, C.byref(a), C.byref(b), C.byref(t)))
         return a.value, b.value, t.value
 
+    # -- dissemination floods: Trickle-timed broadcast relay on the device
+    @staticmethod
+    def flood_params(**kw):
+        """rm_flood_defaults with the given fields replaced: imin_us, doublings, max_intervals, redundancy, max_hops, seed"""
+        p = _lib.FloodParams()
+        _lib.lib().rm_flood_defaults(C.byref(p))
+        for k, v in kw.items():
+            if k not in dict(_lib.FloodParams._fields_):
+                raise TypeError("rm_flood_params has no field " + k)
+            setattr(p, k, int(v) & (2 ** 64 - 1) if k == "seed" else int(v))
+        return p
+
+    @staticmethod
+    def flood_validate(params):
+        """rm_flood_validate (pure host): the return code of the validation rm_flood_enable runs (0: accepted)"""
+        return int(_lib.lib().rm_flood_validate(C.byref(params)))
+
+    @staticmethod
+    def flood_fire(params, node, first_us, m):
+        """rm_flood_fire (pure host): (start_us, fire_us) of interval m of a node that got the data at first_us; (-1, -1): done"""
+        s, f = C.c_int64(), C.c_int64()
+        check(_lib.lib().rm_flood_fire(C.byref(params), int(node), int(first_us), int(m), C.byref(s), C.byref(f)))
+        return s.value, f.value
+
+    def flood_enable(self, params=None, **kw):
+        """rm_flood_enable: the table made (again: cleared) with `params` or flood_params(**kw)"""
+        p = params if params is not None else self.flood_params(**kw)
+        check(self._L.rm_flood_enable(self._h, C.byref(p)))
+
+    def flood_get_params(self):
+        p = _lib.FloodParams()
+        check(self._L.rm_flood_get_params(self._h, C.byref(p)))
+        return p
+
+    def flood_disable(self):
+        check(self._L.rm_flood_disable(self._h))
+
+    def flood_enabled(self):
+        return bool(self._L.rm_flood_enabled(self._h))
+
+    def flood_reset(self):
+        """rm_flood_reset: nobody has the data, counters and totals zero; the parameters kept"""
+        check(self._L.rm_flood_reset(self._h))
+
+    def flood_seed(self, nodes, time_us):
+        """rm_flood_seed: every listed node that lacks the data gets it at time_us (negative entries: padding)"""
+        idx = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+        check(self._L.rm_flood_seed(self._h, _ptr(idx) if idx.shape[0] else None, idx.shape[0], int(time_us)))
+
+    def flood_seed_device(self, dev_nodes_ptr, n, time_us):
+        check(self._L.rm_flood_seed_device(self._h, dev_nodes_ptr, int(n), int(time_us)))
+
+    def flood_sources(self, time_us, cap):
+        """rm_flood_sources: the suppression roll, then -> (int32[cap], the due nodes ascending, padded with -1; their true number)"""
+        out = np.empty(max(int(cap), 0), dtype=np.int32)
+        count = C.c_int32()
+        check(self._L.rm_flood_sources(self._h, int(time_us), int(cap), out.ctypes.data if out.shape[0] else None, C.byref(count)))
+        return out, count.value
+
+    def flood_sources_device(self, time_us, cap, dev_src_ptr, dev_count_ptr):
+        """The raw form: int32[cap] and one int32 in device memory, a ready source list of the device ticks; not waited for"""
+        check(self._L.rm_flood_sources_device(self._h, int(time_us), int(cap), dev_src_ptr, dev_count_ptr))
+
+    def flood_advance(self, slot=0, cand=None):
+        """rm_flood_advance: result slot `slot` of the last evaluating call moves the flood; cand: the candidate list handed to that
+        call (a gated tick), None: the frames' own sources"""
+        if cand is None:
+            check(self._L.rm_flood_advance(self._h, int(slot), None, 0))
+            return
+        idx = np.ascontiguousarray(cand, dtype=np.int32).reshape(-1)
+        keep = idx if idx.shape[0] else np.zeros(1, dtype=np.int32)
+        check(self._L.rm_flood_advance(self._h, int(slot), keep.ctypes.data, idx.shape[0]))
+
+    def flood_advance_device(self, slot, dev_cand_ptr, n_cand):
+        check(self._L.rm_flood_advance_device(self._h, int(slot), dev_cand_ptr, int(n_cand)))
+
+    def flood_read(self, nodes=None):
+        """rm_flood_read: (structured array of FLOOD_NODE_DTYPE -- the listed nodes in list order, or all --, the totals as a dict)"""
+        ptr, n, _idx = self._node_list(nodes)
+        out = np.zeros(n, dtype=_lib.FLOOD_NODE_DTYPE)
+        tot = np.zeros(1, dtype=_lib.FLOOD_TOTALS_DTYPE)
+        check(self._L.rm_flood_read(self._h, ptr, n, out.ctypes.data if n else None, tot.ctypes.data))
+        return out, {k: int(tot[k][0]) for k in tot.dtype.names}
+
+    def flood_device(self):
+        """rm_flood_device: device pointers (rows [n_nodes] of 64 bytes, totals)"""
+        a, t = C.c_void_p(), C.c_void_p()
+        check(self._L.rm_flood_device(self._h, C.byref(a), C.byref(t)))
+        return a.value, t.value
+
+    def flood_tree_device(self, dev_parent_ptr, dev_hop_ptr=None):
+        """rm_flood_tree_device: parent (and hop) by node index into int32[n_nodes] arrays in device memory; not waited for"""
+        check(self._L.rm_flood_tree_device(self._h, dev_parent_ptr, dev_hop_ptr))
+
     # -- java.util.Random
     def seed(self, seed):
         check(self._L.rm_seed(self._h, seed))

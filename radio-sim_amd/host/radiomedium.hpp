@@ -853,6 +853,103 @@ public:
         }
         return true;
     }
+    // Dissemination floods (extension E20): Trickle-timed broadcast relay on the device.  setFlooding(&params) makes the table
+    // (nullptr: releases it); floodSeed gives the data to the listed nodes at `time`; floodSources rolls the suppression and gives
+    // the nodes due at `time` in node order (at most cap; *count: their true number); floodAdvance reads the LAST evaluated tick --
+    // the tick mode's flush -- and moves the flood: without candidates every frame's own source transmitted, with them
+    // candidates[k] is packet k's; floodTree gives every node's parent (nullptr: a seed or a node without the data) and hop (-1:
+    // without the data).  The state is the device's: it survives apply(), and a node table of another size switches the feature
+    // off.  false (or an empty list) and lastError on a refusal.
+    static rm_flood_params floodingDefaults()
+    {
+        rm_flood_params p;
+        rm_flood_defaults(&p);
+        return p;
+    }
+    bool setFlooding(const rm_flood_params *params)
+    {
+        lastError.clear();
+        if (params && !syncNodes()) return false; // the device mirrors the node table first: the table has its size
+        if ((params ? rm_flood_enable(ctx_, params) : rm_flood_disable(ctx_)) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        return true;
+    }
+    bool getFlooding() const { return rm_flood_enabled(ctx_) != 0; }
+    bool floodSeed(const std::vector<const Node *> &seeds, int64_t time)
+    {
+        lastError.clear();
+        if (!syncNodes()) return false;
+        std::vector<int32_t> idx;
+        for (const Node *nd : seeds) idx.push_back(nd ? nd->index : -1);
+        if (rm_flood_seed(ctx_, idx.empty() ? nullptr : idx.data(), int32_t(idx.size()), time) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        return true;
+    }
+    std::vector<Node *> floodSources(int64_t time, int32_t cap, int32_t *count = nullptr)
+    {
+        lastError.clear();
+        std::vector<Node *> out;
+        if (count) *count = 0;
+        if (!simulator || !syncNodes()) return out;
+        std::vector<int32_t> src(size_t(cap > 0 ? cap : 0) + 1);
+        int32_t n = 0;
+        if (rm_flood_sources(ctx_, time, cap, src.data(), &n) != RM_OK) {
+            lastError = rm_last_error();
+            return out;
+        }
+        const std::vector<Node *> &nodes = simulator->getNodes();
+        for (int32_t k = 0; k < std::min(n, cap); ++k) out.push_back(nodes[size_t(src[size_t(k)])]);
+        if (count) *count = n;
+        return out;
+    }
+    bool floodAdvance(const std::vector<const Node *> *candidates = nullptr)
+    {
+        lastError.clear();
+        std::vector<int32_t> cand;
+        if (candidates)
+            for (const Node *nd : *candidates) cand.push_back(nd ? nd->index : -1);
+        cand.push_back(-1); // (never an empty array; not counted)
+        if (rm_flood_advance(ctx_, 0, candidates ? cand.data() : nullptr, candidates ? int32_t(candidates->size()) : 0) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        return true;
+    }
+    // the node's row; totals (may be nullptr)
+    bool getFloodStatistics(const Node &node, rm_flood_node *out, rm_flood_totals *totals = nullptr)
+    {
+        lastError.clear();
+        const int32_t i = node.index;
+        if (!out || !syncNodes()) return false;
+        if (rm_flood_read(ctx_, &i, 1, out, totals) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        return true;
+    }
+    bool floodTree(std::vector<Node *> *parents, std::vector<int32_t> *hops = nullptr)
+    {
+        lastError.clear();
+        if (!parents || !simulator || !syncNodes()) return false;
+        const std::vector<Node *> &nodes = simulator->getNodes();
+        std::vector<rm_flood_node> rows(nodes.size() + 1);
+        if (rm_flood_read(ctx_, nullptr, int32_t(nodes.size()), rows.data(), nullptr) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        parents->assign(nodes.size(), nullptr);
+        if (hops) hops->assign(nodes.size(), -1);
+        for (size_t j = 0; j < nodes.size(); ++j) {
+            const int32_t par = rows[j].parent;
+            if (par >= 0 && size_t(par) < nodes.size()) (*parents)[j] = nodes[size_t(par)];
+            if (hops) (*hops)[j] = rows[j].hop;
+        }
+        return true;
+    }
     // Did a frame reach the node it was addressed to (extension E12)?  One entry per packet of the LAST evaluated tick -- the tick
     // mode's flush, or transmitIfClear() -- in packet order: destinations[k] is packet k's intended receiver (nullptr: not asked).
     // status is RM_UC_*; link the index of the heard link in the tick's result (-1 without one); rssi and sinr as the result has
