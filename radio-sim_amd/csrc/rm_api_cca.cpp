@@ -258,10 +258,7 @@ int cca_batch(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us, const i
         rm::ModelDev m = model_dev(c);
         if (c->f32_slack > 0.05) m.shadow_tbl = nullptr; // (as the query: the link-hash table goes with the fp32 filter of a small frame)
         {
-            // profiling (rm_profile_kernels names the kernels that ran); the gate does not move the ticks' sampling on
-            const uint64_t tick_index = c->tick_index;
-            ProbeScope probe(c);
-            c->tick_index = tick_index;
+            CallProbe probe(c); // (rm_profile_kernels names the kernels that ran)
             sample_stage(probe.smp, RM_STAGE_SINR);
             h_info[0] = 0u;
             RM_HIP(rm::launch_ccab_count(c->stream, nodes_dev(c), m, cb, h_ticks, k.ticks.p, grid));

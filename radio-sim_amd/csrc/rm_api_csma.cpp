@@ -181,10 +181,7 @@ int csma_batch(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us, const 
         rm::ModelDev m = model_dev(c);
         if (c->f32_slack > 0.05) m.shadow_tbl = nullptr; // (as the query: the link-hash table goes with the fp32 filter of a small frame)
         {
-            // profiling (rm_profile_kernels names the kernels that ran); the gate does not move the ticks' sampling on
-            const uint64_t tick_index = c->tick_index;
-            ProbeScope probe(c);
-            c->tick_index = tick_index;
+            CallProbe probe(c); // (rm_profile_kernels names the kernels that ran)
             sample_stage(probe.smp, RM_STAGE_SINR);
             h_info[0] = 0u;
             RM_HIP(rm::launch_csma_count(c->stream, nodes_dev(c), m, cs, h_ticks, k.ticks.p, grid));
@@ -466,9 +463,7 @@ int rm_csma_carry_collect_device(rm_context *c, int32_t n_ticks, const int32_t *
     cc.h_count = h_count;
     cc.cap = (long long)n_out;
     {
-        const uint64_t tick_index = c->tick_index; // (profiling, as the gate: the ticks' sampling does not move on)
-        ProbeScope probe(c);
-        c->tick_index = tick_index;
+        CallProbe probe(c);
         sample_stage(probe.smp, RM_STAGE_SINR);
         RM_HIP(rm::launch_csma_collect(c->stream, cc));
     }

@@ -67,10 +67,7 @@ int energy_launch(rm_context *c, int64_t time_us, const int32_t *nodes, int32_t 
     ed.inv = float(rm::kEdG) / (2.0f * ed.half);
     rm::ModelDev m = model_dev(c);
     if (c->f32_slack > 0.05) m.shadow_tbl = nullptr; // (as the sweep: the link-hash table goes with the fp32 filter of a small frame)
-    // profiling (rm_profile_kernels names the path that ran); a query does not move the ticks' sampling on
-    const uint64_t tick_index = c->tick_index;
-    ProbeScope probe(c);
-    c->tick_index = tick_index;
+    CallProbe probe(c); // (rm_profile_kernels names the path that ran)
     sample_stage(probe.smp, RM_STAGE_SINR);
     if (gated)
         RM_HIP(rm::launch_cca_gate(c->stream, nodes_dev(c), m, c->d_air.p + c->air_head, int(n_win), time_us, ed, grid, nodes, n, cca_threshold,

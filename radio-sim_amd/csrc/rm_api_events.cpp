@@ -261,11 +261,7 @@ int rm_events_process(rm_context *c, int64_t time_us, rm_delivery_view *out)
     RM_HIP(hipSetDevice(c->device));
     RM_TRY(ev_ensure_nodes(c));
     ev_touch(c); // (a batch evaluated before this drain can no longer be handed over: its tick 0 would come after it)
-    // profiling (rm_profile_kernels names the append's form: on its own, or in the drain's first launch); a drain does not move
-    // the ticks' sampling on
-    const uint64_t tick_index = c->tick_index;
-    ProbeScope probe(c);
-    c->tick_index = tick_index;
+    CallProbe probe(c); // (rm_profile_kernels names the append's form: on its own, or in the drain's first launch)
     const rm::EvOut o = ev_out(c);
     const uint32_t seq = ++c->ev.seq;
     // (the ring window the drain looks at: at most the packets numbered since the oldest pending one of the last drain)
@@ -472,9 +468,7 @@ int rm_node_info(rm_context *c, const int32_t *nodes, int32_t n, double *rssi, i
     if (n == 0) return RM_OK;
     if (!nodes && n > c->n) return fail(RM_ERR_INVALID, "more nodes than the table holds");
     RM_HIP(hipSetDevice(c->device));
-    const uint64_t tick_index = c->tick_index; // (profiling, as in rm_events_process: the append that runs on its own is named)
-    ProbeScope probe(c);
-    c->tick_index = tick_index;
+    CallProbe probe(c); // (the append that runs on its own is named)
     RM_TRY(ev_flush_append(c)); // (an append left for the next drain runs with the state it was planned with, before anything reads or resets it)
     RM_TRY(ev_ensure_nodes(c));
     rm_context::Events &v = c->ev;

@@ -3,6 +3,7 @@
 //
 // The table belongs to the context.  No evaluating call reads or writes it: the advance reads a FINISHED result slot through the
 // unicast query's descriptor (uc_describe) and under its state rules (uc_check_state).  Every check comes before the first launch.
+// What a relay feature's calls have in common -- rm_context::Relay and the relay_* helpers over it -- is at the end of rm_host.hpp.
 #include "rm_host.hpp"
 #include "rm_math.hpp"
 
@@ -10,42 +11,18 @@ using namespace rmh;
 
 namespace rmh {
 
+static const char *const kFloodOff = "dissemination floods are off: rm_flood_enable comes first";
+
+// what the feature keeps beside rm_context::Relay
 static void flood_free(rm_context *c)
 {
     rm_context::Flood &fl = c->fl;
-    fl.node.release(); fl.totals.release(); fl.claim.release(); fl.pmin.release(); fl.tmin.release(); fl.act.release();
-    fl.unit_count.release(); fl.stage.release();
-    fl.h.release();
+    fl.node.release(); fl.totals.release(); fl.pmin.release(); fl.tmin.release(); fl.act.release();
 }
 
-// off: the table released (a launch in flight still reads it; pointers handed out end here)
-static int flood_off(rm_context *c)
-{
-    if (c->fl.n >= 0 && c->stream) RM_HIP(hipStreamSynchronize(c->stream));
-    c->fl.on = false;
-    c->fl.n = -1;
-    flood_free(c);
-    return RM_OK;
-}
-
-int flood_nodes_changed(rm_context *c)
-{
-    if (c->fl.n < 0 || c->fl.n == c->n) return RM_OK;
-    return flood_off(c);
-}
-
-void flood_release(rm_context *c)
-{
-    c->fl.on = false;
-    c->fl.n = -1;
-    flood_free(c);
-}
-
-static int flood_have(const rm_context *c)
-{
-    if (!c->fl.on) return fail(RM_ERR_STATE, "dissemination floods are off: rm_flood_enable comes first");
-    return RM_OK;
-}
+int flood_nodes_changed(rm_context *c) { return relay_nodes_changed(c, c->fl, flood_free); }
+void flood_release(rm_context *c) { relay_release(c, c->fl, flood_free); }
+static int flood_have(const rm_context *c) { return relay_have(c->fl, kFloodOff); }
 
 static rm::FloodDev flood_dev(const rm_context *c)
 {
@@ -67,49 +44,12 @@ static rm::FloodDev flood_dev(const rm_context *c)
     return f;
 }
 
-// room for n words of the running call.  Enable sizes the block for n_nodes entries: only a list longer than the node table grows
-// it, and that call waits for the stream first (the stream's earlier calls still use the old block)
-static int flood_act(rm_context *c, int32_t n)
+// the source list's three launches, for relay_sources_device / relay_sources
+static auto flood_src_launch(rm_context *c, int64_t time_us, int32_t cap)
 {
-    if (c->fl.act.n >= size_t(std::max(n, 1))) return RM_OK;
-    RM_HIP(hipStreamSynchronize(c->stream));
-    RM_HIP(c->fl.act.ensure(size_t(std::max(n, 1))));
-    return RM_OK;
-}
-
-// a host form's list in device memory: room for `words` words in the staging block
-static int flood_stage(rm_context *c, size_t words)
-{
-    if (c->fl.stage.n >= std::max<size_t>(words, 1)) return RM_OK;
-    RM_HIP(hipStreamSynchronize(c->stream));
-    RM_HIP(c->fl.stage.ensure(std::max<size_t>(words, 1)));
-    return RM_OK;
-}
-
-static int flood_check_host_list(const rm_context *c, const int32_t *list, int32_t n, const char *what)
-{
-    for (int32_t k = 0; k < n; ++k)
-        if (list[k] >= c->fl.n) return fail(RM_ERR_INVALID, std::string("an entry of the host ") + what + " list is not below the node count");
-    return RM_OK;
-}
-
-// Profiling names the kernels (rm_profile_kernels) without moving the ticks' sampling: a call of the feature is no tick, so the
-// launch-sequence count that begin_sample moved is put back (the forwarding queues' FwdProbe, rm_api_fwd.cpp, says why)
-struct FloodProbe {
-    rm_context *c;
-    uint64_t tick_index;
-    ProbeScope probe;
-    explicit FloodProbe(rm_context *ctx) : c(ctx), tick_index(ctx->tick_index), probe(ctx) { c->tick_index = tick_index; }
-};
-
-// what both advance forms check, in this order, before anything else happens
-static int flood_check_advance(rm_context *c, int32_t slot, int32_t n_cand)
-{
-    if (!c || n_cand < 0) return fail(RM_ERR_INVALID, "bad arguments");
-    RM_TRY(flood_have(c));
-    RM_TRY(uc_check_state(c));
-    if (slot < 0 || slot >= c->uc.slots) return fail(RM_ERR_INVALID, "slot outside the slots of the last evaluating call");
-    return RM_OK;
+    return [=](int units, int chunk, int32_t *dev_src, int32_t *dev_count) {
+        return rm::launch_flood_sources(c->stream, flood_dev(c), time_us, cap, units, chunk, c->fl.unit_count.p, dev_src, dev_count);
+    };
 }
 
 } // namespace rmh
@@ -153,7 +93,7 @@ int rm_flood_enable(rm_context *c, const rm_flood_params *p)
     RM_TRY(graphs_refuse(c, "the extensions' tables are not set on it"));
     if (c->n < 1) return fail(RM_ERR_STATE, "no nodes: rm_nodes_upload comes first");
     RM_HIP(hipSetDevice(c->device));
-    RM_TRY(flood_off(c)); // (another enable: everything anew)
+    RM_TRY(relay_off(c, c->fl, flood_free)); // (another enable: everything anew)
     rm_context::Flood &fl = c->fl;
     const size_t n = size_t(c->n);
     int units = 0, chunk = 0;
@@ -182,7 +122,7 @@ int rm_flood_disable(rm_context *c)
 {
     if (!c) return fail(RM_ERR_INVALID, "ctx is NULL");
     RM_HIP(hipSetDevice(c->device));
-    return flood_off(c);
+    return relay_off(c, c->fl, flood_free);
 }
 
 int rm_flood_enabled(const rm_context *c) { return (c && c->fl.on) ? 1 : 0; }
@@ -210,8 +150,8 @@ int rm_flood_seed_device(rm_context *c, const int32_t *dev_nodes, int32_t n, int
     RM_TRY(flood_have(c));
     if (n == 0) return RM_OK;
     RM_HIP(hipSetDevice(c->device));
-    RM_TRY(flood_act(c, n));
-    FloodProbe probe(c);
+    RM_TRY(relay_room(c, c->fl.act, size_t(n)));
+    CallProbe probe(c);
     RM_HIP(rm::launch_flood_seed(c->stream, flood_dev(c), dev_nodes, n, time_us));
     return RM_OK;
 }
@@ -220,69 +160,45 @@ int rm_flood_seed(rm_context *c, const int32_t *nodes, int32_t n, int64_t time_u
 {
     if (!c || n < 0 || (n > 0 && !nodes) || time_us < 0) return fail(RM_ERR_INVALID, "bad arguments");
     RM_TRY(flood_have(c));
-    RM_TRY(flood_check_host_list(c, nodes, n, "seed"));
+    RM_TRY(relay_check_host_list(c->fl, nodes, n, "seed"));
     if (n == 0) return RM_OK;
-    RM_HIP(hipSetDevice(c->device));
-    RM_TRY(flood_stage(c, size_t(n)));
-    RM_HIP(hipMemcpyAsync(c->fl.stage.p, nodes, size_t(n) * 4, hipMemcpyHostToDevice, c->stream));
-    RM_HIP(hipStreamSynchronize(c->stream));
+    RM_TRY(relay_stage_list(c, c->fl, nodes, n));
     return rm_flood_seed_device(c, c->fl.stage.p, n, time_us);
 }
 
 int rm_flood_sources_device(rm_context *c, int64_t time_us, int32_t cap, int32_t *dev_src, int32_t *dev_count)
 {
-    if (!c || !dev_src || !dev_count || time_us < 0) return fail(RM_ERR_INVALID, "bad arguments");
-    if (cap < 1) return fail(RM_ERR_INVALID, "cap < 1");
-    RM_TRY(flood_have(c));
-    RM_HIP(hipSetDevice(c->device));
-    int units = 0, chunk = 0;
-    rm::traffic_geometry(c->fl.n, &units, &chunk);
-    if (c->fl.unit_count.n < size_t(units)) return fail(RM_ERR_STATE, "internal: the units' counts were sized for another node count");
-    FloodProbe probe(c);
-    RM_HIP(rm::launch_flood_sources(c->stream, flood_dev(c), time_us, cap, units, chunk, c->fl.unit_count.p, dev_src, dev_count));
-    return RM_OK;
+    if (!c) return fail(RM_ERR_INVALID, "bad arguments");
+    return relay_sources_device(c, c->fl, kFloodOff, time_us, cap, dev_src, dev_count, flood_src_launch(c, time_us, cap));
 }
 
 int rm_flood_sources(rm_context *c, int64_t time_us, int32_t cap, int32_t *src, int32_t *count)
 {
-    if (!c || !src || !count || time_us < 0) return fail(RM_ERR_INVALID, "bad arguments");
-    if (cap < 1) return fail(RM_ERR_INVALID, "cap < 1");
-    RM_TRY(flood_have(c));
-    RM_HIP(hipSetDevice(c->device));
-    RM_TRY(flood_stage(c, size_t(cap) + 1));
-    int32_t *d = c->fl.stage.p;
-    RM_TRY(rm_flood_sources_device(c, time_us, cap, d, d + cap));
-    RM_HIP(hipMemcpyAsync(src, d, size_t(cap) * 4, hipMemcpyDeviceToHost, c->stream));
-    RM_HIP(hipMemcpyAsync(count, d + cap, 4, hipMemcpyDeviceToHost, c->stream));
-    RM_HIP(hipStreamSynchronize(c->stream));
-    return RM_OK;
+    if (!c) return fail(RM_ERR_INVALID, "bad arguments");
+    return relay_sources(c, c->fl, kFloodOff, time_us, cap, src, count, flood_src_launch(c, time_us, cap));
 }
 
 int rm_flood_advance_device(rm_context *c, int32_t slot, const int32_t *dev_cand, int32_t n_cand)
 {
-    RM_TRY(flood_check_advance(c, slot, n_cand));
-    RM_HIP(hipSetDevice(c->device));
+    if (!c) return fail(RM_ERR_INVALID, "bad arguments");
     rm::UcSlot d;
-    RM_TRY(uc_describe(c, *slot_of(c, slot), &d));
-    const int32_t P = dev_cand ? std::min(n_cand, d.n_new) : d.n_new;
-    RM_TRY(flood_act(c, P));
-    FloodProbe probe(c);
+    int32_t P = 0;
+    RM_TRY(relay_advance_begin(c, c->fl, kFloodOff, slot, dev_cand, n_cand, &d, &P));
+    RM_TRY(relay_room(c, c->fl.act, size_t(P)));
+    CallProbe probe(c);
     RM_HIP(rm::launch_flood_advance(c->stream, flood_dev(c), d, dev_cand, P));
     return RM_OK;
 }
 
 int rm_flood_advance(rm_context *c, int32_t slot, const int32_t *cand, int32_t n_cand)
 {
-    RM_TRY(flood_check_advance(c, slot, n_cand));
-    if (!cand) return rm_flood_advance_device(c, slot, nullptr, n_cand);
-    RM_TRY(flood_check_host_list(c, cand, n_cand, "candidate"));
-    RM_HIP(hipSetDevice(c->device));
-    RM_TRY(flood_stage(c, size_t(n_cand)));
-    if (n_cand > 0) {
-        RM_HIP(hipMemcpyAsync(c->fl.stage.p, cand, size_t(n_cand) * 4, hipMemcpyHostToDevice, c->stream));
-        RM_HIP(hipStreamSynchronize(c->stream));
+    if (!c) return fail(RM_ERR_INVALID, "bad arguments");
+    RM_TRY(relay_check_advance(c, c->fl, kFloodOff, slot, n_cand));
+    if (cand) {
+        RM_TRY(relay_check_host_list(c->fl, cand, n_cand, "candidate")); // (the forwarding queues' advance has no such check)
+        RM_TRY(relay_stage_list(c, c->fl, cand, n_cand));
     }
-    return rm_flood_advance_device(c, slot, c->fl.stage.p, n_cand);
+    return rm_flood_advance_device(c, slot, cand ? c->fl.stage.p : nullptr, n_cand);
 }
 
 int rm_flood_read(rm_context *c, const int32_t *nodes, int32_t n, rm_flood_node *out, rm_flood_totals *totals)
@@ -310,7 +226,7 @@ int rm_flood_tree_device(rm_context *c, int32_t *dev_parent, int32_t *dev_hop)
     if (!c || !dev_parent) return fail(RM_ERR_INVALID, "ctx or dev_parent is NULL");
     RM_TRY(flood_have(c));
     RM_HIP(hipSetDevice(c->device));
-    FloodProbe probe(c);
+    CallProbe probe(c);
     RM_HIP(rm::launch_flood_tree(c->stream, flood_dev(c), dev_parent, dev_hop));
     return RM_OK;
 }

@@ -3,6 +3,7 @@
 //
 // The tables belong to the context.  No evaluating call reads or writes them: the advance reads a FINISHED result slot through the
 // unicast query's descriptor (uc_describe) and under its state rules (uc_check_state).  Every check comes before the first launch.
+// What a relay feature's calls have in common -- rm_context::Relay and the relay_* helpers over it -- is at the end of rm_host.hpp.
 #include "rm_host.hpp"
 #include "rm_math.hpp"
 
@@ -10,42 +11,18 @@ using namespace rmh;
 
 namespace rmh {
 
+static const char *const kFwdOff = "forwarding queues are off: rm_fwd_enable comes first";
+
+// what the feature keeps beside rm_context::Relay
 static void fwd_free(rm_context *c)
 {
     rm_context::Fwd &fw = c->fw;
-    fw.node.release(); fw.pk.release(); fw.totals.release(); fw.claim.release(); fw.acc.release(); fw.pushed.release();
-    fw.unit_count.release(); fw.stage.release(); fw.act.release();
-    fw.h.release();
+    fw.node.release(); fw.pk.release(); fw.totals.release(); fw.acc.release(); fw.pushed.release(); fw.act.release();
 }
 
-// off: the tables released (a launch in flight still reads them; pointers handed out end here)
-static int fwd_off(rm_context *c)
-{
-    if (c->fw.n >= 0 && c->stream) RM_HIP(hipStreamSynchronize(c->stream));
-    c->fw.on = false;
-    c->fw.n = -1;
-    fwd_free(c);
-    return RM_OK;
-}
-
-int fwd_nodes_changed(rm_context *c)
-{
-    if (c->fw.n < 0 || c->fw.n == c->n) return RM_OK;
-    return fwd_off(c);
-}
-
-void fwd_release(rm_context *c)
-{
-    c->fw.on = false;
-    c->fw.n = -1;
-    fwd_free(c);
-}
-
-static int fwd_have(const rm_context *c)
-{
-    if (!c->fw.on) return fail(RM_ERR_STATE, "forwarding queues are off: rm_fwd_enable comes first");
-    return RM_OK;
-}
+int fwd_nodes_changed(rm_context *c) { return relay_nodes_changed(c, c->fw, fwd_free); }
+void fwd_release(rm_context *c) { relay_release(c, c->fw, fwd_free); }
+static int fwd_have(const rm_context *c) { return relay_have(c->fw, kFwdOff); }
 
 static rm::FwdDev fwd_dev(const rm_context *c)
 {
@@ -69,50 +46,12 @@ static rm::FwdDev fwd_dev(const rm_context *c)
     return f;
 }
 
-// room for n records of the running call.  Enable sizes the block for n_nodes records: only a list longer than the node table
-// grows it, and that call waits for the stream first (the stream's earlier calls still use the old block)
-static int fwd_act(rm_context *c, int32_t n)
+// the source list's three launches, for relay_sources_device / relay_sources
+static auto fwd_src_launch(rm_context *c, int64_t time_us, int32_t cap)
 {
-    if (c->fw.act.n >= size_t(std::max(n, 1))) return RM_OK;
-    RM_HIP(hipStreamSynchronize(c->stream));
-    RM_HIP(c->fw.act.ensure(size_t(std::max(n, 1))));
-    return RM_OK;
-}
-
-// a host form's lists in device memory: room for `words` words in the staging block (the stream's earlier calls still use the old one)
-static int fwd_stage(rm_context *c, size_t words)
-{
-    if (c->fw.stage.n >= std::max<size_t>(words, 1)) return RM_OK;
-    RM_HIP(hipStreamSynchronize(c->stream));
-    RM_HIP(c->fw.stage.ensure(std::max<size_t>(words, 1)));
-    return RM_OK;
-}
-
-static int fwd_check_host_list(const rm_context *c, const int32_t *list, int32_t n, const char *what)
-{
-    for (int32_t k = 0; k < n; ++k)
-        if (list[k] >= c->fw.n) return fail(RM_ERR_INVALID, std::string("an entry of the host ") + what + " list is not below the node count");
-    return RM_OK;
-}
-
-// Profiling names the kernels (rm_profile_kernels), as the traffic generator's are.  begin_sample (rm_api_plan.cpp) moves one
-// piece of state that belongs to the ticks: it counts the launch sequence in c->tick_index, which decides which sequences are
-// sampled under rm_profile_enable(every_n).  (When it does sample it also takes an entry of c->ev_pool and routes this thread's
-// kernel probes to it; ProbeScope's destructor unroutes, drain_profile returns the entry.)  A call of the feature is no tick, so the
-// count is put back: it is sampled iff the tick after it would be, and the ticks' sampling is as without the feature
-struct FwdProbe {
-    rm_context *c;
-    uint64_t tick_index;
-    ProbeScope probe;
-    explicit FwdProbe(rm_context *ctx) : c(ctx), tick_index(ctx->tick_index), probe(ctx) { c->tick_index = tick_index; }
-};
-
-static bool fwd_packet_before(const rm_fwd_packet &a, const rm_fwd_packet &b)
-{
-    if (a.enq_us != b.enq_us) return a.enq_us < b.enq_us;
-    if (a.birth_us != b.birth_us) return a.birth_us < b.birth_us;
-    if (a.origin != b.origin) return a.origin < b.origin;
-    return a.hops < b.hops;
+    return [=](int units, int chunk, int32_t *dev_src, int32_t *dev_count) {
+        return rm::launch_fwd_sources(c->stream, fwd_dev(c), time_us, cap, units, chunk, c->fw.unit_count.p, dev_src, dev_count);
+    };
 }
 
 } // namespace rmh
@@ -157,7 +96,7 @@ int rm_fwd_enable(rm_context *c, const rm_fwd_params *p)
     RM_TRY(graphs_refuse(c, "the extensions' tables are not set on it"));
     if (c->n < 1) return fail(RM_ERR_STATE, "no nodes: rm_nodes_upload comes first");
     RM_HIP(hipSetDevice(c->device));
-    RM_TRY(fwd_off(c)); // (another enable: everything anew)
+    RM_TRY(relay_off(c, c->fw, fwd_free)); // (another enable: everything anew)
     rm_context::Fwd &fw = c->fw;
     const size_t n = size_t(std::max(c->n, 1));
     hipError_t e = fw.node.ensure(n);
@@ -188,7 +127,7 @@ int rm_fwd_disable(rm_context *c)
 {
     if (!c) return fail(RM_ERR_INVALID, "ctx is NULL");
     RM_HIP(hipSetDevice(c->device));
-    return fwd_off(c);
+    return relay_off(c, c->fw, fwd_free);
 }
 
 int rm_fwd_enabled(const rm_context *c) { return (c && c->fw.on) ? 1 : 0; }
@@ -216,7 +155,7 @@ int rm_fwd_set_next_device(rm_context *c, const int32_t *dev_parent, const int32
     if (!c || !dev_parent || n_roots < 0 || (n_roots > 0 && !dev_roots) || time_us < 0) return fail(RM_ERR_INVALID, "bad arguments");
     RM_TRY(fwd_have(c));
     RM_HIP(hipSetDevice(c->device));
-    FwdProbe probe(c);
+    CallProbe probe(c);
     RM_HIP(rm::launch_fwd_set_next(c->stream, fwd_dev(c), dev_parent, dev_roots, n_roots, time_us));
     return RM_OK;
 }
@@ -225,10 +164,10 @@ int rm_fwd_set_next(rm_context *c, const int32_t *parent, const int32_t *roots, 
 {
     if (!c || !parent || n_roots < 0 || (n_roots > 0 && !roots) || time_us < 0) return fail(RM_ERR_INVALID, "bad arguments");
     RM_TRY(fwd_have(c));
-    RM_TRY(fwd_check_host_list(c, roots, n_roots, "roots"));
+    RM_TRY(relay_check_host_list(c->fw, roots, n_roots, "roots"));
     RM_HIP(hipSetDevice(c->device));
     const size_t n = size_t(c->fw.n);
-    RM_TRY(fwd_stage(c, n + size_t(n_roots)));
+    RM_TRY(relay_room(c, c->fw.stage, n + size_t(n_roots)));
     int32_t *d = c->fw.stage.p;
     if (n > 0) RM_HIP(hipMemcpyAsync(d, parent, n * 4, hipMemcpyHostToDevice, c->stream));
     if (n_roots > 0) RM_HIP(hipMemcpyAsync(d + n, roots, size_t(n_roots) * 4, hipMemcpyHostToDevice, c->stream));
@@ -242,8 +181,8 @@ int rm_fwd_inject_device(rm_context *c, const int32_t *dev_src, int32_t n, int64
     RM_TRY(fwd_have(c));
     if (n == 0) return RM_OK;
     RM_HIP(hipSetDevice(c->device));
-    RM_TRY(fwd_act(c, n));
-    FwdProbe probe(c);
+    RM_TRY(relay_room(c, c->fw.act, size_t(n)));
+    CallProbe probe(c);
     RM_HIP(rm::launch_fwd_inject(c->stream, fwd_dev(c), dev_src, n, time_us));
     return RM_OK;
 }
@@ -252,74 +191,43 @@ int rm_fwd_inject(rm_context *c, const int32_t *src, int32_t n, int64_t time_us)
 {
     if (!c || n < 0 || (n > 0 && !src) || time_us < 0) return fail(RM_ERR_INVALID, "bad arguments");
     RM_TRY(fwd_have(c));
-    RM_TRY(fwd_check_host_list(c, src, n, "source"));
+    RM_TRY(relay_check_host_list(c->fw, src, n, "source"));
     if (n == 0) return RM_OK;
-    RM_HIP(hipSetDevice(c->device));
-    RM_TRY(fwd_stage(c, size_t(n)));
-    RM_HIP(hipMemcpyAsync(c->fw.stage.p, src, size_t(n) * 4, hipMemcpyHostToDevice, c->stream));
-    RM_HIP(hipStreamSynchronize(c->stream));
+    RM_TRY(relay_stage_list(c, c->fw, src, n));
     return rm_fwd_inject_device(c, c->fw.stage.p, n, time_us);
 }
 
 int rm_fwd_sources_device(rm_context *c, int64_t time_us, int32_t cap, int32_t *dev_src, int32_t *dev_count)
 {
-    if (!c || !dev_src || !dev_count || time_us < 0) return fail(RM_ERR_INVALID, "bad arguments");
-    if (cap < 1) return fail(RM_ERR_INVALID, "cap < 1");
-    RM_TRY(fwd_have(c));
-    RM_HIP(hipSetDevice(c->device));
-    int units = 0, chunk = 0;
-    rm::traffic_geometry(c->fw.n, &units, &chunk);
-    if (c->fw.unit_count.n < size_t(units)) return fail(RM_ERR_STATE, "internal: the units' counts were sized for another node count");
-    FwdProbe probe(c);
-    RM_HIP(rm::launch_fwd_sources(c->stream, fwd_dev(c), time_us, cap, units, chunk, c->fw.unit_count.p, dev_src, dev_count));
-    return RM_OK;
+    if (!c) return fail(RM_ERR_INVALID, "bad arguments");
+    return relay_sources_device(c, c->fw, kFwdOff, time_us, cap, dev_src, dev_count, fwd_src_launch(c, time_us, cap));
 }
 
 int rm_fwd_sources(rm_context *c, int64_t time_us, int32_t cap, int32_t *src, int32_t *count)
 {
-    if (!c || !src || !count || time_us < 0) return fail(RM_ERR_INVALID, "bad arguments");
-    if (cap < 1) return fail(RM_ERR_INVALID, "cap < 1");
-    RM_TRY(fwd_have(c));
-    RM_HIP(hipSetDevice(c->device));
-    RM_TRY(fwd_stage(c, size_t(cap) + 1));
-    int32_t *d = c->fw.stage.p;
-    RM_TRY(rm_fwd_sources_device(c, time_us, cap, d, d + cap));
-    RM_HIP(hipMemcpyAsync(src, d, size_t(cap) * 4, hipMemcpyDeviceToHost, c->stream));
-    RM_HIP(hipMemcpyAsync(count, d + cap, 4, hipMemcpyDeviceToHost, c->stream));
-    RM_HIP(hipStreamSynchronize(c->stream));
-    return RM_OK;
+    if (!c) return fail(RM_ERR_INVALID, "bad arguments");
+    return relay_sources(c, c->fw, kFwdOff, time_us, cap, src, count, fwd_src_launch(c, time_us, cap));
 }
 
 int rm_fwd_advance_device(rm_context *c, int32_t slot, const int32_t *dev_cand, int32_t n_cand)
 {
-    if (!c || n_cand < 0) return fail(RM_ERR_INVALID, "bad arguments");
-    RM_TRY(fwd_have(c));
-    RM_TRY(uc_check_state(c));
-    if (slot < 0 || slot >= c->uc.slots) return fail(RM_ERR_INVALID, "slot outside the slots of the last evaluating call");
-    RM_HIP(hipSetDevice(c->device));
+    if (!c) return fail(RM_ERR_INVALID, "bad arguments");
     rm::UcSlot d;
-    RM_TRY(uc_describe(c, *slot_of(c, slot), &d));
-    const int32_t P = dev_cand ? std::min(n_cand, d.n_new) : d.n_new;
-    RM_TRY(fwd_act(c, P));
-    FwdProbe probe(c);
+    int32_t P = 0;
+    RM_TRY(relay_advance_begin(c, c->fw, kFwdOff, slot, dev_cand, n_cand, &d, &P));
+    RM_TRY(relay_room(c, c->fw.act, size_t(P)));
+    CallProbe probe(c);
     RM_HIP(rm::launch_fwd_advance(c->stream, fwd_dev(c), d, dev_cand, P));
     return RM_OK;
 }
 
 int rm_fwd_advance(rm_context *c, int32_t slot, const int32_t *cand, int32_t n_cand)
 {
-    if (!c || n_cand < 0) return fail(RM_ERR_INVALID, "bad arguments");
-    RM_TRY(fwd_have(c));
-    RM_TRY(uc_check_state(c));
-    if (slot < 0 || slot >= c->uc.slots) return fail(RM_ERR_INVALID, "slot outside the slots of the last evaluating call");
-    if (!cand) return rm_fwd_advance_device(c, slot, nullptr, n_cand);
-    RM_HIP(hipSetDevice(c->device));
-    RM_TRY(fwd_stage(c, size_t(n_cand)));
-    if (n_cand > 0) {
-        RM_HIP(hipMemcpyAsync(c->fw.stage.p, cand, size_t(n_cand) * 4, hipMemcpyHostToDevice, c->stream));
-        RM_HIP(hipStreamSynchronize(c->stream));
-    }
-    return rm_fwd_advance_device(c, slot, c->fw.stage.p, n_cand);
+    if (!c) return fail(RM_ERR_INVALID, "bad arguments");
+    RM_TRY(relay_check_advance(c, c->fw, kFwdOff, slot, n_cand));
+    // (no bound check of the host list, unlike the flood's: k_fwd_adv_claim treats a candidate outside the table as foreign)
+    if (cand) RM_TRY(relay_stage_list(c, c->fw, cand, n_cand));
+    return rm_fwd_advance_device(c, slot, cand ? c->fw.stage.p : nullptr, n_cand);
 }
 
 int rm_fwd_read(rm_context *c, const int32_t *nodes, int32_t n, rm_fwd_node *out, rm_fwd_totals *totals)
@@ -351,7 +259,7 @@ int rm_fwd_queue_read(rm_context *c, const int32_t *nodes, int32_t n, rm_fwd_pac
         int m = 0;
         for (int s = 0; s < Q; ++s)
             if ((rows[size_t(k)].slot_mask >> s) & 1u) q[m++] = q[s];
-        std::sort(q, q + m, fwd_packet_before);
+        std::sort(q, q + m, rm::fwd_packet_order);
         for (int s = m; s < Q; ++s) q[s] = rm_fwd_packet{};
         len[k] = m;
     }

@@ -72,10 +72,7 @@ static int hops_run(rm_context *c, int32_t direction, double min_rssi, const int
         const bool scan = !c->rx_sorted || c->f32_slack > 0.05 || !(c->params.ld_exponent > 0.0);
         const rm::NodesDev nd = nodes_dev(c);
         const rm::ModelDev m = model_dev(c);
-        // profiling (rm_profile_kernels names the path that ran); a query does not move the ticks' sampling on
-        const uint64_t tick_index = c->tick_index;
-        ProbeScope probe(c);
-        c->tick_index = tick_index;
+        CallProbe probe(c); // (rm_profile_kernels names the path that ran)
         // the tail after the launches enqueued so far: one copy into the pinned word, one wait
         auto tail = [&](int &count) -> int {
             RM_HIP(hipMemcpyAsync(hp.h_tail, h.tail, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));

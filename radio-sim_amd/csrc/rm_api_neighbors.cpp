@@ -64,10 +64,7 @@ static int neighbors_launch(rm_context *c, int32_t direction, int32_t K, const i
     // the boxes bound nothing on a table that is not sorted, in an fp32 frame beyond the plan's slack (LaunchCfg::f64_filter) and
     // for a medium without a finite cut-off: every pair is evaluated then
     const bool scan = !c->rx_sorted || c->f32_slack > 0.05 || !(c->params.ld_exponent > 0.0);
-    // profiling (rm_profile_kernels names the path that ran); a query does not move the ticks' sampling on
-    const uint64_t tick_index = c->tick_index;
-    ProbeScope probe(c);
-    c->tick_index = tick_index;
+    CallProbe probe(c); // (rm_profile_kernels names the path that ran)
     RM_HIP(rm::launch_nb_query(c->stream, nodes_dev(c), model_dev(c), q, direction, scan));
     return RM_OK;
 }
@@ -197,9 +194,7 @@ int rm_linkstats_watch_device(rm_context *c, const int32_t *dev_nodes, int32_t n
     RM_HIP(hipStreamSynchronize(c->stream)); // (the flag word is the host's to write now)
     *lk.h_bad = 0u;
     {
-        const uint64_t tick_index = c->tick_index;
-        ProbeScope probe(c);
-        c->tick_index = tick_index;
+        CallProbe probe(c);
         RM_HIP(rm::launch_nb_watch_check(c->stream, dev_nodes, n, dev_peers, lk.n, lk.K, lk.mark.p, lk.stamp, lk.h_bad));
     }
     RM_HIP(hipStreamSynchronize(c->stream));

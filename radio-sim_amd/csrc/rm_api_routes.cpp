@@ -111,10 +111,7 @@ static int routes_run(rm_context *c, const rm_routes_params &p, const int32_t *r
         // the whole-table scan exactly where the neighbour query takes it (rm_api_neighbors.cpp)
         const bool scan = !c->rx_sorted || c->f32_slack > 0.05 || !(c->params.ld_exponent > 0.0);
         const rm::NodesDev nd = nodes_dev(c);
-        // profiling (rm_profile_kernels names the path that ran); a query does not move the ticks' sampling on
-        const uint64_t tick_index = c->tick_index;
-        ProbeScope probe(c);
-        c->tick_index = tick_index;
+        CallProbe probe(c); // (rm_profile_kernels names the path that ran)
         // a queue's tail after the launches enqueued so far: one copy into the pinned word, one wait
         auto tail = [&](int which, int &count) -> int {
             RM_HIP(hipMemcpyAsync(rt.h_words, r.tail + which, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));

@@ -199,10 +199,7 @@ int rm_traffic_generate_device(rm_context *c, uint64_t seed, int32_t n_ticks, co
     g.out_src = dev_src;
     g.out_count = dev_count;
     g.out_totals = dev_totals;
-    // profiling (rm_profile_kernels names the three kernels); a generate does not move the ticks' sampling on
-    const uint64_t tick_index = c->tick_index;
-    ProbeScope probe(c);
-    c->tick_index = tick_index;
+    CallProbe probe(c); // (rm_profile_kernels names the three kernels)
     RM_HIP(rm::launch_traffic_generate(c->stream, g));
     return RM_OK;
 }

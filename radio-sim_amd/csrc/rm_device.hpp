@@ -897,4 +897,97 @@ RM_D int uc_find(const UcSlot &s, int p, int w, int n_nodes, int32_t &link)
     return status;
 }
 
+// ---- what the kernels of the node-table features share: the traffic generator's scan (rm_traffic.hip) and all of the following
+// for the relay features, which are driven by a finished result slot (rm_fwd.hip, rm_flood.hip)
+using u64 = unsigned long long;
+constexpr int kRelayThreads = 256;
+inline int relay_blocks(int n) { return std::max(1, (n + kRelayThreads - 1) / kRelayThreads); } // (host: workgroups for n lanes)
+
+RM_D u64 *relay_w(uint64_t *p) { return reinterpret_cast<u64 *>(p); }
+template <typename Dev> RM_D bool relay_in(const Dev &f, int j) { return j >= 0 && j < f.n_nodes; }
+RM_D bool relay_slot_lost(const UcSlot &s) { return s.out_count && uc_lost(s); }
+
+// the wave's share of a total -- one address for everybody -- added once
+RM_D void relay_total(uint64_t *word, u64 v)
+{
+    v = wave_sum_u64(v);
+    if ((threadIdx.x & 63u) == 0u && v != 0ull) atomicAdd(relay_w(word), v);
+}
+RM_D void relay_total_max(uint64_t *word, u64 v)
+{
+    for (int d = 32; d > 0; d >>= 1) {
+        const u64 o = __shfl_xor(v, d);
+        v = o > v ? o : v;
+    }
+    if ((threadIdx.x & 63u) == 0u && v != 0ull) atomicMax(relay_w(word), v);
+}
+
+// The scan of an ordered stream compaction, one 256-thread workgroup per list: the first wave turns the units' counts -- col[u * W],
+// a column of unit_count [units][W] -- into exclusive prefixes in place, 64 units at a time, and writes their sum to *out_count;
+// then all four waves pad the list behind min(sum, cap) with -1
+RM_D void units_scan(const int units, const int W, const int cap, int32_t *col, int32_t *row, int32_t *out_count)
+{
+    __shared__ int32_t s_total;
+    if (threadIdx.x < 64) {
+        const int lane = threadIdx.x;
+        uint32_t carry = 0;
+        for (int u0 = 0; u0 < units; u0 += 64) {
+            const int u = u0 + lane;
+            const uint32_t v = u < units ? uint32_t(col[size_t(u) * W]) : 0u;
+            const uint32_t inc = wave_inclusive_scan(v, lane);
+            if (u < units) col[size_t(u) * W] = int32_t(carry + inc - v);
+            carry += __shfl(inc, 63);
+        }
+        if (lane == 0) {
+            s_total = int32_t(carry);
+            *out_count = int32_t(carry);
+        }
+    }
+    __syncthreads();
+    for (int p = min(s_total, cap) + int(threadIdx.x); p < cap; p += 256) row[p] = -1;
+}
+
+// The walk of a single source list, before (count) and behind (WRITE) that scan: the node table cut into units of `chunk`
+// consecutive nodes, one wave per unit, one lane per node, 64 nodes a round.  member(node) -- called exactly once per node of
+// the table and pass -- says whether the node is in the list.  count: unit_count[unit] = the unit's members; WRITE: the members
+// go to out_src in ascending order from the unit's prefix on, clipped at cap
+template <bool WRITE, typename Member>
+RM_D void source_walk(const int n_nodes, const int cap, const int chunk, int32_t *unit_count, int32_t *out_src, Member member)
+{
+    const int lane = threadIdx.x;
+    const int unit = blockIdx.x;
+    const int first = unit * chunk;
+    const int last = min(first + chunk, n_nodes);
+    int run = WRITE ? unit_count[unit] : 0; // WRITE: where the unit's next source goes; else its sources so far
+    for (int i0 = first; i0 < last; i0 += 64) {
+        const int node = i0 + lane;
+        const bool hit = node < last && member(node);
+        const uint64_t m = ballot64(hit);
+        if (WRITE) {
+            const int pos = run + int(lane_prefix(m));
+            if (hit && pos < cap) out_src[pos] = node;
+        }
+        run += __popcll(m);
+    }
+    if (!WRITE && lane == 0) unit_count[unit] = run;
+}
+
+// The first launch of an advance, lane p of P: a lost slot is counted once and nothing else happens (kClaimNone, as for p >= P);
+// else the candidate -- cand[p], or the frame's source -- claims its first occurrence by atomicMin of p over claim[j] if it is a
+// participant(j) inside the table, and is -1 (foreign traffic) if not.  The caller stores the answer in its own record of p
+constexpr int32_t kClaimNone = INT32_MIN;
+template <typename Dev, typename Participant>
+RM_D int32_t relay_claim(const Dev &f, const UcSlot &s, const int32_t *cand, const int P, const int p, Participant participant)
+{
+    if (relay_slot_lost(s)) {
+        if (p == 0) atomicAdd(relay_w(&f.totals->skipped_slots), 1ull);
+        return kClaimNone;
+    }
+    if (p >= P) return kClaimNone;
+    const int32_t j = cand ? cand[p] : s.recs[p].src;
+    if (!relay_in(f, j) || !participant(j)) return -1;
+    atomicMin(&f.claim[j], p);
+    return j;
+}
+
 } // namespace rm

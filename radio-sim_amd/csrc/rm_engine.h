@@ -943,8 +943,8 @@ int64_t host_linkstats_q8(double x);
 // (rm_traffic.hip) the traffic generator.  The node table is cut into `units` runs of `chunk`
 // consecutive nodes (traffic_geometry), one wave each; a generate is three launches: the units' sources per window into
 // unit_count [units][n_ticks] and their packets into unit_packets [units]; one workgroup per window turns its column into
-// exclusive prefixes, writes count[b] and pads the row's tail with -1; the units write their nodes behind their prefixes, and the
-// first of them the totals (out_totals may be nullptr).  win: [2 * n_ticks] device words, the n_ticks win_lo then the n_ticks win_hi.
+// exclusive prefixes, writes count[b] and pads the row's tail with -1 (units_scan, rm_device.hpp, which the relay features' source
+// lists below share); the units write their nodes behind their prefixes, and the first of them the totals (out_totals may be nullptr).  win: [2 * n_ticks] device words, the n_ticks win_lo then the n_ticks win_hi.
 struct TrafficGen {
     const rm_traffic_schedule *sched; // [n_nodes], by node index
     int n_nodes;
@@ -1062,7 +1062,9 @@ hipError_t launch_unicast_at(hipStream_t s, const UcSlot *dev_slots, const UcSlo
 
 // (rm_fwd.hip) the forwarding queues.  node / pk / totals are the context's tables; claim
 // ([n_nodes], INT32_MAX at rest), acc and pushed ([n_nodes], 0 at rest) are per-node scratch that every call leaves as it found it;
-// act holds one record per packet number of the running advance or inject (the decisions one launch leaves for the next).
+// act holds one record per packet number of the running advance or inject (the decisions one launch leaves for the next).  What
+// these kernels share with the floods' -- the source list's walk and scan, the advance's claim step, the small relay_* helpers -- is
+// at the end of rm_device.hpp; the queue order is fwd_packet_order of rm_math.hpp.
 struct FwdAct {
     int32_t j, w;      // the candidate (-1: none in the table) and its next hop
     int32_t state;     // kFwd*
@@ -1086,7 +1088,7 @@ hipError_t launch_fwd_init(hipStream_t s, const FwdDev &f, bool keep_next);
 hipError_t launch_fwd_set_next(hipStream_t s, const FwdDev &f, const int32_t *parent, const int32_t *roots, int n_roots, int64_t time_us);
 // act: room for n records
 hipError_t launch_fwd_inject(hipStream_t s, const FwdDev &f, const int32_t *src, int n, int64_t time_us);
-// unit_count: [units] words of scratch, units and chunk from traffic_geometry(n_nodes)
+// source_walk / units_scan / source_walk.  unit_count: [units] words of scratch, units and chunk from traffic_geometry(n_nodes)
 hipError_t launch_fwd_sources(hipStream_t s, const FwdDev &f, int64_t time_us, int cap, int units, int chunk, int32_t *unit_count, int32_t *out_src,
                               int32_t *out_count);
 // packet numbers 0 .. P - 1 of the slot described by `slot` (cand: nullptr or [P]); act: room for P records
@@ -1094,7 +1096,8 @@ hipError_t launch_fwd_advance(hipStream_t s, const FwdDev &f, const UcSlot &slot
 
 // (rm_flood.hip) the dissemination floods.  node / totals are the context's table; claim and
 // pmin ([n_nodes], INT32_MAX at rest) and tmin ([n_nodes], INT64_MAX at rest) are per-node scratch that every call leaves as it found
-// it; act holds one word per entry of the running advance or seed list (the candidate in the table with the data, or -1).
+// it; act holds one word per entry of the running advance or seed list (the candidate in the table with the data, or -1).  The
+// shared pieces: as the forwarding queues above.
 struct FloodDev {
     rm_flood_node *node;
     rm_flood_totals *totals;
@@ -1110,7 +1113,7 @@ struct FloodDev {
 hipError_t launch_flood_init(hipStream_t s, const FloodDev &f);
 // act: room for n words
 hipError_t launch_flood_seed(hipStream_t s, const FloodDev &f, const int32_t *nodes, int n, int64_t time_us);
-// unit_count: [units] words of scratch, units and chunk from traffic_geometry(n_nodes)
+// source_walk / units_scan / source_walk.  unit_count: [units] words of scratch, units and chunk from traffic_geometry(n_nodes)
 hipError_t launch_flood_sources(hipStream_t s, const FloodDev &f, int64_t time_us, int cap, int units, int chunk, int32_t *unit_count,
                                 int32_t *out_src, int32_t *out_count);
 // packet numbers 0 .. P - 1 of the slot described by `slot` (cand: nullptr or [P]) and all of the slot's links; act: room for P words

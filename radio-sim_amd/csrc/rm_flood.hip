@@ -9,6 +9,7 @@
 //   sources   k_flood_src_count    a node's own lane: due and c >= k -> the suppression roll (and a mark in claim[j]); else counted
 //             k_flood_src_scan     the units' counts scanned, the list padded
 //             k_flood_src_write    the unmarked due nodes written in ascending order (their state is as at the start); marks cleared
+//             (source_walk on both sides of units_scan, rm_device.hpp, with the two bodies above as its membership test)
 //   advance   k_flood_adv_claim    atomicMin of p over claim[j]: the first occurrence of every candidate that has the data
 //             k_flood_rx_hear      a lane per link: heard[d]++; d with the data and not sending: c[d]++; d without: atomicMin of
 //                                  t_end over tmin[d]
@@ -21,22 +22,20 @@
 // and by integer atomic adds for heard and c.  A link's packet number is found by a search of the slot's pkt_offset, which
 // uc_describe hands out for every slot kind; UcSlot was not given TickDev's out_pkt column, because whether every path that
 // materializes a slot's compact arrays also fills that column was not established, and log2(n_new) cached loads per link do not
-// depend on it.  The totals -- one address for everybody -- are added once per wave.  No LDS beyond the scan's word, no scratch
-// memory, no floating point.
+// depend on it.  The totals -- one address for everybody -- are added once per wave (relay_total, relay_total_max; those, the
+// claim step relay_claim and the other relay_* helpers are rm_device.hpp's, shared with the forwarding queues, rm_fwd.hip).  No
+// LDS beyond the scan's word, no scratch memory, no floating point.
 #include "rm_device.hpp"
 
 namespace rm {
 
-constexpr int kFloodThreads = 256;
+constexpr int kFloodThreads = kRelayThreads;
 // Workgroups per pass over the slot's links, as the traffic counters' pass: 16 384 lanes per stride (not tuned)
 constexpr int kFloodBlocks = 64;
 constexpr int32_t kFloodRest = INT32_MAX;
 constexpr long long kFloodNever = INT64_MAX;
 
-using u64 = unsigned long long;
-RM_D u64 *flood_w(uint64_t *p) { return reinterpret_cast<u64 *>(p); }
 RM_D long long *flood_t(int64_t *p) { return reinterpret_cast<long long *>(p); }
-RM_D bool flood_in(const FloodDev &f, int j) { return j >= 0 && j < f.n_nodes; }
 
 RM_D bool flood_due(const FloodDev &f, const rm_flood_node &r, int64_t t)
 {
@@ -50,22 +49,6 @@ RM_D void flood_schedule(const FloodDev &f, rm_flood_node &r, int j)
     flood_fire(f.imin_us, f.doublings, f.max_intervals, f.seed, j, r.first_us, r.interval, start, fire);
     r.start_us = start;
     r.fire_us = fire;
-}
-
-// the wave's share of a total, added once
-RM_D void flood_total(uint64_t *word, u64 v)
-{
-    v = wave_sum_u64(v);
-    if ((threadIdx.x & 63u) == 0u && v != 0ull) atomicAdd(flood_w(word), v);
-}
-
-RM_D void flood_total_max(uint64_t *word, u64 v)
-{
-    for (int d = 32; d > 0; d >>= 1) {
-        const u64 o = __shfl_xor(v, d);
-        v = o > v ? o : v;
-    }
-    if ((threadIdx.x & 63u) == 0u && v != 0ull) atomicMax(flood_w(word), v);
 }
 
 // ---- enable / reset, the tree
@@ -99,7 +82,7 @@ __global__ void __launch_bounds__(kFloodThreads) k_flood_seed_claim(const FloodD
     const int e = int(blockIdx.x) * kFloodThreads + int(threadIdx.x);
     if (e >= n) return;
     int32_t j = nodes[e];
-    if (!flood_in(f, j) || f.node[j].first_us >= 0) j = -1;
+    if (!relay_in(f, j) || f.node[j].first_us >= 0) j = -1;
     else atomicMin(&f.claim[j], e);
     f.act[e] = j;
 }
@@ -123,93 +106,50 @@ __global__ void __launch_bounds__(kFloodThreads) k_flood_seed_apply(const FloodD
             t_seeds = 1ull;
         }
     }
-    flood_total(&f.totals->seeds, t_seeds);
-    flood_total(&f.totals->covered, t_seeds);
-    flood_total_max(&f.totals->last_first_us, t_seeds ? u64(time_us) : 0ull);
+    relay_total(&f.totals->seeds, t_seeds);
+    relay_total(&f.totals->covered, t_seeds);
+    relay_total_max(&f.totals->last_first_us, t_seeds ? u64(time_us) : 0ull);
 }
 
 // ---- the source list: the nodes due at time_us that are not suppressed, ascending
 
-template <bool WRITE>
-RM_D void flood_src_walk(const FloodDev &f, const int64_t time_us, const int cap, const int chunk, int32_t *unit_count, int32_t *out_src)
-{
-    const int lane = threadIdx.x;
-    const int unit = blockIdx.x;
-    const int first = unit * chunk;
-    const int last = min(first + chunk, f.n_nodes);
-    int run = WRITE ? unit_count[unit] : 0; // WRITE: where the unit's next source goes; else its sources so far
-    u64 t_supp = 0;
-    for (int i0 = first; i0 < last; i0 += 64) {
-        const int node = i0 + lane;
-        bool hit = false;
-        if (node < last) {
-            rm_flood_node &r = f.node[node];
-            if (WRITE) {
-                if (f.claim[node] != kFloodRest) f.claim[node] = kFloodRest; // suppressed by the count launch: not listed
-                else hit = flood_due(f, r, time_us);                         // (its row is as at the start of the call)
-            } else if (flood_due(f, r, time_us)) {
-                if (f.redundancy > 0 && r.c >= f.redundancy) {
-                    r.suppressed += 1u;
-                    r.interval += 1;
-                    r.c = 0;
-                    flood_schedule(f, r, node);
-                    f.claim[node] = -1;
-                    t_supp += 1ull;
-                } else {
-                    hit = true;
-                }
-            }
-        }
-        const uint64_t m = ballot64(hit);
-        if (WRITE) {
-            const int pos = run + int(lane_prefix(m));
-            if (hit && pos < cap) out_src[pos] = node;
-        }
-        run += __popcll(m);
-    }
-    if (!WRITE) {
-        if (lane == 0) unit_count[unit] = run;
-        flood_total(&f.totals->suppressed, t_supp);
-    }
-}
-
+// count: a due node with c >= k is suppressed now -- its row moves to the next interval, claim[node] is marked for the write
+// launch -- and any other due node is listed
 __global__ void __launch_bounds__(64) k_flood_src_count(const FloodDev f, const int64_t time_us, const int chunk, int32_t *unit_count)
 {
-    flood_src_walk<false>(f, time_us, 0, chunk, unit_count, nullptr);
+    u64 t_supp = 0;
+    source_walk<false>(f.n_nodes, 0, chunk, unit_count, nullptr, [&](int node) {
+        rm_flood_node &r = f.node[node];
+        if (!flood_due(f, r, time_us)) return false;
+        if (f.redundancy <= 0 || r.c < f.redundancy) return true;
+        r.suppressed += 1u;
+        r.interval += 1;
+        r.c = 0;
+        flood_schedule(f, r, node);
+        f.claim[node] = -1;
+        t_supp += 1ull;
+        return false;
+    });
+    relay_total(&f.totals->suppressed, t_supp);
 }
 
-// the first wave scans the units' counts in place, 64 at a time; then all four waves pad the list
 __global__ void __launch_bounds__(256) k_flood_src_scan(const int units, const int cap, int32_t *unit_count, int32_t *out_src, int32_t *out_count)
 {
-    __shared__ int32_t s_total;
-    if (threadIdx.x < 64) {
-        const int lane = threadIdx.x;
-        uint32_t carry = 0;
-        for (int u0 = 0; u0 < units; u0 += 64) {
-            const int u = u0 + lane;
-            const uint32_t v = u < units ? uint32_t(unit_count[u]) : 0u;
-            const uint32_t inc = wave_inclusive_scan(v, lane);
-            if (u < units) unit_count[u] = int32_t(carry + inc - v);
-            carry += __shfl(inc, 63);
-        }
-        if (lane == 0) {
-            s_total = int32_t(carry);
-            *out_count = int32_t(carry);
-        }
-    }
-    __syncthreads();
-    for (int p = min(s_total, cap) + int(threadIdx.x); p < cap; p += 256) out_src[p] = -1;
+    units_scan(units, 1, cap, unit_count, out_src, out_count);
 }
 
+// write: a marked node is not listed and its mark is cleared; the row of any other is as at the start of the call
 __global__ void __launch_bounds__(64) k_flood_src_write(const FloodDev f, const int64_t time_us, const int cap, const int chunk, int32_t *unit_count,
                                                         int32_t *out_src)
 {
-    flood_src_walk<true>(f, time_us, cap, chunk, unit_count, out_src);
+    source_walk<true>(f.n_nodes, cap, chunk, unit_count, out_src, [&](int node) {
+        if (f.claim[node] == kFloodRest) return flood_due(f, f.node[node], time_us);
+        f.claim[node] = kFloodRest;
+        return false;
+    });
 }
 
 // ---- advance
-
-RM_D bool flood_slot_lost(const UcSlot &s) { return s.out_count && uc_lost(s); }
 
 // the slot's links: stored ones only, and none behind the last packet's segment
 RM_D uint32_t flood_links(const UcSlot &s)
@@ -249,7 +189,7 @@ RM_D bool flood_link(const FloodDev &f, const UcSlot &s, const uint32_t i, Flood
     l.p = flood_pkt(s, i);
     l.src = s.recs[l.p].src;
     l.dst = s.dst[i];
-    if (!flood_in(f, l.src) || !flood_in(f, l.dst)) return false;
+    if (!relay_in(f, l.src) || !relay_in(f, l.dst)) return false;
     l.t_end = s.recs[l.p].start_us + s.recs[l.p].air_us;
     return true;
 }
@@ -257,20 +197,13 @@ RM_D bool flood_link(const FloodDev &f, const UcSlot &s, const uint32_t i, Flood
 __global__ void __launch_bounds__(kFloodThreads) k_flood_adv_claim(const FloodDev f, const UcSlot s, const int32_t *__restrict__ cand, const int P)
 {
     const int p = int(blockIdx.x) * kFloodThreads + int(threadIdx.x);
-    if (flood_slot_lost(s)) {
-        if (p == 0) atomicAdd(flood_w(&f.totals->skipped_slots), 1ull);
-        return;
-    }
-    if (p >= P) return;
-    int32_t j = cand ? cand[p] : s.recs[p].src;
-    if (!flood_in(f, j) || f.node[j].first_us < 0) j = -1; // foreign traffic
-    else atomicMin(&f.claim[j], p);
-    f.act[p] = j;
+    const int32_t j = relay_claim(f, s, cand, P, p, [&](int j) { return f.node[j].first_us >= 0; }); // (a node that has the data)
+    if (j != kClaimNone) f.act[p] = j;
 }
 
 __global__ void __launch_bounds__(kFloodThreads) k_flood_rx_hear(const FloodDev f, const UcSlot s)
 {
-    if (flood_slot_lost(s)) return; // (uniform)
+    if (relay_slot_lost(s)) return; // (uniform)
     const uint32_t stride = gridDim.x * blockDim.x;
     const uint32_t n = flood_links(s);
     const uint32_t n_up = (n + 63u) & ~63u; // whole waves
@@ -289,12 +222,12 @@ __global__ void __launch_bounds__(kFloodThreads) k_flood_rx_hear(const FloodDev 
             atomicMin(flood_t(&f.tmin[l.dst]), (long long)l.t_end);
         }
     }
-    flood_total(&f.totals->heard, t_heard);
+    relay_total(&f.totals->heard, t_heard);
 }
 
 __global__ void __launch_bounds__(kFloodThreads) k_flood_rx_pick(const FloodDev f, const UcSlot s)
 {
-    if (flood_slot_lost(s)) return;
+    if (relay_slot_lost(s)) return;
     const uint32_t stride = gridDim.x * blockDim.x;
     const uint32_t n = flood_links(s);
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -308,7 +241,7 @@ __global__ void __launch_bounds__(kFloodThreads) k_flood_rx_pick(const FloodDev 
 
 __global__ void __launch_bounds__(kFloodThreads) k_flood_settle(const FloodDev f, const UcSlot s, const int P)
 {
-    if (flood_slot_lost(s)) return;
+    if (relay_slot_lost(s)) return;
     const uint32_t stride = gridDim.x * blockDim.x;
     const uint32_t n = flood_links(s);
     const uint32_t n_up = (n + 63u) & ~63u;
@@ -355,17 +288,16 @@ __global__ void __launch_bounds__(kFloodThreads) k_flood_settle(const FloodDev f
             t_sent += 1ull;
         }
     }
-    flood_total(&f.totals->covered, t_new);
-    flood_total(&f.totals->sent, t_sent);
-    flood_total(&f.totals->deferred, t_deferred);
-    flood_total(&f.totals->stray, t_stray);
-    flood_total_max(&f.totals->max_hop, t_hop);
-    flood_total_max(&f.totals->last_first_us, t_last);
+    relay_total(&f.totals->covered, t_new);
+    relay_total(&f.totals->sent, t_sent);
+    relay_total(&f.totals->deferred, t_deferred);
+    relay_total(&f.totals->stray, t_stray);
+    relay_total_max(&f.totals->max_hop, t_hop);
+    relay_total_max(&f.totals->last_first_us, t_last);
 }
 
 // ---- launches
 
-static int flood_blocks(int n) { return std::max(1, (n + kFloodThreads - 1) / kFloodThreads); }
 static bool flood_dev_ok(const FloodDev &f)
 {
     return f.node && f.totals && f.claim && f.pmin && f.tmin && f.n_nodes >= 0 && f.max_intervals >= 1 && f.max_intervals <= 64 && f.imin_us >= 2;
@@ -374,14 +306,14 @@ static bool flood_dev_ok(const FloodDev &f)
 hipError_t launch_flood_init(hipStream_t s, const FloodDev &f)
 {
     if (!flood_dev_ok(f)) return hipErrorInvalidValue;
-    RM_KLAUNCH(k_flood_init, dim3(flood_blocks(f.n_nodes)), dim3(kFloodThreads), 0, s, f);
+    RM_KLAUNCH(k_flood_init, dim3(relay_blocks(f.n_nodes)), dim3(kFloodThreads), 0, s, f);
     return hipGetLastError();
 }
 
 hipError_t launch_flood_tree(hipStream_t s, const FloodDev &f, int32_t *parent, int32_t *hop)
 {
     if (!flood_dev_ok(f) || !parent) return hipErrorInvalidValue;
-    RM_KLAUNCH(k_flood_tree, dim3(flood_blocks(f.n_nodes)), dim3(kFloodThreads), 0, s, f, parent, hop);
+    RM_KLAUNCH(k_flood_tree, dim3(relay_blocks(f.n_nodes)), dim3(kFloodThreads), 0, s, f, parent, hop);
     return hipGetLastError();
 }
 
@@ -389,8 +321,8 @@ hipError_t launch_flood_seed(hipStream_t s, const FloodDev &f, const int32_t *no
 {
     if (n <= 0) return hipSuccess;
     if (!flood_dev_ok(f) || !nodes || !f.act) return hipErrorInvalidValue;
-    RM_KLAUNCH(k_flood_seed_claim, dim3(flood_blocks(n)), dim3(kFloodThreads), 0, s, f, nodes, n);
-    RM_KLAUNCH(k_flood_seed_apply, dim3(flood_blocks(n)), dim3(kFloodThreads), 0, s, f, n, time_us);
+    RM_KLAUNCH(k_flood_seed_claim, dim3(relay_blocks(n)), dim3(kFloodThreads), 0, s, f, nodes, n);
+    RM_KLAUNCH(k_flood_seed_apply, dim3(relay_blocks(n)), dim3(kFloodThreads), 0, s, f, n, time_us);
     return hipGetLastError();
 }
 
@@ -408,7 +340,7 @@ hipError_t launch_flood_sources(hipStream_t s, const FloodDev &f, int64_t time_u
 hipError_t launch_flood_advance(hipStream_t s, const FloodDev &f, const UcSlot &slot, const int32_t *cand, int P)
 {
     if (!flood_dev_ok(f) || P < 0 || P > slot.n_new || (P > 0 && (!f.act || !slot.recs))) return hipErrorInvalidValue;
-    RM_KLAUNCH(k_flood_adv_claim, dim3(flood_blocks(P)), dim3(kFloodThreads), 0, s, f, slot, cand, P); // (also with P == 0: a lost slot is counted)
+    RM_KLAUNCH(k_flood_adv_claim, dim3(relay_blocks(P)), dim3(kFloodThreads), 0, s, f, slot, cand, P); // (also with P == 0: a lost slot is counted)
     if (slot.n_new <= 0) return hipGetLastError();
     RM_KLAUNCH(k_flood_rx_hear, dim3(kFloodBlocks), dim3(kFloodThreads), 0, s, f, slot);
     RM_KLAUNCH(k_flood_rx_pick, dim3(kFloodBlocks), dim3(kFloodThreads), 0, s, f, slot);

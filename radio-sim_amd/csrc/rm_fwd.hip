@@ -16,27 +16,16 @@
 //   inject    k_fwd_inj_place   tickets per node, the packets written;  k_fwd_inj_apply  masks, lengths, counters
 // Rows are written with integer atomics where another lane may write the same word (commutative: add, or, and, max) and with
 // plain stores where only the node's own lane can (a node participates once per call).  The totals -- one address for everybody --
-// are added once per wave.  The source list is an ordered stream compaction cut as the traffic generator's (rm_traffic.hip):
-// k_fwd_src_count / _scan / _write.  No LDS beyond the scan's word, no scratch memory, no floating point.
+// are added once per wave (relay_total).  The source list is an ordered stream compaction, k_fwd_src_count / _scan / _write:
+// source_walk with fwd_sendable as the membership test on both sides of units_scan.  Those, relay_claim and the small relay_*
+// helpers are rm_device.hpp's, shared with the floods (rm_flood.hip); the queue order is rm_math.hpp's fwd_packet_order.  No LDS
+// beyond the scan's word, no scratch memory, no floating point.
 #include "rm_device.hpp"
 
 namespace rm {
 
-constexpr int kFwdThreads = 256;
+constexpr int kFwdThreads = kRelayThreads;
 enum { kFwdNone = 0, kFwdStray, kFwdDeferred, kFwdFailed, kFwdRejected, kFwdPending, kFwdSink, kFwdPush, kFwdTtl, kFwdNoRoute, kFwdFull };
-
-using u64 = unsigned long long;
-RM_D u64 *fwd_w(uint64_t *p) { return reinterpret_cast<u64 *>(p); }
-RM_D bool fwd_in(const FwdDev &f, int j) { return j >= 0 && j < f.n_nodes; }
-
-// queue order
-RM_D bool fwd_before(const rm_fwd_packet &a, const rm_fwd_packet &b)
-{
-    if (a.enq_us != b.enq_us) return a.enq_us < b.enq_us;
-    if (a.birth_us != b.birth_us) return a.birth_us < b.birth_us;
-    if (a.origin != b.origin) return a.origin < b.origin;
-    return a.hops < b.hops;
-}
 
 // the slot of node j's head (-1: the queue is empty) and the head itself
 RM_D int fwd_head(const FwdDev &f, int j, uint32_t mask, rm_fwd_packet &head)
@@ -47,7 +36,7 @@ RM_D int fwd_head(const FwdDev &f, int j, uint32_t mask, rm_fwd_packet &head)
         const int s = __ffs(int(mask)) - 1;
         mask &= mask - 1u;
         const rm_fwd_packet q = f.pk[size_t(j) * size_t(f.Q) + size_t(s)];
-        if (at < 0 || fwd_before(q, head)) {
+        if (at < 0 || fwd_packet_order(q, head)) {
             head = q;
             at = s;
         }
@@ -72,23 +61,16 @@ RM_D int fwd_free_slot(const FwdDev &f, uint32_t mask, int k)
     return free ? __ffs(int(free)) - 1 : -1;
 }
 
-// the wave's share of a total, added once
-RM_D void fwd_total(uint64_t *word, u64 v)
-{
-    v = wave_sum_u64(v);
-    if ((threadIdx.x & 63u) == 0u && v != 0ull) atomicAdd(fwd_w(word), v);
-}
-
 // a packet that arrives at a sink at time t with `hops` hops behind it
 RM_D void fwd_arrive(const FwdDev &f, const rm_fwd_packet &q, int64_t t, int hops, u64 &t_arrived, u64 &t_lat, u64 &t_hops)
 {
     const u64 lat = u64(t - q.birth_us);
-    if (fwd_in(f, q.origin)) {
+    if (relay_in(f, q.origin)) {
         rm_fwd_node &o = f.node[q.origin];
-        atomicAdd(fwd_w(&o.arrived), 1ull);
-        atomicAdd(fwd_w(&o.latency_us_sum), lat);
-        atomicMax(fwd_w(&o.latency_us_max), lat);
-        atomicAdd(fwd_w(&o.hops_sum), u64(hops));
+        atomicAdd(relay_w(&o.arrived), 1ull);
+        atomicAdd(relay_w(&o.latency_us_sum), lat);
+        atomicMax(relay_w(&o.latency_us_max), lat);
+        atomicAdd(relay_w(&o.hops_sum), u64(hops));
     }
     t_arrived += 1ull, t_lat += lat, t_hops += u64(hops);
 }
@@ -96,8 +78,8 @@ RM_D void fwd_arrive(const FwdDev &f, const rm_fwd_packet &q, int64_t t, int hop
 // a packet dropped at node `at`
 RM_D void fwd_drop(const FwdDev &f, const rm_fwd_packet &q, int at)
 {
-    if (fwd_in(f, q.origin)) atomicAdd(fwd_w(&f.node[q.origin].lost), 1ull);
-    atomicAdd(fwd_w(&f.node[at].dropped), 1ull);
+    if (relay_in(f, q.origin)) atomicAdd(relay_w(&f.node[q.origin].lost), 1ull);
+    atomicAdd(relay_w(&f.node[at].dropped), 1ull);
 }
 
 // ---- enable / reset, routes
@@ -120,7 +102,7 @@ __global__ void __launch_bounds__(kFwdThreads) k_fwd_next(const FwdDev f, const 
     const int j = int(blockIdx.x) * kFwdThreads + int(threadIdx.x);
     if (j >= f.n_nodes) return;
     const int32_t v = parent[j];
-    f.node[j].next = (fwd_in(f, v) && v != j) ? v : RM_FWD_NO_ROUTE;
+    f.node[j].next = (relay_in(f, v) && v != j) ? v : RM_FWD_NO_ROUTE;
 }
 
 __global__ void __launch_bounds__(kFwdThreads) k_fwd_roots(const FwdDev f, const int32_t *__restrict__ roots, const int n_roots)
@@ -128,7 +110,7 @@ __global__ void __launch_bounds__(kFwdThreads) k_fwd_roots(const FwdDev f, const
     const int k = int(blockIdx.x) * kFwdThreads + int(threadIdx.x);
     if (k >= n_roots) return;
     const int32_t r = roots[k];
-    if (fwd_in(f, r)) f.node[r].next = RM_FWD_SINK; // (duplicates store the same value)
+    if (relay_in(f, r)) f.node[r].next = RM_FWD_SINK; // (duplicates store the same value)
 }
 
 // the queues of the nodes that are now sinks or without a route
@@ -158,11 +140,11 @@ __global__ void __launch_bounds__(kFwdThreads) k_fwd_settle(const FwdDev f, cons
             r.queue_len = 0;
         }
     }
-    fwd_total(&f.totals->arrived, t_arrived);
-    fwd_total(&f.totals->latency_us_sum, t_lat);
-    fwd_total(&f.totals->hops_sum, t_hops);
-    fwd_total(&f.totals->dropped_no_route, t_noroute);
-    fwd_total(&f.totals->in_flight, 0ull - t_gone);
+    relay_total(&f.totals->arrived, t_arrived);
+    relay_total(&f.totals->latency_us_sum, t_lat);
+    relay_total(&f.totals->hops_sum, t_hops);
+    relay_total(&f.totals->dropped_no_route, t_noroute);
+    relay_total(&f.totals->in_flight, 0ull - t_gone);
 }
 
 // ---- inject
@@ -174,7 +156,7 @@ __global__ void __launch_bounds__(kFwdThreads) k_fwd_inj_place(const FwdDev f, c
     FwdAct a{};
     a.j = a.w = a.head = a.push = -1;
     const int32_t j = src[e];
-    if (fwd_in(f, j)) {
+    if (relay_in(f, j)) {
         a.j = j;
         const rm_fwd_node &r = f.node[j];
         if (r.next == RM_FWD_SINK) {
@@ -204,10 +186,10 @@ __global__ void __launch_bounds__(kFwdThreads) k_fwd_inj_apply(const FwdDev f, c
         const FwdAct a = f.act[e];
         if (a.j >= 0) {
             rm_fwd_node &r = f.node[a.j];
-            atomicAdd(fwd_w(&r.generated), 1ull);
+            atomicAdd(relay_w(&r.generated), 1ull);
             t_gen = 1ull;
             if (a.state == kFwdSink) {
-                atomicAdd(fwd_w(&r.arrived), 1ull);
+                atomicAdd(relay_w(&r.arrived), 1ull);
                 t_arrived = 1ull;
             } else if (a.state == kFwdPush) {
                 atomicOr(&r.slot_mask, 1u << a.push);
@@ -215,100 +197,52 @@ __global__ void __launch_bounds__(kFwdThreads) k_fwd_inj_apply(const FwdDev f, c
                 atomicMax(&r.queue_max, a.qmax);
                 t_in = 1ull;
             } else {
-                atomicAdd(fwd_w(&r.lost), 1ull);
-                atomicAdd(fwd_w(&r.dropped), 1ull);
+                atomicAdd(relay_w(&r.lost), 1ull);
+                atomicAdd(relay_w(&r.dropped), 1ull);
                 if (a.state == kFwdNoRoute) t_noroute = 1ull;
                 else t_full = 1ull;
             }
             f.pushed[a.j] = 0;
         }
     }
-    fwd_total(&f.totals->generated, t_gen);
-    fwd_total(&f.totals->arrived, t_arrived);
-    fwd_total(&f.totals->dropped_no_route, t_noroute);
-    fwd_total(&f.totals->dropped_full, t_full);
-    fwd_total(&f.totals->in_flight, t_in);
+    relay_total(&f.totals->generated, t_gen);
+    relay_total(&f.totals->arrived, t_arrived);
+    relay_total(&f.totals->dropped_no_route, t_noroute);
+    relay_total(&f.totals->dropped_full, t_full);
+    relay_total(&f.totals->in_flight, t_in);
 }
 
 // ---- the source list: the nodes sendable at time_us, ascending
 
-template <bool WRITE>
-RM_D void fwd_src_walk(const FwdDev &f, const int64_t time_us, const int cap, const int chunk, int32_t *unit_count, int32_t *out_src)
-{
-    const int lane = threadIdx.x;
-    const int unit = blockIdx.x;
-    const int first = unit * chunk;
-    const int last = min(first + chunk, f.n_nodes);
-    int run = WRITE ? unit_count[unit] : 0; // WRITE: where the unit's next source goes; else its sources so far
-    for (int i0 = first; i0 < last; i0 += 64) {
-        const int node = i0 + lane;
-        const bool hit = node < last && fwd_sendable(f, node, time_us, nullptr);
-        const uint64_t m = ballot64(hit);
-        if (WRITE) {
-            const int pos = run + int(lane_prefix(m));
-            if (hit && pos < cap) out_src[pos] = node;
-        }
-        run += __popcll(m);
-    }
-    if (!WRITE && lane == 0) unit_count[unit] = run;
-}
-
 __global__ void __launch_bounds__(64) k_fwd_src_count(const FwdDev f, const int64_t time_us, const int chunk, int32_t *unit_count)
 {
-    fwd_src_walk<false>(f, time_us, 0, chunk, unit_count, nullptr);
+    source_walk<false>(f.n_nodes, 0, chunk, unit_count, nullptr, [&](int node) { return fwd_sendable(f, node, time_us, nullptr); });
 }
 
-// the first wave scans the units' counts in place, 64 at a time; then all four waves pad the list
 __global__ void __launch_bounds__(256) k_fwd_src_scan(const int units, const int cap, int32_t *unit_count, int32_t *out_src, int32_t *out_count)
 {
-    __shared__ int32_t s_total;
-    if (threadIdx.x < 64) {
-        const int lane = threadIdx.x;
-        uint32_t carry = 0;
-        for (int u0 = 0; u0 < units; u0 += 64) {
-            const int u = u0 + lane;
-            const uint32_t v = u < units ? uint32_t(unit_count[u]) : 0u;
-            const uint32_t inc = wave_inclusive_scan(v, lane);
-            if (u < units) unit_count[u] = int32_t(carry + inc - v);
-            carry += __shfl(inc, 63);
-        }
-        if (lane == 0) {
-            s_total = int32_t(carry);
-            *out_count = int32_t(carry);
-        }
-    }
-    __syncthreads();
-    for (int p = min(s_total, cap) + int(threadIdx.x); p < cap; p += 256) out_src[p] = -1;
+    units_scan(units, 1, cap, unit_count, out_src, out_count);
 }
 
 __global__ void __launch_bounds__(64) k_fwd_src_write(const FwdDev f, const int64_t time_us, const int cap, const int chunk, int32_t *unit_count,
                                                       int32_t *out_src)
 {
-    fwd_src_walk<true>(f, time_us, cap, chunk, unit_count, out_src);
+    source_walk<true>(f.n_nodes, cap, chunk, unit_count, out_src, [&](int node) { return fwd_sendable(f, node, time_us, nullptr); });
 }
 
 // ---- advance
 
-RM_D bool fwd_slot_lost(const UcSlot &s) { return s.out_count && uc_lost(s); }
-
 __global__ void __launch_bounds__(kFwdThreads) k_fwd_adv_claim(const FwdDev f, const UcSlot s, const int32_t *__restrict__ cand, const int P)
 {
     const int p = int(blockIdx.x) * kFwdThreads + int(threadIdx.x);
-    if (fwd_slot_lost(s)) {
-        if (p == 0) atomicAdd(fwd_w(&f.totals->skipped_slots), 1ull);
-        return;
-    }
-    if (p >= P) return;
-    int32_t j = cand ? cand[p] : s.recs[p].src;
-    if (!fwd_in(f, j)) j = -1;
-    else atomicMin(&f.claim[j], p);
-    f.act[p].j = j;
+    const int32_t j = relay_claim(f, s, cand, P, p, [](int) { return true; }); // (every node of the table takes part)
+    if (j != kClaimNone) f.act[p].j = j;
 }
 
 __global__ void __launch_bounds__(kFwdThreads) k_fwd_adv_match(const FwdDev f, const UcSlot s, const int P)
 {
     const int p = int(blockIdx.x) * kFwdThreads + int(threadIdx.x);
-    if (p >= P || fwd_slot_lost(s)) return;
+    if (p >= P || relay_slot_lost(s)) return;
     FwdAct a{};
     a.j = f.act[p].j;
     a.w = a.head = a.push = -1;
@@ -317,7 +251,7 @@ __global__ void __launch_bounds__(kFwdThreads) k_fwd_adv_match(const FwdDev f, c
         if (f.claim[a.j] == p && fwd_sendable(f, a.j, s.recs[p].start_us, &a.head)) {
             const int32_t w = f.node[a.j].next;
             a.state = kFwdFailed;
-            if (fwd_in(f, w)) { // (a non-empty queue implies it)
+            if (relay_in(f, w)) { // (a non-empty queue implies it)
                 a.w = w;
                 int32_t link;
                 if (s.recs[p].src != a.j) {
@@ -339,7 +273,7 @@ __global__ void __launch_bounds__(kFwdThreads) k_fwd_adv_match(const FwdDev f, c
 __global__ void __launch_bounds__(kFwdThreads) k_fwd_adv_accept(const FwdDev f, const UcSlot s, const int P)
 {
     const int p = int(blockIdx.x) * kFwdThreads + int(threadIdx.x);
-    if (p >= P || fwd_slot_lost(s)) return;
+    if (p >= P || relay_slot_lost(s)) return;
     FwdAct a = f.act[p];
     if (a.state != kFwdPending) return;
     const rm_fwd_node &w = f.node[a.w];
@@ -365,7 +299,7 @@ __global__ void __launch_bounds__(kFwdThreads) k_fwd_adv_accept(const FwdDev f, 
 __global__ void __launch_bounds__(kFwdThreads) k_fwd_adv_apply(const FwdDev f, const UcSlot s, const int P)
 {
     const int p = int(blockIdx.x) * kFwdThreads + int(threadIdx.x);
-    if (fwd_slot_lost(s)) return; // (uniform)
+    if (relay_slot_lost(s)) return; // (uniform)
     u64 t_arrived = 0, t_lat = 0, t_hops = 0, t_retries = 0, t_ttl = 0, t_stray = 0, t_in = 0;
     if (p < P) {
         const FwdAct a = f.act[p];
@@ -398,7 +332,7 @@ __global__ void __launch_bounds__(kFwdThreads) k_fwd_adv_apply(const FwdDev f, c
             } else {
                 if (a.state == kFwdDeferred) r.deferred += 1;
                 else r.failed += 1;
-                if (a.state == kFwdRejected) atomicAdd(fwd_w(&f.node[a.w].rejected), 1ull);
+                if (a.state == kFwdRejected) atomicAdd(relay_w(&f.node[a.w].rejected), 1ull);
                 const int tries = r.tries + 1;
                 if (tries > f.max_retries) {
                     pop = true;
@@ -418,18 +352,17 @@ __global__ void __launch_bounds__(kFwdThreads) k_fwd_adv_apply(const FwdDev f, c
             }
         }
     }
-    fwd_total(&f.totals->arrived, t_arrived);
-    fwd_total(&f.totals->latency_us_sum, t_lat);
-    fwd_total(&f.totals->hops_sum, t_hops);
-    fwd_total(&f.totals->dropped_retries, t_retries);
-    fwd_total(&f.totals->dropped_ttl, t_ttl);
-    fwd_total(&f.totals->stray, t_stray);
-    fwd_total(&f.totals->in_flight, t_in);
+    relay_total(&f.totals->arrived, t_arrived);
+    relay_total(&f.totals->latency_us_sum, t_lat);
+    relay_total(&f.totals->hops_sum, t_hops);
+    relay_total(&f.totals->dropped_retries, t_retries);
+    relay_total(&f.totals->dropped_ttl, t_ttl);
+    relay_total(&f.totals->stray, t_stray);
+    relay_total(&f.totals->in_flight, t_in);
 }
 
 // ---- launches
 
-static int fwd_blocks(int n) { return std::max(1, (n + kFwdThreads - 1) / kFwdThreads); }
 static bool fwd_dev_ok(const FwdDev &f)
 {
     return f.node && f.pk && f.totals && f.claim && f.acc && f.pushed && f.n_nodes >= 0 && f.Q >= 1 && f.Q <= 16;
@@ -438,16 +371,16 @@ static bool fwd_dev_ok(const FwdDev &f)
 hipError_t launch_fwd_init(hipStream_t s, const FwdDev &f, bool keep_next)
 {
     if (!fwd_dev_ok(f)) return hipErrorInvalidValue;
-    RM_KLAUNCH(k_fwd_init, dim3(fwd_blocks(f.n_nodes)), dim3(kFwdThreads), 0, s, f, keep_next ? 1 : 0);
+    RM_KLAUNCH(k_fwd_init, dim3(relay_blocks(f.n_nodes)), dim3(kFwdThreads), 0, s, f, keep_next ? 1 : 0);
     return hipGetLastError();
 }
 
 hipError_t launch_fwd_set_next(hipStream_t s, const FwdDev &f, const int32_t *parent, const int32_t *roots, int n_roots, int64_t time_us)
 {
     if (!fwd_dev_ok(f) || !parent || n_roots < 0 || (n_roots > 0 && !roots)) return hipErrorInvalidValue;
-    RM_KLAUNCH(k_fwd_next, dim3(fwd_blocks(f.n_nodes)), dim3(kFwdThreads), 0, s, f, parent);
-    if (n_roots > 0) RM_KLAUNCH(k_fwd_roots, dim3(fwd_blocks(n_roots)), dim3(kFwdThreads), 0, s, f, roots, n_roots);
-    RM_KLAUNCH(k_fwd_settle, dim3(fwd_blocks(f.n_nodes)), dim3(kFwdThreads), 0, s, f, time_us);
+    RM_KLAUNCH(k_fwd_next, dim3(relay_blocks(f.n_nodes)), dim3(kFwdThreads), 0, s, f, parent);
+    if (n_roots > 0) RM_KLAUNCH(k_fwd_roots, dim3(relay_blocks(n_roots)), dim3(kFwdThreads), 0, s, f, roots, n_roots);
+    RM_KLAUNCH(k_fwd_settle, dim3(relay_blocks(f.n_nodes)), dim3(kFwdThreads), 0, s, f, time_us);
     return hipGetLastError();
 }
 
@@ -455,8 +388,8 @@ hipError_t launch_fwd_inject(hipStream_t s, const FwdDev &f, const int32_t *src,
 {
     if (n <= 0) return hipSuccess;
     if (!fwd_dev_ok(f) || !src || !f.act) return hipErrorInvalidValue;
-    RM_KLAUNCH(k_fwd_inj_place, dim3(fwd_blocks(n)), dim3(kFwdThreads), 0, s, f, src, n, time_us);
-    RM_KLAUNCH(k_fwd_inj_apply, dim3(fwd_blocks(n)), dim3(kFwdThreads), 0, s, f, n);
+    RM_KLAUNCH(k_fwd_inj_place, dim3(relay_blocks(n)), dim3(kFwdThreads), 0, s, f, src, n, time_us);
+    RM_KLAUNCH(k_fwd_inj_apply, dim3(relay_blocks(n)), dim3(kFwdThreads), 0, s, f, n);
     return hipGetLastError();
 }
 
@@ -474,7 +407,7 @@ hipError_t launch_fwd_sources(hipStream_t s, const FwdDev &f, int64_t time_us, i
 hipError_t launch_fwd_advance(hipStream_t s, const FwdDev &f, const UcSlot &slot, const int32_t *cand, int P)
 {
     if (!fwd_dev_ok(f) || P < 0 || P > slot.n_new || (P > 0 && (!f.act || !slot.recs))) return hipErrorInvalidValue;
-    const dim3 grid(fwd_blocks(P)), block(kFwdThreads);
+    const dim3 grid(relay_blocks(P)), block(kFwdThreads);
     RM_KLAUNCH(k_fwd_adv_claim, grid, block, 0, s, f, slot, cand, P); // (also with P == 0: a lost slot is counted)
     if (P == 0) return hipGetLastError();
     RM_KLAUNCH(k_fwd_adv_match, grid, block, 0, s, f, slot, P);

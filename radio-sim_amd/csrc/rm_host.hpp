@@ -289,34 +289,34 @@ struct rm_context : TickSlot {
         hipEvent_t h_ev[2] = {nullptr, nullptr};
         int gen = 0;
     } uc;
-    // forwarding queues (E19; rm_api_fwd.cpp, rm_fwd.hip): the parameters, the tables by node index (the rows, the packets
-    // [n][queue_slots], the totals), the per-node scratch every call leaves at rest, the per-packet-number records of an advance or
-    // an inject, the source list's unit counts, the host forms' lists in device memory, and the pinned, host-mapped block a list
-    // read is staged through.  Nothing is allocated before rm_fwd_enable.
-    struct Fwd {
+    // What a relay feature -- a node table driven by a finished result slot -- keeps whatever it relays (the relay_* helpers at the
+    // end of this file work on it): the claim word per node every call leaves at rest, the source list's unit counts, the host
+    // forms' lists in device memory, and the pinned, host-mapped block a list read is staged through.  Nothing is allocated
+    // before the feature's enable.
+    struct Relay {
         bool on = false;
         int32_t n = -1; // the node count the tables were made for; -1: off
+        DevBuf<int32_t> claim, unit_count, stage;
+        PinnedBlock h;
+    };
+    // forwarding queues (E19; rm_api_fwd.cpp, rm_fwd.hip): the parameters, the tables by node index (the rows, the packets
+    // [n][queue_slots], the totals), the rest of the per-node scratch, the per-packet-number records of an advance or an inject
+    struct Fwd : Relay {
         rm_fwd_params p{};
         DevBuf<rm_fwd_node> node;
         DevBuf<rm_fwd_packet> pk;
         DevBuf<rm_fwd_totals> totals;
-        DevBuf<int32_t> claim, acc, pushed, unit_count, stage;
+        DevBuf<int32_t> acc, pushed;
         DevBuf<rm::FwdAct> act;
-        PinnedBlock h;
     } fw;
     // dissemination floods (E20; rm_api_flood.cpp, rm_flood.hip): the parameters, the table by node index and its totals, the
-    // per-node scratch every call leaves at rest, one word per entry of an advance or seed list, the source list's unit counts,
-    // the host forms' lists in device memory, and the pinned, host-mapped block a list read is staged through.  Nothing is
-    // allocated before rm_flood_enable.
-    struct Flood {
-        bool on = false;
-        int32_t n = -1; // the node count the table was made for; -1: off
+    // rest of the per-node scratch, one word per entry of an advance or seed list
+    struct Flood : Relay {
         rm_flood_params p{};
         DevBuf<rm_flood_node> node;
         DevBuf<rm_flood_totals> totals;
-        DevBuf<int32_t> claim, pmin, act, unit_count, stage;
+        DevBuf<int32_t> pmin, act;
         DevBuf<int64_t> tmin;
-        PinnedBlock h;
     } fl;
     double base_rssi = -100.0; // AbstractRadioMedium.java:38
 
@@ -759,6 +759,22 @@ struct ProbeScope {
     ProbeScope(const ProbeScope &) = delete;
     ProbeScope &operator=(const ProbeScope &) = delete;
 };
+// The same for a call that is no tick (a query, a gate, a generate, a drain, a relay feature's call): rm_profile_kernels names
+// its kernels.  begin_sample (rm_api_plan.cpp) moves one piece of state that belongs to the ticks: it counts the launch sequence
+// in c->tick_index, which decides which sequences are sampled under rm_profile_enable(every_n).  Such a call puts the count
+// back: it is sampled iff the tick after it would be, and the ticks' sampling is as without the call
+struct CallProbe {
+    rm_context::Sample *smp;
+    explicit CallProbe(rm_context *c)
+    {
+        const uint64_t tick_index = c->tick_index;
+        smp = begin_sample(c);
+        c->tick_index = tick_index;
+    }
+    ~CallProbe() { if (smp) end_sample(); }
+    CallProbe(const CallProbe &) = delete;
+    CallProbe &operator=(const CallProbe &) = delete;
+};
 
 // ---- rm_api_events.cpp: the reception stage
 rm::EvDev ev_dev(rm_context *c);
@@ -1010,5 +1026,106 @@ int batch_run(rm_context *c, int32_t n_ticks, const int64_t *t_begin_us, const i
               int gather_block = 0, int digest_off = -1);
 // (gather_block: elements from one rank's block of the gathered buffer to the next, 0 = n_ticks * gather_slots; digest_off: where
 // in a rank's block of source indices its node-table digest lies -- two words, rm_table_digest -- or -1)
+
+// ---- the relay features' scaffold (E19 rm_api_fwd.cpp, E20 rm_api_flood.cpp): rm_context::Relay, the feature's own words passed in
+// (free_own releases the buffers the feature keeps beside the base's; off_msg is what a call says while the feature is off)
+inline void relay_release(rm_context *c, rm_context::Relay &r, void (*free_own)(rm_context *))
+{
+    r.on = false;
+    r.n = -1;
+    free_own(c);
+    r.claim.release(); r.unit_count.release(); r.stage.release();
+    r.h.release();
+}
+// off: the tables released (a launch in flight still reads them; pointers handed out end here)
+inline int relay_off(rm_context *c, rm_context::Relay &r, void (*free_own)(rm_context *))
+{
+    if (r.n >= 0 && c->stream) RM_HIP(hipStreamSynchronize(c->stream));
+    relay_release(c, r, free_own);
+    return RM_OK;
+}
+inline int relay_nodes_changed(rm_context *c, rm_context::Relay &r, void (*free_own)(rm_context *))
+{
+    if (r.n < 0 || r.n == c->n) return RM_OK;
+    return relay_off(c, r, free_own);
+}
+inline int relay_have(const rm_context::Relay &r, const char *off_msg) { return r.on ? RM_OK : fail(RM_ERR_STATE, off_msg); }
+// room for n entries of the running call in a block the stream's earlier calls may still use: a call that grows it waits for the
+// stream first.  (Enable sizes the per-entry records for n_nodes entries: only a list longer than the node table grows them)
+template <typename T> int relay_room(rm_context *c, DevBuf<T> &b, size_t n)
+{
+    n = std::max<size_t>(n, 1);
+    if (b.n >= n) return RM_OK;
+    RM_HIP(hipStreamSynchronize(c->stream));
+    RM_HIP(b.ensure(n));
+    return RM_OK;
+}
+inline int relay_check_host_list(const rm_context::Relay &r, const int32_t *list, int32_t n, const char *what)
+{
+    for (int32_t k = 0; k < n; ++k)
+        if (list[k] >= r.n) return fail(RM_ERR_INVALID, std::string("an entry of the host ") + what + " list is not below the node count");
+    return RM_OK;
+}
+// a host form's list in device memory (r.stage.p), there when this returns
+inline int relay_stage_list(rm_context *c, rm_context::Relay &r, const int32_t *list, int32_t n)
+{
+    RM_HIP(hipSetDevice(c->device));
+    RM_TRY(relay_room(c, r.stage, size_t(n)));
+    if (n < 1) return RM_OK;
+    RM_HIP(hipMemcpyAsync(r.stage.p, list, size_t(n) * 4, hipMemcpyHostToDevice, c->stream));
+    RM_HIP(hipStreamSynchronize(c->stream));
+    return RM_OK;
+}
+// the source list, device form: launch(units, chunk, dev_src, dev_count) is the feature's three launches
+template <typename Launch>
+int relay_sources_device(rm_context *c, rm_context::Relay &r, const char *off_msg, int64_t time_us, int32_t cap, int32_t *dev_src, int32_t *dev_count,
+                         Launch launch)
+{
+    if (!dev_src || !dev_count || time_us < 0) return fail(RM_ERR_INVALID, "bad arguments");
+    if (cap < 1) return fail(RM_ERR_INVALID, "cap < 1");
+    RM_TRY(relay_have(r, off_msg));
+    RM_HIP(hipSetDevice(c->device));
+    int units = 0, chunk = 0;
+    rm::traffic_geometry(r.n, &units, &chunk);
+    if (r.unit_count.n < size_t(units)) return fail(RM_ERR_STATE, "internal: the units' counts were sized for another node count");
+    CallProbe probe(c);
+    RM_HIP(launch(units, chunk, dev_src, dev_count));
+    return RM_OK;
+}
+// ... and the host form: the list and its count through the staging block, waited for
+template <typename Launch>
+int relay_sources(rm_context *c, rm_context::Relay &r, const char *off_msg, int64_t time_us, int32_t cap, int32_t *src, int32_t *count, Launch launch)
+{
+    if (!src || !count || time_us < 0) return fail(RM_ERR_INVALID, "bad arguments");
+    if (cap < 1) return fail(RM_ERR_INVALID, "cap < 1");
+    RM_TRY(relay_have(r, off_msg));
+    RM_HIP(hipSetDevice(c->device));
+    RM_TRY(relay_room(c, r.stage, size_t(cap) + 1));
+    int32_t *d = r.stage.p;
+    RM_TRY(relay_sources_device(c, r, off_msg, time_us, cap, d, d + cap, launch));
+    RM_HIP(hipMemcpyAsync(src, d, size_t(cap) * 4, hipMemcpyDeviceToHost, c->stream));
+    RM_HIP(hipMemcpyAsync(count, d + cap, 4, hipMemcpyDeviceToHost, c->stream));
+    RM_HIP(hipStreamSynchronize(c->stream));
+    return RM_OK;
+}
+// what both advance forms check, in this order, before anything else happens
+inline int relay_check_advance(rm_context *c, const rm_context::Relay &r, const char *off_msg, int32_t slot, int32_t n_cand)
+{
+    if (n_cand < 0) return fail(RM_ERR_INVALID, "bad arguments");
+    RM_TRY(relay_have(r, off_msg));
+    RM_TRY(uc_check_state(c));
+    if (slot < 0 || slot >= c->uc.slots) return fail(RM_ERR_INVALID, "slot outside the slots of the last evaluating call");
+    return RM_OK;
+}
+// the device form's way to its launches: the checks, the finished slot described for the kernels, P packet numbers to look at
+inline int relay_advance_begin(rm_context *c, const rm_context::Relay &r, const char *off_msg, int32_t slot, const int32_t *dev_cand, int32_t n_cand,
+                               rm::UcSlot *d, int32_t *P)
+{
+    RM_TRY(relay_check_advance(c, r, off_msg, slot, n_cand));
+    RM_HIP(hipSetDevice(c->device));
+    RM_TRY(uc_describe(c, *slot_of(c, slot), d));
+    *P = dev_cand ? std::min(n_cand, d->n_new) : d->n_new;
+    return RM_OK;
+}
 
 } // namespace rmh

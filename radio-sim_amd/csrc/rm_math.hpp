@@ -232,6 +232,15 @@ RM_HD uint32_t fwd_backoff_factor(const uint64_t seed, const int32_t min_be, con
     return uint32_t(h2 >> (64 - be));
 }
 
+// the order of a queue's packets: the text the kernels' head search (rm_fwd.hip) and rm_fwd_queue_read are built from
+RM_HD bool fwd_packet_order(const rm_fwd_packet &a, const rm_fwd_packet &b)
+{
+    if (a.enq_us != b.enq_us) return a.enq_us < b.enq_us;
+    if (a.birth_us != b.birth_us) return a.birth_us < b.birth_us;
+    if (a.origin != b.origin) return a.origin < b.origin;
+    return a.hops < b.hops;
+}
+
 // the floods' Trickle schedule: what the parameters may hold, and interval m of a node that got the data
 // at first_us -- where it starts and when the node fires in it; m >= max_intervals: done, both -1.  The text the kernels
 // (rm_flood.hip), rm_flood_fire and rm_flood_validate are built from.  64-bit integers only.

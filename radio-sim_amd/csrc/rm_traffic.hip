@@ -119,30 +119,11 @@ __global__ void __launch_bounds__(64) k_traffic_write(const TrafficGen g)
     }
 }
 
-// window blockIdx.x: the first wave scans the column over the units, 64 at a time, in place; then all four waves pad the row
+// window blockIdx.x: its column of unit_count and its row of out_src (units_scan, rm_device.hpp)
 __global__ void __launch_bounds__(256) k_traffic_scan(const TrafficGen g)
 {
-    __shared__ int32_t s_total;
     const int b = blockIdx.x;
-    const int W = g.n_ticks;
-    if (threadIdx.x < 64) {
-        const int lane = threadIdx.x;
-        uint32_t carry = 0;
-        for (int u0 = 0; u0 < g.units; u0 += 64) {
-            const int u = u0 + lane;
-            const uint32_t v = u < g.units ? uint32_t(g.unit_count[size_t(u) * W + b]) : 0u;
-            const uint32_t inc = wave_inclusive_scan(v, lane);
-            if (u < g.units) g.unit_count[size_t(u) * W + b] = int32_t(carry + inc - v);
-            carry += __shfl(inc, 63);
-        }
-        if (lane == 0) {
-            s_total = int32_t(carry);
-            g.out_count[b] = int32_t(carry);
-        }
-    }
-    __syncthreads();
-    int32_t *row = g.out_src + size_t(b) * size_t(g.cap);
-    for (int p = min(s_total, g.cap) + int(threadIdx.x); p < g.cap; p += 256) row[p] = -1;
+    units_scan(g.units, g.n_ticks, g.cap, g.unit_count + b, g.out_src + size_t(b) * size_t(g.cap), g.out_count + b);
 }
 
 hipError_t launch_traffic_generate(hipStream_t s, const TrafficGen &g)

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 
 import flood_ref as F
+from test_gpu_fwd import cut_list, launches_added, multi_round_caps, multi_round_set
+from test_gpu_traffic import _bare
 from util import DeviceArray, KINDS, _PARAM_MAP
 
 pytestmark = pytest.mark.gpu
@@ -256,6 +258,54 @@ def test_to_fwd(O, make):
     rows, tot = eng.fwd_read()
     assert tot["arrived"] == 1 and tot["in_flight"] == 0 and int(rows["hops_sum"][n - 1]) == n - 1
     assert rows["next"].tolist() == [-2] + list(range(n - 1))
+
+
+# ---- the source list where a unit walks more than one round; kernel names and launches per call ------------------------------------
+
+def test_sources_of_units_of_several_rounds(rsa):
+    """a bare table of MULTI_ROUND nodes, no medium work, redundancy 0 (no advance has run: nothing is suppressed): the nodes of the
+    seeded set whose first fire time -- rm_flood_fire, the host rule -- has come, under caps that cut inside a later round of a unit.
+    A source list does not move an unsuppressed node on: the same call again gives the same list"""
+    n, nodes = multi_round_set()
+    params = rsa.Engine.flood_params(redundancy=0)
+    fire = {j: rsa.Engine.flood_fire(params, j, 0, 0)[1] for j in nodes}
+    t_mid, t_all = sorted(fire.values())[len(nodes) // 2], max(fire.values()) + 1
+    eng = _bare(rsa, n)
+    try:
+        eng.flood_enable(params)
+        eng.flood_seed(nodes, 0)
+        for t in (t_mid, t_all):
+            due = [j for j in nodes if fire[j] <= t]
+            assert (0 < len(due) < len(nodes)) if t == t_mid else due == nodes
+            for cap in multi_round_caps(len(nodes)):
+                for again in (False, True):
+                    got, count = eng.flood_sources(t, cap)
+                    assert count == len(due) and got.tolist() == cut_list(due, cap), (t, cap, again)
+        assert eng.flood_read()[1]["suppressed"] == 0
+    finally:
+        eng.close()
+
+
+def test_launches_per_call(rsa, O):
+    """a source list is three launches and an advance four, each kernel under its name once"""
+    nd = F.lattice_nodes()
+    eng = rsa.Engine(0)
+    src = DeviceArray(np.arange(0, nd.n, 3, dtype=np.int32))
+    try:
+        eng.upload_table(nd)
+        eng.set_model(KINDS["logdist"], **{_PARAM_MAP[k]: v for k, v in F.LATTICE.items()})
+        eng.profile_enable(1)
+        eng.flood_enable(imin_us=2)
+        eng.flood_seed(list(range(nd.n)), 0)
+        added = launches_added(eng, "k_flood_", lambda: eng.flood_sources(100, nd.n))
+        assert added == {"k_flood_src_count": 1, "k_flood_src_scan": 1, "k_flood_src_write": 1}, added
+        eng.tick_run_sources_device(0, F.TICK, src.ptr.value, 27, 100, F.AIR)
+        added = launches_added(eng, "k_flood_", lambda: eng.flood_advance(0))
+        assert added == {"k_flood_adv_claim": 1, "k_flood_rx_hear": 1, "k_flood_rx_pick": 1, "k_flood_settle": 1}, added
+        assert eng.flood_read()[1]["sent"] == 27
+    finally:
+        src.free()
+        eng.close()
 
 
 # ---- refusals ---------------------------------------------------------------------------------------------------------------------

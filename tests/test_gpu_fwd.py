@@ -9,6 +9,7 @@ import pytest
 
 import fwd_ref as F
 import hops_ref as H
+from test_gpu_traffic import MULTI_ROUND, _bare, _chunk
 from util import DeviceArray, KINDS, _PARAM_MAP
 
 pytestmark = pytest.mark.gpu
@@ -248,6 +249,129 @@ def test_chain(rsa, O, make):
     pk, ln = d.eng.fwd_queue_read()
     assert a[0].tobytes() == r.tobytes() and a[1] == tot and a[2].tobytes() == pk.tobytes() and a[3].tolist() == ln.tolist()
     assert tot["arrived"] >= 1 and tot["generated"] > 30
+
+
+# ---- the source list where a unit walks more than one round --------------------------------------------------------------------
+
+def multi_round_set():
+    """-> (n, the nodes of two whole units straddling node 65 536, every third node of the two units after them, and node n - 1) in a
+    table of MULTI_ROUND nodes, whose units walk two rounds of 64 nodes"""
+    n, chunk = MULTI_ROUND, _chunk(MULTI_ROUND)
+    first = 65536 - chunk
+    assert chunk == 128 and first % chunk == 0 and (n - 1) // chunk * chunk + 64 < n      # (the last unit's second round is partial)
+    return n, list(range(first, first + 2 * chunk)) + list(range(first + 2 * chunk, first + 4 * chunk, 3)) + [n - 1]
+
+
+def multi_round_caps(count):
+    """a cut in the second round of the first unit, in the second round of the second, at the units' end, none, and room to spare"""
+    chunk = _chunk(MULTI_ROUND)
+    return (64 + 36, chunk + 64 + 10, 2 * chunk, count, count + 44)
+
+
+def cut_list(nodes, cap):
+    """what a source list of `nodes` (ascending) holds under cap: cut at cap, -1 behind the count"""
+    return (nodes + [-1] * cap)[:cap]
+
+
+def test_sources_of_units_of_several_rounds(rsa):
+    """a bare table of MULTI_ROUND nodes, no medium work: the unit's running position carries over to its second round and cap cuts
+    inside a later round; count is the whole count every time"""
+    n, nodes = multi_round_set()
+    eng = _bare(rsa, n)
+    try:
+        eng.fwd_enable()
+        eng.fwd_set_next(np.arange(-1, n - 1), [0], 0)        # a line toward node 0
+        eng.fwd_inject(nodes, 0)
+        for cap in multi_round_caps(len(nodes)):
+            got, count = eng.fwd_sources(0, cap)
+            assert count == len(nodes) and got.tolist() == cut_list(nodes, cap), cap
+    finally:
+        eng.close()
+
+
+# ---- kernel names and launches per call, sampling ------------------------------------------------------------------------------
+
+def launches(eng, prefixes):
+    return {k: v[0] for k, v in eng.profile_kernels().items() if k.startswith(prefixes)}
+
+
+def launches_added(eng, prefix, call):
+    """what `call` adds to the sampled launches of the kernels named prefix*"""
+    before = launches(eng, prefix)
+    call()
+    return {k: v - before.get(k, 0) for k, v in launches(eng, prefix).items() if v != before.get(k, 0)}
+
+
+def lattice_engine(rsa, nd, every_n):
+    eng = rsa.Engine(0)
+    eng.upload_table(nd)
+    eng.set_model(KINDS["logdist"], **{_PARAM_MAP[k]: v for k, v in F.LATTICE.items()})
+    eng.profile_enable(every_n)
+    return eng
+
+
+def test_launches_per_call(rsa, O):
+    """a source list is three launches and an advance of a non-empty slot four, each kernel under its name once"""
+    nd = F.lattice_nodes()
+    eng = lattice_engine(rsa, nd, 1)
+    src = DeviceArray(np.arange(0, nd.n, 3, dtype=np.int32))
+    try:
+        eng.fwd_enable()
+        eng.fwd_set_next(np.arange(-1, nd.n - 1), [0], 0)
+        eng.fwd_inject(list(range(nd.n)), 0)
+        added = launches_added(eng, "k_fwd_", lambda: eng.fwd_sources(100, nd.n))
+        assert added == {"k_fwd_src_count": 1, "k_fwd_src_scan": 1, "k_fwd_src_write": 1}, added
+        eng.tick_run_sources_device(0, F.TICK, src.ptr.value, 27, 100, F.AIR)
+        added = launches_added(eng, "k_fwd_", lambda: eng.fwd_advance(0))
+        assert added == {"k_fwd_adv_claim": 1, "k_fwd_adv_match": 1, "k_fwd_adv_accept": 1, "k_fwd_adv_apply": 1}, added
+        assert eng.fwd_read()[1]["generated"] == nd.n
+    finally:
+        src.free()
+        eng.close()
+
+
+# what the interleaved calls of the test below launch: their kernels' names begin with one of these, no kernel of a tick's does
+FEATURE_KERNELS = ("k_fwd_", "k_flood_", "k_traffic_", "k_hop_", "k_nb_", "k_energy_")
+
+
+def _seven_ticks(rsa, nd, interleave):
+    """7 lone ticks under rm_profile_enable(3), the features on; interleave: a source list of either relay feature, a generated
+    traffic row, a hop query and an energy query between the ticks -> {kernel: sampled launches}"""
+    eng = lattice_engine(rsa, nd, 3)
+    src = DeviceArray(np.arange(0, nd.n, 3, dtype=np.int32))
+    try:
+        eng.fwd_enable()
+        eng.fwd_set_next(np.arange(-1, nd.n - 1), [0], 0)
+        eng.fwd_inject(list(range(nd.n)), 0)
+        eng.flood_enable(imin_us=2)
+        eng.flood_seed(list(range(nd.n)), 0)
+        eng.traffic_set(np.asarray(F.lattice_table(nd.n, 0), dtype=np.int64))
+        eng.profile_enable(3)                                   # (anew: nothing of the set-up above is in the record)
+        for k in range(7):
+            t = k * F.TICK
+            eng.tick_run_sources_device(t, t + F.TICK, src.ptr.value, 27, t + 100, F.AIR)
+            if interleave:
+                eng.fwd_sources(t + 100, nd.n)
+                eng.flood_sources(t + 100, nd.n)
+                eng.traffic_generate(5, [t], [t + F.TICK], nd.n)
+                eng.hops(H.HEARD_BY, [0])
+                eng.channel_energy(t + 500)
+        return launches(eng, "k_")
+    finally:
+        src.free()
+        eng.close()
+
+
+def test_feature_calls_do_not_move_the_ticks_sampling(rsa, O):
+    """every third launch sequence is sampled, and a call that is no tick puts the sequence count back: the ticks' kernels are
+    sampled as often with feature calls between the ticks as without; the calls themselves are sampled where the next tick is"""
+    nd = F.lattice_nodes()
+    plain, mixed = _seven_ticks(rsa, nd, False), _seven_ticks(rsa, nd, True)
+    ticks_of = lambda m: {k: v for k, v in m.items() if not k.startswith(FEATURE_KERNELS)}
+    assert ticks_of(plain) == plain and plain                     # (no feature kernel without a feature call)
+    assert ticks_of(mixed) == plain
+    for prefix in FEATURE_KERNELS:
+        assert any(k.startswith(prefix) for k in mixed), (prefix, sorted(mixed))
 
 
 # ---- refusals ---------------------------------------------------------------------------------------------------------------------
