@@ -1104,6 +1104,84 @@ int rm_routes_from_links(int32_t n_nodes, int32_t n_links, const int32_t *node, 
                          const rm_routes_params *params, double noise_dbm, const int32_t *roots, int32_t n_roots, const rm_routes_out *out,
                          rm_routes_totals *totals);
 
+/* ---- measured-route query: minimum-ETX routes over watched-link statistics ---------------------------------------------
+ * (not reference behaviour.)  What a collection protocol's link estimator and parent selection
+ * do with the counters of the watched links: a pure function of a watch table (peer, rm_link_stats), the parameters, the roots and
+ * optionally the current parents, in exact integer arithmetic.  The medium plays no part: accepted on every medium.
+ * Tables: peer and stats are [n_nodes][K], K = 1, 2, 4 or 8; peer[j][k] outside 0 .. n_nodes - 1 or equal to j is an empty slot; a
+ * far end may occur in several slots of a row.  tables == NULL: the context's own E14 tables as they stand on the stream.
+ * Entry (j, k) with far end p, H = heard, D = delivered is usable iff max(min_heard, 1) <= H <= 2^40 and D >= 1; its inbound cost
+ * is c_in = max(128, (128 * H + (D >> 1)) / D) in 64-bit unsigned arithmetic: the rounded ETX = 1 / PRR of the link p -> j as j
+ * measured it, in units of 1/128.
+ * RM_ETX_INBOUND: link (j, k) counts iff the entry is usable and c_in <= max_link_cost; c = c_in.
+ * RM_ETX_BOTH: with k' the lowest slot of row p whose peer is j, the link counts iff (j, k) counts under INBOUND, k' exists,
+ * (p, k') counts under INBOUND and c = (c_in(j, k) * c_in(p, k') + 64) >> 7 <= max_link_cost (ETX = 1 / (d_f * d_r)).
+ * cost[r] = 0 for every valid root; otherwise cost[j] is the minimum over j's counting links of cost[p] + c (the least fixed
+ * point); a node never reached has RM_ROUTE_UNREACHED.  For a reached node j that is no root: if cur != NULL, q = cur[j] is a
+ * node index, some slot k holds q with a counting link, cost[q] < cost[j] and cost[q] + c(j, k) <= cost[j] + hysteresis, then
+ * parent[j] = q, and among those slots the one with the least (c, k) gives slot[j] and link_cost[j] (the keep rule); otherwise
+ * among the counting links with cost[p] + c == cost[j] the one with the least (c, p, k) gives parent, slot and link_cost.  Roots and
+ * unreached nodes have parent -1, slot -1, link_cost 0.  children[p] is the number of nodes whose parent is p.  Every parent has
+ * a strictly smaller cost than its child: the parent array is loop-free for every hysteresis.  cur may be the buffer of
+ * out->parent.  Totals: reached, roots (distinct valid roots), max_cost (0 when nothing is reached); with "valid" a cur[j] inside
+ * the table: kept the reached non-roots with parent == cur[j], switched those with a valid cur[j] != parent, lost the unreached
+ * nodes with a valid cur[j]; all three 0 without cur.  A query changes nothing but its outputs and scratch of its own.  parent is a
+ * valid argument of rm_fwd_set_next_device, of rm_hops_next_device and of a K = 1 rm_linkstats_watch_device. */
+#define RM_ETX_INBOUND 0
+#define RM_ETX_BOTH 1
+typedef struct rm_etx_tables {
+    const int32_t *peer;        /* [n_nodes][K], aligned to 4 K bytes */
+    const rm_link_stats *stats; /* [n_nodes][K], aligned to 8 bytes */
+    int32_t K;                  /* 1, 2, 4 or 8 */
+    int32_t reserved;           /* 0 */
+} rm_etx_tables;
+typedef struct rm_etx_params {
+    int32_t mode;           /* RM_ETX_INBOUND / RM_ETX_BOTH */
+    int32_t reserved;       /* 0 */
+    uint32_t min_heard;     /* 0 .. 2^31: an entry with fewer heard frames is not usable */
+    uint32_t max_link_cost; /* 128 .. 65535: a link whose cost is above it does not count */
+    uint32_t hysteresis;    /* 0 .. 65535, in units of 1/128: how much worse than the least cost the current parent's path may be */
+    uint32_t reserved2;     /* 0 */
+} rm_etx_params;            /* 24 bytes */
+/* the outputs, [n_nodes] each, by node index: cost is required, the others may be NULL */
+typedef struct rm_etx_out { uint64_t *cost; int32_t *parent; int32_t *slot; uint32_t *link_cost; int32_t *children; } rm_etx_out;
+typedef struct rm_etx_totals { int32_t reached, roots, kept, switched, lost, reserved; uint64_t max_cost; } rm_etx_totals;
+/* RM_ETX_INBOUND, min_heard 4, max_link_cost 2048, hysteresis 192 */
+void rm_etx_defaults(rm_etx_params *params);
+/* RM_OK or RM_ERR_INVALID (NULL, an unknown mode, a field outside its range, a reserved field that is not 0) */
+int rm_etx_validate(const rm_etx_params *params);
+/* tables (a host struct, or NULL), dev_roots, dev_cur (or NULL) and the arrays dev_out (a host struct) points to are device
+ * memory; a root entry outside 0 .. n_nodes - 1 is ignored.  The call waits on the context's stream once per round and returns
+ * when the outputs are complete; totals (host) may be NULL.  Nothing is validated on the device: any table content is defined.
+ * RM_ERR_STATE, nothing launched: NULL tables while E14 is off or on a context with a receiver partition, between rm_tick_begin
+ * and rm_tick_flush, a context made under RM_GRAPH=1.  RM_ERR_INVALID: NULL ctx, params, dev_out or cost, what rm_etx_validate
+ * refuses, explicit tables with K outside {1, 2, 4, 8}, reserved != 0, a NULL or misaligned peer or stats, n_roots < 0, n_roots > 0
+ * with NULL roots.  A context without nodes: RM_OK with empty totals.
+ * Cost: one launch and one wait on the stream per round, and the rounds are at least the tree's depth in links.  On a shallow
+ * graph (a field: hundreds of rounds at a million nodes) that is several times faster than reading the table to the host; on a
+ * graph tens of thousands of links deep (a line, a band) it is 12 to 64 times SLOWER than rm_etx_from_tables over the same
+ * table: a caller with such a table copies it out and calls that. */
+int rm_etx_query_device(rm_context *ctx, const rm_etx_params *params, const rm_etx_tables *tables, const int32_t *dev_roots, int32_t n_roots,
+                        const int32_t *dev_cur, const rm_etx_out *dev_out, rm_etx_totals *totals);
+/* the same with host arrays (explicit tables are host arrays of any alignment); a root outside the table is RM_ERR_INVALID before
+ * anything is launched */
+int rm_etx_query(rm_context *ctx, const rm_etx_params *params, const rm_etx_tables *tables, const int32_t *roots, int32_t n_roots,
+                 const int32_t *cur, const rm_etx_out *out, rm_etx_totals *totals);
+/* what the context's last completed measured-route query did, for measurements: its relaxation rounds (launches) and the nodes
+ * they examined in all; 0 and 0 before the first query.  Either may be NULL.  Both may vary from run to run; the answer may not. */
+int rm_etx_last_work(rm_context *ctx, int32_t *rounds, uint64_t *examined);
+/* INBOUND's rule for one entry, a pure host function without a device: 1 and *cost when an entry with these counters counts under
+ * params, else 0 -- not usable, a cost above the cap, or parameters rm_etx_validate refuses.  mode is not looked at; cost may be
+ * NULL. */
+int rm_etx_link_cost(const rm_etx_params *params, uint64_t heard, uint64_t delivered, uint32_t *cost);
+/* BOTH's product of two inbound costs, (c_in * c_rev + 64) >> 7 in 64-bit arithmetic, a pure host function */
+uint64_t rm_etx_combine(uint32_t c_in, uint32_t c_rev);
+/* The same rule on the host by a heap Dijkstra, a pure host function without a device: tables (required), roots, cur (or NULL) and
+ * out are host arrays.  RM_ERR_INVALID: what the query's argument checks refuse (alignment aside), n_nodes < 0, a root outside the
+ * table. */
+int rm_etx_from_tables(int32_t n_nodes, const rm_etx_tables *tables, const rm_etx_params *params, const int32_t *roots, int32_t n_roots,
+                       const int32_t *cur, const rm_etx_out *out, rm_etx_totals *totals);
+
 /* ---- forwarding queues: multi-hop packet relay on the device ------------------------------------------------------------------
  * (not reference behaviour.)  Per-node packet queues in device memory and the calls that move
  * packets along a next-hop table from one evaluated tick to the next.  No evaluating call changes: every call here reads a FINISHED

@@ -19,5 +19,6 @@ from ._lib import (MODEL_NULL, MODEL_UDGM, MODEL_UDGM_CONST, MODEL_N2N, MODEL_LO
                    ListenSchedule, LISTEN_SCHEDULE_DTYPE, LinkStats, LINK_STATS_DTYPE,
                    TrafficSchedule, TrafficTotals, TRAFFIC_SCHEDULE_DTYPE, UnicastOut, UC_NONE, UC_NOT_SENT, UC_UNHEARD, UC_INTERFERED,
                    UC_DELIVERED, UC_LOST, NB_HEARD_BY, NB_HEARS, NB_MAX_K, HopsOut, HopsTotals,
-                   RoutesParams, RoutesOut, RoutesTotals, ROUTE_UNREACHED)
+                   RoutesParams, RoutesOut, RoutesTotals, ROUTE_UNREACHED,
+                   ETX_INBOUND, ETX_BOTH, EtxTables, EtxParams, EtxOut, EtxTotals)
 from .engine import Engine, Group  # noqa: F401

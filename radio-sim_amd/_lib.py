@@ -106,6 +106,34 @@ class RoutesTotals(C.Structure):
 ROUTES_FIELDS = (("cost", np.uint64), ("parent", np.int32), ("rssi", np.float64), ("link_cost", np.uint32), ("children", np.int32))
 ROUTE_UNREACHED = 0xFFFFFFFFFFFFFFFF
 
+ETX_INBOUND, ETX_BOTH = 0, 1
+
+
+class EtxTables(C.Structure):
+    """rm_etx_tables: a watch table of the measured-route query, peer and stats [n_nodes][K]"""
+    _fields_ = [("peer", C.c_void_p), ("stats", C.c_void_p), ("K", C.c_int32), ("reserved", C.c_int32)]
+
+
+class EtxParams(C.Structure):
+    """rm_etx_params (24 bytes)"""
+    _fields_ = [("mode", C.c_int32), ("reserved", C.c_int32), ("min_heard", C.c_uint32), ("max_link_cost", C.c_uint32),
+                ("hysteresis", C.c_uint32), ("reserved2", C.c_uint32)]
+
+
+class EtxOut(C.Structure):
+    """rm_etx_out: the output arrays of the measured-route query, [n_nodes] each; all but cost may be NULL"""
+    _fields_ = [("cost", C.c_void_p), ("parent", C.c_void_p), ("slot", C.c_void_p), ("link_cost", C.c_void_p), ("children", C.c_void_p)]
+
+
+class EtxTotals(C.Structure):
+    """rm_etx_totals"""
+    _fields_ = [("reached", C.c_int32), ("roots", C.c_int32), ("kept", C.c_int32), ("switched", C.c_int32), ("lost", C.c_int32),
+                ("reserved", C.c_int32), ("max_cost", C.c_uint64)]
+
+
+assert C.sizeof(EtxParams) == 24 and C.sizeof(EtxTotals) == 32
+ETX_FIELDS = (("cost", np.uint64), ("parent", np.int32), ("slot", np.int32), ("link_cost", np.uint32), ("children", np.int32))
+
 
 class FwdParams(C.Structure):
     """rm_fwd_params: the forwarding queues' parameters (40 bytes)"""
@@ -456,6 +484,17 @@ SIGNATURES = {
     "rm_routes_link_cost": (C.c_int, [C.POINTER(RoutesParams), C.c_double, C.c_double, C.POINTER(C.c_uint32)]),
     "rm_routes_from_links": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RoutesParams), C.c_double, C.c_void_p,
                                        C.c_int32, C.POINTER(RoutesOut), C.POINTER(RoutesTotals)]),
+    "rm_etx_defaults": (None, [C.POINTER(EtxParams)]),
+    "rm_etx_validate": (C.c_int, [C.POINTER(EtxParams)]),
+    "rm_etx_query_device": (C.c_int, [C.c_void_p, C.POINTER(EtxParams), C.POINTER(EtxTables), C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(EtxOut),
+                                      C.POINTER(EtxTotals)]),
+    "rm_etx_query": (C.c_int, [C.c_void_p, C.POINTER(EtxParams), C.POINTER(EtxTables), C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(EtxOut),
+                               C.POINTER(EtxTotals)]),
+    "rm_etx_last_work": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
+    "rm_etx_link_cost": (C.c_int, [C.POINTER(EtxParams), C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]),
+    "rm_etx_combine": (C.c_uint64, [C.c_uint32, C.c_uint32]),
+    "rm_etx_from_tables": (C.c_int, [C.c_int32, C.POINTER(EtxTables), C.POINTER(EtxParams), C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(EtxOut),
+                                     C.POINTER(EtxTotals)]),
     "rm_fwd_defaults": (None, [C.POINTER(FwdParams)]),
     "rm_fwd_validate": (C.c_int, [C.POINTER(FwdParams)]),
     "rm_fwd_backoff": (C.c_int, [C.POINTER(FwdParams), C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),

@@ -129,6 +129,7 @@ void passes_release(rm_context *c)
     neighbors_release(c);
     hops_release(c);
     routes_release(c);
+    etx_release(c);
     fwd_release(c);
     flood_release(c);
 }

@@ -1052,6 +1052,42 @@ hipError_t launch_route_parent(hipStream_t s, const NodesDev &nd, const ModelDev
 // sums[0] += the reached nodes, sums[1] = max(sums[1], the largest finite cost); sums zeroed by the caller
 hipError_t launch_route_totals(hipStream_t s, const RouteDev &r, int n);
 
+// (rm_etx.hip) the measured-route query.  peer / stats: the watch table, [n][K], a peer row
+// aligned to its 4 K bytes.  lc [n][K]: every entry's link cost, 0 where it does not count (launch_etx_cost writes it, the rounds
+// and the parent pass read it and never the stats).  stamp [n]: the round after the one that last lowered the node (roots: 1; else
+// 0).  The outputs are [n] by node index (all but cost may be nullptr); cur (nullptr or [n]) may be the buffer of parent.
+// words: [0] and [1] the rounds' counters by round parity (examined << 32 | lowered), [2] reached, [3] max_cost, [4] roots,
+// [5] kept, [6] switched, [7] lost.
+struct EtxDev {
+    const int32_t *peer;
+    const rm_link_stats *stats;
+    uint32_t *lc;
+    uint32_t *stamp;
+    unsigned long long *cost;
+    int32_t *parent;
+    int32_t *slot;
+    uint32_t *link_cost;
+    int32_t *children;
+    const int32_t *cur;
+    unsigned long long *words;
+    int n, K;
+    int mode;
+    uint32_t min_heard, max_link_cost, hysteresis;
+};
+constexpr int kEtxWords = 8;
+// lc for all n * K entries, BOTH's reverse lookup included
+hipError_t launch_etx_cost(hipStream_t s, const EtxDev &e);
+// cost as "nothing reached" and the stamps 0, then the roots (device memory, entries outside the table skipped) with cost 0 and
+// stamp 1
+hipError_t launch_etx_seed(hipStream_t s, const EtxDev &e, const int32_t *roots, int n_roots);
+// round r >= 1: a lane per node; a node with a peer of stamp r takes the least cost its counting links offer and, if that lowers
+// its own, stores it with stamp r + 1.  words[r & 1] += examined << 32 | lowered; words[(r & 1) ^ 1] = 0 for the round after
+hipError_t launch_etx_relax(hipStream_t s, const EtxDev &e, int round);
+// parent, slot, link_cost and children of every node (children zeroed in front of it on the stream), and kept / switched / lost
+hipError_t launch_etx_parent(hipStream_t s, const EtxDev &e);
+// words[2] += the reached nodes, words[3] = max(words[3], the largest finite cost), words[4] += the nodes of cost 0
+hipError_t launch_etx_totals(hipStream_t s, const EtxDev &e);
+
 // (rm_unicast.hip) the unicast outcome query, one launch: a lane per entry.  n_slots result slots described by dev_slots -- or, with
 // dev_slots == nullptr, the one slot `lone`.  Slots form (dev_prefix: [n_slots + 1] exclusive prefix of the entries per slot; nullptr
 // with one slot): entry e is packet e - prefix[b] of slot b.  At form: entry e names (dev_slot[e], dev_pkt[e]).

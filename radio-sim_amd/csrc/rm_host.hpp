@@ -262,6 +262,17 @@ struct rm_context : TickSlot {
         int32_t last_rounds = 0;   // the last query's relaxation launches and the frontier entries they walked (rm_routes_last_work)
         uint64_t last_entries = 0;
     } rt;
+    // the measured-route query (E21; rm_api_etx.cpp, rm_etx.hip): every entry's link cost ([n_nodes][K]), the per-node round
+    // stamps, the word block (rm::kEtxWords, zeroed per query) and the pinned words a round's counter and the totals are copied
+    // to.  Nothing is allocated before the first query.
+    struct Etx {
+        DevBuf<uint32_t> lc;
+        DevBuf<uint32_t> stamp;
+        DevBuf<unsigned long long> words;
+        unsigned long long *h_words = nullptr;
+        int32_t last_rounds = 0;    // the last query's relaxation launches and the nodes they examined (rm_etx_last_work)
+        uint64_t last_examined = 0;
+    } etx;
     // traffic schedules (E15; rm_api_traffic.cpp, rm_traffic.hip): one schedule per node index; the pinned, host-mapped block a list
     // update or a list read is staged through; the generator's scratch (the windows, the units' counts and packets) and the pinned
     // staging of its windows -- two blocks, each rewritten only after its copy has completed
@@ -872,6 +883,10 @@ void hops_release(rm_context *c);
 // ---- rm_api_routes.cpp: the route query (E18)
 // rm_destroy
 void routes_release(rm_context *c);
+
+// ---- rm_api_etx.cpp: the measured-route query (E21)
+// rm_destroy
+void etx_release(rm_context *c);
 
 // ---- rm_api_traffic.cpp: traffic schedules (E15)
 // rm_nodes_upload: another node count clears the feature

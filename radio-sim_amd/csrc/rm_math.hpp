@@ -173,6 +173,27 @@ RM_HD bool route_link_cost(int kind, double us_per_bit, int64_t air_us, double n
     return true;
 }
 
+// the measured-route query's entry cost: the rounded 128 * heard / delivered of one watched-link entry
+// -- the text the kernels (rm_etx.hip) and rm_etx_link_cost / rm_etx_from_tables are both built from.  false: the entry is not
+// usable or its cost is above the cap.  128 * H <= 2^47 and D >> 1 < 2^63: the sum cannot wrap.
+RM_HD bool etx_entry_cost(uint32_t min_heard, uint32_t max_link_cost, uint64_t heard, uint64_t delivered, uint32_t &cost)
+{
+    const uint64_t least = min_heard > 1u ? uint64_t(min_heard) : 1ull;
+    if (heard < least || heard > (1ull << 40) || delivered < 1ull) return false;
+    uint64_t q = (128ull * heard + (delivered >> 1)) / delivered;
+    if (q < 128ull) q = 128ull; // (a caller's table with delivered > heard)
+    if (q > uint64_t(max_link_cost)) return false;
+    cost = uint32_t(q);
+    return true;
+}
+// RM_ETX_BOTH: the product of the two directions' inbound costs, in units of 1/128
+RM_HD uint64_t etx_combine(uint32_t c_in, uint32_t c_rev) { return (uint64_t(c_in) * uint64_t(c_rev) + 64ull) >> 7; }
+// the order of two candidate links of one node: (c, p, k) ascending
+RM_HD bool etx_precedes(uint32_t c, int32_t p, int k, uint32_t bc, int32_t bp, int bk)
+{
+    return c < bc || (c == bc && (p < bp || (p == bp && k < bk)));
+}
+
 // the link's uniform deviate: a hash of (seed, the frame's start, its source node, the receiver) and of nothing else -- not of
 // packet numbers, ticks, slots or ranks, so a frame's verdict at a receiver is the same however the frame was evaluated
 RM_HD double em_draw(uint64_t seed, int32_t src, int64_t start_us, int32_t dst)

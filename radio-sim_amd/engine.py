@@ -646,6 +646,108 @@ class Engine:
                                               _ptr(idx), idx.shape[0], C.byref(st), C.byref(tot)))
         return out, Engine._routes_totals(tot)
 
+    # -- measured-route query: minimum-ETX routes over watched-link statistics
+    @staticmethod
+    def etx_params(**kw):
+        """rm_etx_defaults with the given fields replaced: mode, min_heard, max_link_cost, hysteresis (and the reserved ones)"""
+        p = _lib.EtxParams()
+        _lib.lib().rm_etx_defaults(C.byref(p))
+        for k, v in kw.items():
+            if k not in dict(_lib.EtxParams._fields_):
+                raise TypeError("rm_etx_params has no field " + k)
+            setattr(p, k, int(v))
+        return p
+
+    @staticmethod
+    def etx_validate(params):
+        """rm_etx_validate (pure host): 0 when the query would accept the parameters"""
+        return int(_lib.lib().rm_etx_validate(C.byref(params)))
+
+    @staticmethod
+    def _etx_out(n, fields):
+        out = {name: np.empty(n, dtype=dt) for name, dt in _lib.ETX_FIELDS if name == "cost" or fields is None or name in fields}
+        return out, _lib.EtxOut(**{name: a.ctypes.data for name, a in out.items()})
+
+    @staticmethod
+    def _etx_totals(tot):
+        return {k: int(getattr(tot, k)) for k in ("reached", "roots", "kept", "switched", "lost", "max_cost")}
+
+    @staticmethod
+    def _etx_tables(tables, keep):
+        """(peer [n][K], stats [n][K] of LINK_STATS_DTYPE) as host arrays -> an rm_etx_tables over contiguous copies (held in keep)"""
+        peer = np.ascontiguousarray(tables[0], dtype=np.int32)
+        stats = np.ascontiguousarray(tables[1], dtype=_lib.LINK_STATS_DTYPE)
+        if peer.ndim != 2 or stats.shape != peer.shape:
+            raise ValueError("peer and stats are [n_nodes][K]")
+        keep += [peer, stats]
+        return _lib.EtxTables(peer=peer.ctypes.data, stats=stats.ctypes.data, K=peer.shape[1], reserved=0)
+
+    def etx_routes(self, params, roots, tables=None, cur=None, fields=None):
+        """rm_etx_query: least measured-ETX path cost (units of 1/128) toward the roots over a watch table and the parent on it,
+        the current parent kept within params.hysteresis -> ({"cost": uint64[n] (ROUTE_UNREACHED: not reached), "parent":
+        int32[n], "slot": int32[n], "link_cost": uint32[n], "children": int32[n]}, {"reached", "roots", "kept", "switched", "lost",
+        "max_cost"}).  tables: None (the context's own watched-link tables) or (peer [n][K], stats [n][K]); cur: None or the
+        current parents int32[n]; params: etx_params(...)"""
+        keep = []
+        n = max(int(self._L.rm_node_count(self._h)), 0)
+        idx = np.ascontiguousarray(roots, dtype=np.int32).reshape(-1)
+        t = None if tables is None else self._etx_tables(tables, keep)
+        if t is not None and keep[0].shape[0] != n:
+            raise ValueError("one row of the tables per node")
+        c = None if cur is None else np.ascontiguousarray(cur, dtype=np.int32).reshape(-1)
+        if c is not None and c.shape[0] != n:
+            raise ValueError("one current parent per node")
+        out, st = self._etx_out(n, fields)
+        tot = _lib.EtxTotals()
+        check(self._L.rm_etx_query(self._h, C.byref(params), None if t is None else C.byref(t), _ptr(idx), idx.shape[0], _ptr(c), C.byref(st),
+                                   C.byref(tot)))
+        return out, self._etx_totals(tot)
+
+    def etx_routes_device(self, params, dev_roots_ptr, n_roots, dev_cost_ptr, dev_parent_ptr=None, dev_slot_ptr=None, dev_link_cost_ptr=None,
+                          dev_children_ptr=None, dev_cur_ptr=None, dev_tables=None):
+        """rm_etx_query_device: the raw form -- roots, cur (or None), outputs (uint64[n], int32[n], int32[n], uint32[n], int32[n];
+        all but the first may be None) and dev_tables (None: the context's own, or (peer pointer, stats pointer, K)) in device
+        memory; dev_cur_ptr may be dev_parent_ptr; waits once per round, complete on return -> the totals"""
+        st = _lib.EtxOut(cost=dev_cost_ptr, parent=dev_parent_ptr, slot=dev_slot_ptr, link_cost=dev_link_cost_ptr, children=dev_children_ptr)
+        t = None if dev_tables is None else _lib.EtxTables(peer=dev_tables[0], stats=dev_tables[1], K=int(dev_tables[2]), reserved=0)
+        tot = _lib.EtxTotals()
+        check(self._L.rm_etx_query_device(self._h, C.byref(params), None if t is None else C.byref(t), dev_roots_ptr, int(n_roots), dev_cur_ptr,
+                                          C.byref(st), C.byref(tot)))
+        return self._etx_totals(tot)
+
+    def etx_last_work(self):
+        """rm_etx_last_work: (relaxation rounds, nodes examined in all) of the last completed measured-route query"""
+        rounds, examined = C.c_int32(0), C.c_uint64(0)
+        check(self._L.rm_etx_last_work(self._h, C.byref(rounds), C.byref(examined)))
+        return int(rounds.value), int(examined.value)
+
+    @staticmethod
+    def etx_link_cost(params, heard, delivered):
+        """rm_etx_link_cost (pure host function): the inbound cost of an entry with these counters, or None when it does not count"""
+        c = C.c_uint32(0)
+        return int(c.value) if _lib.lib().rm_etx_link_cost(C.byref(params), int(heard), int(delivered), C.byref(c)) else None
+
+    @staticmethod
+    def etx_combine(c_in, c_rev):
+        """rm_etx_combine (pure host function): RM_ETX_BOTH's cost of two inbound costs"""
+        return int(_lib.lib().rm_etx_combine(int(c_in), int(c_rev)))
+
+    @staticmethod
+    def etx_from_tables(tables, params, roots, cur=None, fields=None):
+        """rm_etx_from_tables (pure host function, a heap Dijkstra): the same rule over (peer [n][K], stats [n][K]) -> what
+        etx_routes returns"""
+        keep = []
+        t = Engine._etx_tables(tables, keep)
+        n = keep[0].shape[0]
+        idx = np.ascontiguousarray(roots, dtype=np.int32).reshape(-1)
+        c = None if cur is None else np.ascontiguousarray(cur, dtype=np.int32).reshape(-1)
+        if c is not None and c.shape[0] != n:
+            raise ValueError("one current parent per node")
+        out, st = Engine._etx_out(n, fields)
+        tot = _lib.EtxTotals()
+        check(_lib.lib().rm_etx_from_tables(n, C.byref(t), C.byref(params), _ptr(idx), idx.shape[0], _ptr(c), C.byref(st), C.byref(tot)))
+        return out, Engine._etx_totals(tot)
+
     def linkstats_watch_device(self, dev_peers_ptr, dev_nodes_ptr=None, n=None):
         """rm_linkstats_watch_device: rm_linkstats_watch with rows (int32[n][K] of the enabled K) and list in device memory (None: all
         nodes) -- e.g. the peer block of neighbors_device(NB_HEARS, K); validated on the device, waited for"""

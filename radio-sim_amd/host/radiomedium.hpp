@@ -745,6 +745,57 @@ public:
         }
         return out;
     }
+    // The measured-route query (extension E21): least path cost (measured ETX in units of 1/128) toward a set of roots over the
+    // watched links' counters as they stand, and the parent on such a path -- the current parent (current[i] for node i of
+    // Simulator.getNodes(), nullptr: none; an empty list: no current parents) kept while its path is within params.hysteresis of
+    // the least cost.  tables: the caller's own watch table (host arrays, a row per node) in place of the medium's.  One row per
+    // node in node order; empty rows and lastError on a refusal (without tables, setLinkWatch(K) comes first).
+    struct MeasuredRouteRow {
+        uint64_t cost; // RM_ROUTE_UNREACHED: not reached
+        Node *parent;  // nullptr for a root and for a node that was not reached
+        int slot;      // the watch slot of the link to the parent, -1 without one
+        uint32_t linkCost;
+        int children;
+    };
+    struct MeasuredRouteTree {
+        std::vector<MeasuredRouteRow> rows;
+        rm_etx_totals totals;
+    };
+    static rm_etx_params measuredRouteDefaults()
+    {
+        rm_etx_params p;
+        rm_etx_defaults(&p);
+        return p;
+    }
+    MeasuredRouteTree measuredRoutes(const rm_etx_params &params, const std::vector<const Node *> &roots, const std::vector<const Node *> &current = {},
+                                     const rm_etx_tables *tables = nullptr)
+    {
+        lastError.clear();
+        MeasuredRouteTree tree{{}, {0, 0, 0, 0, 0, 0, 0}};
+        if (!simulator || !syncNodes()) return tree;
+        const std::vector<Node *> &all = simulator->getNodes();
+        const size_t n = all.size();
+        if (!current.empty() && current.size() != n) {
+            lastError = "measuredRoutes: one current parent (or nullptr) per node";
+            return tree;
+        }
+        std::vector<int32_t> idx, cur;
+        for (const Node *nd : roots) idx.push_back(nd ? nd->index : -1);
+        for (const Node *nd : current) cur.push_back(nd ? nd->index : -1);
+        std::vector<uint64_t> cost(n + 1);
+        std::vector<int32_t> parent(n + 1), slot(n + 1), children(n + 1);
+        std::vector<uint32_t> linkCost(n + 1);
+        const rm_etx_out out{cost.data(), parent.data(), slot.data(), linkCost.data(), children.data()};
+        if (rm_etx_query(ctx_, &params, tables, idx.data(), int32_t(idx.size()), cur.empty() ? nullptr : cur.data(), &out, &tree.totals) != RM_OK) {
+            lastError = rm_last_error();
+            tree.totals = {0, 0, 0, 0, 0, 0, 0};
+            return tree;
+        }
+        tree.rows.resize(n);
+        for (size_t j = 0; j < n; ++j)
+            tree.rows[j] = MeasuredRouteRow{cost[j], parent[j] >= 0 ? all[size_t(parent[j])] : nullptr, slot[j], linkCost[j], children[j]};
+        return tree;
+    }
     // Forwarding queues (extension E19): per-node packet queues and a next-hop table on the device; packets move one hop per
     // evaluated tick.  setForwarding(&params) makes the queues (nullptr: releases them); setNextHops gives every node its next hop
     // (parents[i] for node i of Simulator.getNodes(), nullptr: no route) and makes the listed nodes sinks; forwardInject puts one
