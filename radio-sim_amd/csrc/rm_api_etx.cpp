@@ -4,11 +4,8 @@
 //
 // The query READS a watch table -- the context's own (E14) or the caller's -- and writes the caller's outputs and scratch of its
 // own (rm_context::Etx).  The node table, the model and the medium play no part.
-#include "rm_host.hpp"
+#include "rm_query.hpp"
 #include "rm_math.hpp"
-
-#include <limits>
-#include <queue>
 
 using namespace rmh;
 
@@ -19,8 +16,7 @@ void etx_release(rm_context *c)
     c->etx.lc.release();
     c->etx.stamp.release();
     c->etx.words.release();
-    if (c->etx.h_words) (void)hipHostFree(c->etx.h_words);
-    c->etx.h_words = nullptr;
+    c->etx.h.release();
 }
 
 static int etx_params_check(const rm_etx_params *p)
@@ -53,8 +49,7 @@ static int etx_check(rm_context *c, const rm_etx_params *p, const rm_etx_tables 
     if (!out || !out->cost) return fail(RM_ERR_INVALID, "out or out->cost is NULL");
     RM_TRY(etx_params_check(p));
     if (t) RM_TRY(etx_tables_check(t, aligned));
-    if (n_roots < 0) return fail(RM_ERR_INVALID, "negative root count");
-    if (n_roots > 0 && !roots) return fail(RM_ERR_INVALID, "roots is NULL");
+    RM_TRY(roots_check(roots, n_roots));
     if (c->in_tick) return fail(RM_ERR_STATE, "rm_etx_query between rm_tick_begin and rm_tick_flush");
     RM_TRY(graphs_refuse(c, "the measured-route query is not part of them"));
     if (!t) {
@@ -86,13 +81,8 @@ static int etx_run(rm_context *c, const rm_etx_params &p, const rm_etx_tables *t
             e.K = ld.K;
         }
         const size_t n = size_t(c->n), nk = n * size_t(e.K);
-        if (x.lc.n < nk || x.stamp.n < n || x.words.n < size_t(rm::kEtxWords) || !x.h_words) {
-            RM_HIP(hipStreamSynchronize(c->stream)); // (an earlier query may still read the old blocks)
-            RM_HIP(x.lc.ensure(nk));
-            RM_HIP(x.stamp.ensure(n));
-            RM_HIP(x.words.ensure(size_t(rm::kEtxWords)));
-            if (!x.h_words) RM_HIP(hipHostMalloc(reinterpret_cast<void **>(&x.h_words), 64, hipHostMallocMapped));
-        }
+        RM_TRY(grow(c, need(x.lc, nk), need(x.stamp, n), need(x.words, size_t(rm::kEtxWords))));
+        RM_HIP(x.h.ensure());
         RM_HIP(hipMemsetAsync(x.words.p, 0, size_t(rm::kEtxWords) * sizeof(unsigned long long), c->stream));
         e.lc = x.lc.p;
         e.stamp = x.stamp.p;
@@ -116,26 +106,24 @@ static int etx_run(rm_context *c, const rm_etx_params &p, const rm_etx_tables *t
         // a round that lowered nobody ends the query: the costs are a fixed point.  One launch, one 8-byte copy, one wait per round
         for (int round = 1; n_roots > 0; ++round) {
             RM_HIP(rm::launch_etx_relax(c->stream, e, round));
-            RM_HIP(hipMemcpyAsync(x.h_words, e.words + (round & 1), sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-            RM_HIP(hipStreamSynchronize(c->stream));
+            RM_TRY(x.h.read(c->stream, e.words + (round & 1), sizeof(unsigned long long)));
             ++x.last_rounds;
-            x.last_examined += uint64_t(x.h_words[0] >> 32);
-            if (uint32_t(x.h_words[0]) == 0u) break;
+            x.last_examined += uint64_t(x.h.p[0] >> 32);
+            if (x.h.low() == 0u) break;
         }
         if (out.parent || out.slot || out.link_cost || out.children || cur) {
             if (out.children) RM_HIP(hipMemsetAsync(out.children, 0, n * sizeof(int32_t), c->stream));
             RM_HIP(rm::launch_etx_parent(c->stream, e));
         }
         RM_HIP(rm::launch_etx_totals(c->stream, e));
-        RM_HIP(hipMemcpyAsync(x.h_words, e.words + 2, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        RM_HIP(hipStreamSynchronize(c->stream));
-        const unsigned long long top = (unsigned long long)c->n;
-        tt.reached = int32_t(std::min(x.h_words[0], top));
-        tt.max_cost = x.h_words[1];
-        tt.roots = int32_t(std::min(x.h_words[2], top));
-        tt.kept = int32_t(std::min(x.h_words[3], top));
-        tt.switched = int32_t(std::min(x.h_words[4], top));
-        tt.lost = int32_t(std::min(x.h_words[5], top));
+        RM_TRY(x.h.read(c->stream, e.words + 2, 6 * sizeof(unsigned long long)));
+        const unsigned long long top = (unsigned long long)c->n, *w = x.h.p;
+        tt.reached = int32_t(std::min(w[0], top));
+        tt.max_cost = w[1];
+        tt.roots = int32_t(std::min(w[2], top));
+        tt.kept = int32_t(std::min(w[3], top));
+        tt.switched = int32_t(std::min(w[4], top));
+        tt.lost = int32_t(std::min(w[5], top));
     }
     if (totals) *totals = tt;
     return RM_OK;
@@ -191,8 +179,7 @@ int rm_etx_query(rm_context *c, const rm_etx_params *params, const rm_etx_tables
                  const rm_etx_out *out, rm_etx_totals *totals)
 {
     RM_TRY(etx_check(c, params, tables, false, roots, n_roots, out));
-    for (int32_t k = 0; k < n_roots; ++k)
-        if (roots[k] < 0 || roots[k] >= c->n) return fail(RM_ERR_INVALID, "root index out of range");
+    RM_TRY(roots_in_table(roots, n_roots, c->n));
     if (c->n < 1) {
         if (totals) *totals = rm_etx_totals{0, 0, 0, 0, 0, 0, 0};
         return RM_OK;
@@ -200,40 +187,31 @@ int rm_etx_query(rm_context *c, const rm_etx_params *params, const rm_etx_tables
     RM_HIP(hipSetDevice(c->device));
     // the call's device block lives for this call only: cost, parent, slot, link_cost, children, cur, roots, and the caller's tables
     const size_t n = size_t(c->n), nk = tables ? n * size_t(tables->K) : 0;
-    const size_t o_par = pad64(n * 8), o_slot = o_par + pad64(n * 4), o_lc = o_slot + pad64(n * 4), o_chl = o_lc + pad64(n * 4),
-                 o_cur = o_chl + pad64(n * 4), o_roots = o_cur + pad64(n * 4), o_peer = o_roots + pad64(size_t(std::max(n_roots, 1)) * 4),
-                 o_stats = o_peer + pad64(nk * 4), total = o_stats + pad64(nk * sizeof(rm_link_stats));
-    char *d = nullptr;
-    RM_HIP(hipMalloc(reinterpret_cast<void **>(&d), total));
-    rm_etx_out dv{};
-    dv.cost = reinterpret_cast<uint64_t *>(d);
-    dv.parent = out->parent ? reinterpret_cast<int32_t *>(d + o_par) : nullptr;
-    dv.slot = out->slot ? reinterpret_cast<int32_t *>(d + o_slot) : nullptr;
-    dv.link_cost = out->link_cost ? reinterpret_cast<uint32_t *>(d + o_lc) : nullptr;
-    dv.children = out->children ? reinterpret_cast<int32_t *>(d + o_chl) : nullptr;
-    int32_t *d_cur = cur ? reinterpret_cast<int32_t *>(d + o_cur) : nullptr;
-    int32_t *d_roots = reinterpret_cast<int32_t *>(d + o_roots);
+    CallBlock b(c);
+    const size_t o_cost = b.reserve(n * 8), o_par = b.reserve(n * 4), o_slot = b.reserve(n * 4), o_lc = b.reserve(n * 4), o_chl = b.reserve(n * 4),
+                 o_cur = b.reserve(n * 4), o_roots = b.reserve(size_t(std::max(n_roots, 1)) * 4), o_peer = b.reserve(nk * 4),
+                 o_stats = b.reserve(nk * sizeof(rm_link_stats));
+    RM_TRY(b.alloc());
+    const rm_etx_out dv{b.at<uint64_t>(o_cost), b.at<int32_t>(o_par, out->parent), b.at<int32_t>(o_slot, out->slot),
+                        b.at<uint32_t>(o_lc, out->link_cost), b.at<int32_t>(o_chl, out->children)};
+    int32_t *d_cur = b.at<int32_t>(o_cur, cur), *d_roots = b.at<int32_t>(o_roots);
     rm_etx_tables dt{};
-    if (tables) dt = rm_etx_tables{reinterpret_cast<const int32_t *>(d + o_peer), reinterpret_cast<const rm_link_stats *>(d + o_stats), tables->K, 0};
-    int rc = RM_OK;
-    hipError_t e = hipSuccess;
-    if (n_roots > 0) e = hipMemcpyAsync(d_roots, roots, size_t(n_roots) * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && cur) e = hipMemcpyAsync(d_cur, cur, n * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && tables) e = hipMemcpyAsync(d + o_peer, tables->peer, nk * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && tables) e = hipMemcpyAsync(d + o_stats, tables->stats, nk * sizeof(rm_link_stats), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) rc = etx_run(c, *params, tables ? &dt : nullptr, d_roots, n_roots, d_cur, dv, totals);
-    if (rc == RM_OK && e == hipSuccess) {
-        e = hipMemcpyAsync(out->cost, dv.cost, n * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && dv.parent) e = hipMemcpyAsync(out->parent, dv.parent, n * 4, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && dv.slot) e = hipMemcpyAsync(out->slot, dv.slot, n * 4, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && dv.link_cost) e = hipMemcpyAsync(out->link_cost, dv.link_cost, n * 4, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && dv.children) e = hipMemcpyAsync(out->children, dv.children, n * 4, hipMemcpyDeviceToHost, c->stream);
+    if (tables) {
+        dt = rm_etx_tables{b.at<int32_t>(o_peer), b.at<rm_link_stats>(o_stats), tables->K, 0};
+        b.in(b.at<int32_t>(o_peer), tables->peer, nk * 4);
+        b.in(b.at<rm_link_stats>(o_stats), tables->stats, nk * sizeof(rm_link_stats));
     }
-    const hipError_t es = hipStreamSynchronize(c->stream); // (also on the way out of a failure: the block is freed below)
-    if (e == hipSuccess) e = es;
-    if (rc == RM_OK && e != hipSuccess) rc = fail(RM_ERR_HIP, std::string("rm_etx_query: ") + hipGetErrorString(e));
-    (void)hipFree(d);
-    return rc;
+    b.in(d_roots, roots, size_t(n_roots) * 4);
+    b.in(d_cur, cur, n * 4);
+    const int rc = b.ok() ? etx_run(c, *params, tables ? &dt : nullptr, d_roots, n_roots, d_cur, dv, totals) : RM_OK;
+    if (rc == RM_OK) {
+        b.out(out->cost, dv.cost, n * 8);
+        b.out(out->parent, dv.parent, n * 4);
+        b.out(out->slot, dv.slot, n * 4);
+        b.out(out->link_cost, dv.link_cost, n * 4);
+        b.out(out->children, dv.children, n * 4);
+    }
+    return b.finish(rc, "rm_etx_query");
 }
 
 int rm_etx_last_work(rm_context *c, int32_t *rounds, uint64_t *examined)
@@ -263,51 +241,17 @@ int rm_etx_from_tables(int32_t n_nodes, const rm_etx_tables *tables, const rm_et
     if (!tables) return fail(RM_ERR_INVALID, "tables is NULL");
     RM_TRY(etx_tables_check(tables, false));
     if (n_nodes < 0 || n_roots < 0) return fail(RM_ERR_INVALID, "negative count");
-    if (n_roots > 0 && !roots) return fail(RM_ERR_INVALID, "roots is NULL");
-    for (int32_t k = 0; k < n_roots; ++k)
-        if (roots[k] < 0 || roots[k] >= n_nodes) return fail(RM_ERR_INVALID, "root index out of range");
+    RM_TRY(roots_check(roots, n_roots));
+    RM_TRY(roots_in_table(roots, n_roots, n_nodes));
     const uint64_t unreached = std::numeric_limits<uint64_t>::max();
     const int K = tables->K;
     std::vector<uint32_t> lc;
     etx_host_costs(n_nodes, *tables, *params, lc);
-    // the counting entries by their far end (a counting sort): a settled node finds the nodes it may be the parent of
-    std::vector<size_t> first(size_t(n_nodes) + 1, 0), by_far(lc.size(), 0);
-    for (size_t i = 0; i < lc.size(); ++i)
-        if (lc[i]) ++first[size_t(tables->peer[i]) + 1];
-    for (int32_t p = 0; p < n_nodes; ++p) first[size_t(p) + 1] += first[size_t(p)];
-    {
-        std::vector<size_t> at(first.begin(), first.end() - 1);
-        for (size_t i = 0; i < lc.size(); ++i)
-            if (lc[i]) by_far[at[size_t(tables->peer[i])]++] = i;
-    }
-    // Dijkstra from all roots at once
-    rm_etx_totals t{0, 0, 0, 0, 0, 0, 0};
-    for (int32_t j = 0; j < n_nodes; ++j) out->cost[j] = unreached;
-    typedef std::pair<uint64_t, int32_t> Entry;
-    std::priority_queue<Entry, std::vector<Entry>, std::greater<Entry>> heap;
-    for (int32_t k = 0; k < n_roots; ++k)
-        if (out->cost[roots[k]] == unreached) {
-            out->cost[roots[k]] = 0;
-            heap.push(Entry(0, roots[k]));
-            ++t.roots;
-        }
-    while (!heap.empty()) {
-        const Entry top = heap.top();
-        heap.pop();
-        const int32_t p = top.second;
-        if (top.first != out->cost[p]) continue; // (an entry from before the node's cost fell)
-        ++t.reached;
-        t.max_cost = std::max(t.max_cost, top.first);
-        for (size_t k = first[size_t(p)]; k < first[size_t(p) + 1]; ++k) {
-            const size_t i = by_far[k];
-            const int32_t j = int32_t(i / size_t(K));
-            const uint64_t nc = top.first + lc[i];
-            if (nc < out->cost[j]) {
-                out->cost[j] = nc;
-                heap.push(Entry(nc, j));
-            }
-        }
-    }
+    // the counting entries by their far end -- a settled node finds the nodes it may be the parent of -- and Dijkstra over them
+    const ByFar g = by_far(size_t(n_nodes), lc.size(), [&](size_t i) { return lc[i] != 0u; }, [&](size_t i) { return tables->peer[i]; });
+    const LeastCosts found =
+        least_costs(n_nodes, g, roots, n_roots, [&](size_t i) { return int32_t(i / size_t(K)); }, [&](size_t i) { return lc[i]; }, out->cost);
+    rm_etx_totals t{found.reached, found.roots, 0, 0, 0, 0, found.max_cost};
     // the parents (k_etx_parent's text); cur[j] is read before parent[j] is written: the two may be one array
     if (out->children)
         for (int32_t j = 0; j < n_nodes; ++j) out->children[j] = 0;

@@ -5,9 +5,7 @@
 // The query READS the node table and the model and writes the caller's outputs and scratch of its own (rm_context::Hops): no
 // tick slot, no result buffer, no on-air window, not the generator, none of E11-E15's tables, not the source-candidate cache, not
 // the neighbour query's scratch.  An evaluating call after a query gives what it gave without one.
-#include "rm_host.hpp"
-
-#include <limits>
+#include "rm_query.hpp"
 
 using namespace rmh;
 
@@ -18,8 +16,7 @@ void hops_release(rm_context *c)
     c->hp.words.release();
     c->hp.off_list.release();
     c->hp.queue.release();
-    if (c->hp.h_tail) (void)hipHostFree(c->hp.h_tail);
-    c->hp.h_tail = nullptr;
+    c->hp.h.release();
 }
 
 // what both forms refuse, before anything is launched
@@ -29,8 +26,7 @@ static int hops_check(rm_context *c, int32_t direction, double min_rssi, const i
     if (!out || !out->hop) return fail(RM_ERR_INVALID, "out or out->hop is NULL");
     if (direction != RM_NB_HEARD_BY && direction != RM_NB_HEARS) return fail(RM_ERR_INVALID, "direction is RM_NB_HEARD_BY or RM_NB_HEARS");
     if (min_rssi != min_rssi) return fail(RM_ERR_INVALID, "min_rssi_dbm is NaN");
-    if (n_roots < 0) return fail(RM_ERR_INVALID, "negative root count");
-    if (n_roots > 0 && !roots) return fail(RM_ERR_INVALID, "roots is NULL");
+    RM_TRY(roots_check(roots, n_roots));
     if (c->params.kind != RM_MODEL_LOGDIST)
         return fail(RM_ERR_STATE, "the hop query walks links that have an rssi: only the log-distance medium computes one per link");
     if (c->in_tick) return fail(RM_ERR_STATE, "rm_hops_query between rm_tick_begin and rm_tick_flush");
@@ -50,13 +46,8 @@ static int hops_run(rm_context *c, int32_t direction, double min_rssi, const int
         if (c->n_rx != c->n) return fail(RM_ERR_STATE, "internal: the receiver table does not hold every node");
         rm_context::Hops &hp = c->hp;
         const size_t n = size_t(c->n);
-        if (hp.words.n < 4 || hp.off_list.n < n || hp.queue.n < n || !hp.h_tail) {
-            RM_HIP(hipStreamSynchronize(c->stream)); // (an earlier query may still read the old blocks)
-            RM_HIP(hp.words.ensure(4));
-            RM_HIP(hp.off_list.ensure(n));
-            RM_HIP(hp.queue.ensure(n));
-            if (!hp.h_tail) RM_HIP(hipHostMalloc(reinterpret_cast<void **>(&hp.h_tail), 64, hipHostMallocMapped));
-        }
+        RM_TRY(grow(c, need(hp.words, 4), need(hp.off_list, n), need(hp.queue, n)));
+        RM_HIP(hp.h.ensure());
         RM_HIP(hipMemsetAsync(hp.words.p, 0, 4 * sizeof(unsigned long long), c->stream));
         rm::HopDev h{};
         h.hop = out.hop;
@@ -68,16 +59,14 @@ static int hops_run(rm_context *c, int32_t direction, double min_rssi, const int
         h.prep = hp.words.p;
         h.off_list = hp.off_list.p;
         h.min_rssi = min_rssi;
-        // the whole-table scan exactly where the neighbour query takes it (rm_api_neighbors.cpp)
-        const bool scan = !c->rx_sorted || c->f32_slack > 0.05 || !(c->params.ld_exponent > 0.0);
+        const bool scan = nb_needs_scan(c);
         const rm::NodesDev nd = nodes_dev(c);
         const rm::ModelDev m = model_dev(c);
         CallProbe probe(c); // (rm_profile_kernels names the path that ran)
-        // the tail after the launches enqueued so far: one copy into the pinned word, one wait
+        // the tail after the launches enqueued so far
         auto tail = [&](int &count) -> int {
-            RM_HIP(hipMemcpyAsync(hp.h_tail, h.tail, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            RM_HIP(hipStreamSynchronize(c->stream));
-            count = int(std::min<uint32_t>(*hp.h_tail, uint32_t(c->n)));
+            RM_TRY(hp.h.read(c->stream, h.tail, sizeof(uint32_t)));
+            count = int(std::min<uint32_t>(hp.h.low(), uint32_t(c->n)));
             return RM_OK;
         };
         // both directions walk as a receiver somewhere: HEARD_BY in the expansion (the frontier node receives), HEARS in the
@@ -119,8 +108,7 @@ int rm_hops_query(rm_context *c, int32_t direction, double min_rssi_dbm, const i
                   rm_hops_totals *totals)
 {
     RM_TRY(hops_check(c, direction, min_rssi_dbm, roots, n_roots, out));
-    for (int32_t k = 0; k < n_roots; ++k)
-        if (roots[k] < 0 || roots[k] >= c->n) return fail(RM_ERR_INVALID, "root index out of range");
+    RM_TRY(roots_in_table(roots, n_roots, c->n));
     if (c->n < 1) {
         if (totals) *totals = rm_hops_totals{0, -1, 0, 0};
         return RM_OK;
@@ -128,30 +116,21 @@ int rm_hops_query(rm_context *c, int32_t direction, double min_rssi_dbm, const i
     RM_HIP(hipSetDevice(c->device));
     // the call's device block lives for this call only: rssi, hop, parent, children, roots
     const size_t n = size_t(c->n);
-    const size_t o_hop = pad64(n * 8), o_par = o_hop + pad64(n * 4), o_chl = o_par + pad64(n * 4), o_roots = o_chl + pad64(n * 4);
-    char *d = nullptr;
-    RM_HIP(hipMalloc(reinterpret_cast<void **>(&d), o_roots + pad64(size_t(std::max(n_roots, 1)) * 4)));
-    rm_hops_out dv{};
-    dv.hop = reinterpret_cast<int32_t *>(d + o_hop);
-    dv.parent = out->parent ? reinterpret_cast<int32_t *>(d + o_par) : nullptr;
-    dv.rssi = out->rssi ? reinterpret_cast<double *>(d) : nullptr;
-    dv.children = out->children ? reinterpret_cast<int32_t *>(d + o_chl) : nullptr;
-    int32_t *d_roots = reinterpret_cast<int32_t *>(d + o_roots);
-    int rc = RM_OK;
-    hipError_t e = hipSuccess;
-    if (n_roots > 0) e = hipMemcpyAsync(d_roots, roots, size_t(n_roots) * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) rc = hops_run(c, direction, min_rssi_dbm, d_roots, n_roots, dv, totals);
-    if (rc == RM_OK && e == hipSuccess) {
-        e = hipMemcpyAsync(out->hop, dv.hop, n * 4, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && dv.parent) e = hipMemcpyAsync(out->parent, dv.parent, n * 4, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && dv.rssi) e = hipMemcpyAsync(out->rssi, dv.rssi, n * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && dv.children) e = hipMemcpyAsync(out->children, dv.children, n * 4, hipMemcpyDeviceToHost, c->stream);
+    CallBlock b(c);
+    const size_t o_rssi = b.reserve(n * 8), o_hop = b.reserve(n * 4), o_par = b.reserve(n * 4), o_chl = b.reserve(n * 4),
+                 o_roots = b.reserve(size_t(std::max(n_roots, 1)) * 4);
+    RM_TRY(b.alloc());
+    const rm_hops_out dv{b.at<int32_t>(o_hop), b.at<int32_t>(o_par, out->parent), b.at<double>(o_rssi, out->rssi), b.at<int32_t>(o_chl, out->children)};
+    int32_t *d_roots = b.at<int32_t>(o_roots);
+    b.in(d_roots, roots, size_t(n_roots) * 4);
+    const int rc = b.ok() ? hops_run(c, direction, min_rssi_dbm, d_roots, n_roots, dv, totals) : RM_OK;
+    if (rc == RM_OK) {
+        b.out(out->hop, dv.hop, n * 4);
+        b.out(out->parent, dv.parent, n * 4);
+        b.out(out->rssi, dv.rssi, n * 8);
+        b.out(out->children, dv.children, n * 4);
     }
-    const hipError_t es = hipStreamSynchronize(c->stream); // (also on the way out of a failure: the block is freed below)
-    if (e == hipSuccess) e = es;
-    if (rc == RM_OK && e != hipSuccess) rc = fail(RM_ERR_HIP, std::string("rm_hops_query: ") + hipGetErrorString(e));
-    (void)hipFree(d);
-    return rc;
+    return b.finish(rc, "rm_hops_query");
 }
 
 int rm_hops_next_device(rm_context *c, const int32_t *dev_parent, const int32_t *dev_src, int32_t n, int32_t *dev_want)
@@ -170,33 +149,21 @@ int rm_hops_from_links(int32_t n_nodes, int32_t n_links, const int32_t *node, co
     if (!out || !out->hop) return fail(RM_ERR_INVALID, "out or out->hop is NULL");
     if (n_nodes < 0 || n_links < 0 || n_roots < 0) return fail(RM_ERR_INVALID, "negative count");
     if (n_links > 0 && (!node || !far || !rssi)) return fail(RM_ERR_INVALID, "node, far or rssi is NULL");
-    if (n_roots > 0 && !roots) return fail(RM_ERR_INVALID, "roots is NULL");
+    RM_TRY(roots_check(roots, n_roots));
     if (min_rssi_dbm != min_rssi_dbm) return fail(RM_ERR_INVALID, "min_rssi_dbm is NaN");
     for (int32_t i = 0; i < n_links; ++i)
         if (node[i] < 0 || node[i] >= n_nodes || far[i] < 0 || far[i] >= n_nodes) return fail(RM_ERR_INVALID, "link index out of range");
-    for (int32_t k = 0; k < n_roots; ++k)
-        if (roots[k] < 0 || roots[k] >= n_nodes) return fail(RM_ERR_INVALID, "root index out of range");
-    uint64_t nan_bits = 0x7FF8000000000000ull;
-    double nan;
-    std::memcpy(&nan, &nan_bits, sizeof(nan));
+    RM_TRY(roots_in_table(roots, n_roots, n_nodes));
+    const double nan = quiet_nan();
     for (int32_t j = 0; j < n_nodes; ++j) {
         out->hop[j] = -1;
         if (out->parent) out->parent[j] = -1;
         if (out->rssi) out->rssi[j] = nan;
         if (out->children) out->children[j] = 0;
     }
-    // the links by their far end (a counting sort): a frontier node finds the nodes it may be the parent of
-    auto is_link = [&](int32_t i) { return node[i] != far[i] && rssi[i] >= min_rssi_dbm; }; // (a NaN rssi compares false)
-    std::vector<int32_t> first(size_t(n_nodes) + 1, 0);
-    std::vector<int32_t> by_far(static_cast<size_t>(n_links), 0);
-    for (int32_t i = 0; i < n_links; ++i)
-        if (is_link(i)) ++first[size_t(far[i]) + 1];
-    for (int32_t p = 0; p < n_nodes; ++p) first[size_t(p) + 1] += first[size_t(p)];
-    {
-        std::vector<int32_t> at(first.begin(), first.end() - 1);
-        for (int32_t i = 0; i < n_links; ++i)
-            if (is_link(i)) by_far[size_t(at[size_t(far[i])]++)] = i;
-    }
+    // the links by their far end: a frontier node finds the nodes it may be the parent of
+    auto is_link = [&](size_t i) { return node[i] != far[i] && rssi[i] >= min_rssi_dbm; }; // (a NaN rssi compares false)
+    const ByFar g = by_far(size_t(n_nodes), size_t(n_links), is_link, [&](size_t i) { return far[i]; });
     rm_hops_totals t{0, -1, 0, 0};
     std::vector<int32_t> frontier, next;
     for (int32_t k = 0; k < n_roots; ++k)
@@ -210,8 +177,8 @@ int rm_hops_from_links(int32_t n_nodes, int32_t n_links, const int32_t *node, co
         t.reached += int32_t(frontier.size());
         next.clear();
         for (const int32_t p : frontier)
-            for (int32_t k = first[size_t(p)]; k < first[size_t(p) + 1]; ++k) {
-                const int32_t j = node[by_far[size_t(k)]];
+            for (size_t k = g.first[size_t(p)]; k < g.first[size_t(p) + 1]; ++k) {
+                const int32_t j = node[g.entry[k]];
                 if (out->hop[j] == -1) {
                     out->hop[j] = level + 1;
                     next.push_back(j);
@@ -221,14 +188,9 @@ int rm_hops_from_links(int32_t n_nodes, int32_t n_links, const int32_t *node, co
     }
     if (out->parent || out->rssi || out->children) {
         // the best candidate one level closer, by the rule's order: rssi descending, then the smaller node index
-        std::vector<int32_t> best(size_t(n_nodes), -1);
-        for (int32_t i = 0; i < n_links; ++i) {
-            if (!is_link(i)) continue;
-            const int32_t j = node[i];
-            if (out->hop[j] < 1 || out->hop[far[i]] != out->hop[j] - 1) continue;
-            const int32_t b = best[size_t(j)];
-            if (b < 0 || rssi[i] > rssi[b] || (rssi[i] == rssi[b] && far[i] < far[b])) best[size_t(j)] = i;
-        }
+        const std::vector<int32_t> best = best_by_rssi(n_nodes, n_links, node, far, rssi, [&](int32_t i) {
+            return is_link(size_t(i)) && out->hop[node[i]] >= 1 && out->hop[far[i]] == out->hop[node[i]] - 1;
+        });
         for (int32_t j = 0; j < n_nodes; ++j) {
             const int32_t b = best[size_t(j)];
             if (b < 0) continue;

@@ -5,9 +5,7 @@
 // The query READS the node table and the model and writes the caller's outputs and two scratch blocks of its own
 // (rm_context::Neighbors): no tick slot, no result buffer, no on-air window, not the generator, none of E11-E15's tables, not the
 // source-candidate cache.  An evaluating call after a query gives what it gave without one.
-#include "rm_host.hpp"
-
-#include <limits>
+#include "rm_query.hpp"
 
 using namespace rmh;
 
@@ -52,20 +50,13 @@ static int neighbors_launch(rm_context *c, int32_t direction, int32_t K, const i
     q.degree = degree;
     if (direction == RM_NB_HEARS) {
         rm_context::Neighbors &nb = c->nb;
-        if (nb.prep.n < 2 || nb.off_list.n < size_t(std::max(c->n, 1))) {
-            RM_HIP(hipStreamSynchronize(c->stream)); // (an earlier query may still read the old blocks)
-            RM_HIP(nb.prep.ensure(2));
-            RM_HIP(nb.off_list.ensure(size_t(std::max(c->n, 1))));
-        }
+        RM_TRY(grow(c, need(nb.prep, 2), need(nb.off_list, size_t(std::max(c->n, 1)))));
         RM_HIP(hipMemsetAsync(nb.prep.p, 0, 2 * sizeof(unsigned long long), c->stream));
         q.prep = nb.prep.p;
         q.off_list = nb.off_list.p;
     }
-    // the boxes bound nothing on a table that is not sorted, in an fp32 frame beyond the plan's slack (LaunchCfg::f64_filter) and
-    // for a medium without a finite cut-off: every pair is evaluated then
-    const bool scan = !c->rx_sorted || c->f32_slack > 0.05 || !(c->params.ld_exponent > 0.0);
     CallProbe probe(c); // (rm_profile_kernels names the path that ran)
-    RM_HIP(rm::launch_nb_query(c->stream, nodes_dev(c), model_dev(c), q, direction, scan));
+    RM_HIP(rm::launch_nb_query(c->stream, nodes_dev(c), model_dev(c), q, direction, nb_needs_scan(c)));
     return RM_OK;
 }
 
@@ -90,25 +81,19 @@ int rm_neighbors_query(rm_context *c, int32_t direction, int32_t K, const int32_
     RM_HIP(hipSetDevice(c->device));
     // the call's device block lives for this call only: list, rows, rssi, degrees
     const size_t rows = size_t(n) * size_t(K);
-    const size_t o_rssi = pad64(size_t(n) * 4), o_peer = o_rssi + pad64(rows * 8), o_deg = o_peer + pad64(rows * 4);
-    char *d = nullptr;
-    RM_HIP(hipMalloc(reinterpret_cast<void **>(&d), o_deg + pad64(size_t(n) * 4)));
-    int32_t *d_nodes = reinterpret_cast<int32_t *>(d), *d_peer = reinterpret_cast<int32_t *>(d + o_peer), *d_deg = reinterpret_cast<int32_t *>(d + o_deg);
-    double *d_rssi = reinterpret_cast<double *>(d + o_rssi);
-    int rc = RM_OK;
-    hipError_t e = hipSuccess;
-    if (nodes) e = hipMemcpyAsync(d_nodes, nodes, size_t(n) * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) rc = neighbors_launch(c, direction, K, nodes ? d_nodes : nullptr, n, d_peer, rssi ? d_rssi : nullptr, degree ? d_deg : nullptr);
-    if (rc == RM_OK && e == hipSuccess) {
-        e = hipMemcpyAsync(peer, d_peer, rows * 4, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && rssi) e = hipMemcpyAsync(rssi, d_rssi, rows * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && degree) e = hipMemcpyAsync(degree, d_deg, size_t(n) * 4, hipMemcpyDeviceToHost, c->stream);
+    CallBlock b(c);
+    const size_t o_nodes = b.reserve(size_t(n) * 4), o_rssi = b.reserve(rows * 8), o_peer = b.reserve(rows * 4), o_deg = b.reserve(size_t(n) * 4);
+    RM_TRY(b.alloc());
+    int32_t *d_nodes = b.at<int32_t>(o_nodes, nodes), *d_peer = b.at<int32_t>(o_peer), *d_deg = b.at<int32_t>(o_deg, degree);
+    double *d_rssi = b.at<double>(o_rssi, rssi);
+    b.in(d_nodes, nodes, size_t(n) * 4);
+    const int rc = b.ok() ? neighbors_launch(c, direction, K, d_nodes, n, d_peer, d_rssi, d_deg) : RM_OK;
+    if (rc == RM_OK) {
+        b.out(peer, d_peer, rows * 4);
+        b.out(rssi, d_rssi, rows * 8);
+        b.out(degree, d_deg, size_t(n) * 4);
     }
-    const hipError_t es = hipStreamSynchronize(c->stream); // (also on the way out of a failure: the block is freed below)
-    if (e == hipSuccess) e = es;
-    if (rc == RM_OK && e != hipSuccess) rc = fail(RM_ERR_HIP, std::string("rm_neighbors_query: ") + hipGetErrorString(e));
-    (void)hipFree(d);
-    return rc;
+    return b.finish(rc, "rm_neighbors_query");
 }
 
 int rm_neighbors_from_result(const rm_host_result *r, int32_t n_pkt, int32_t K, int32_t *peer, double *rssi, int32_t *degree)
@@ -118,9 +103,7 @@ int rm_neighbors_from_result(const rm_host_result *r, int32_t n_pkt, int32_t K, 
     if (n_pkt < 0 || uint32_t(n_pkt) > r->n_packets) return fail(RM_ERR_INVALID, "n_pkt outside 0 .. the result's packets");
     const bool have = r->pkt_offset && r->dst && (r->rssi || r->pkt_rssi);
     if (n_pkt > 0 && r->count > 0 && !have) return fail(RM_ERR_INVALID, "the result lacks pkt_offset, dst or an rssi column");
-    uint64_t nan_bits = 0x7FF8000000000000ull;
-    double nan;
-    std::memcpy(&nan, &nan_bits, sizeof(nan));
+    const double nan = quiet_nan();
     for (int32_t p = 0; p < n_pkt; ++p) {
         int32_t top_n[RM_NB_MAX_K];
         double top_r[RM_NB_MAX_K];

@@ -5,11 +5,8 @@
 // The query READS the node table and the model and writes the caller's outputs and scratch of its own (rm_context::Routes): what
 // the hop query leaves alone it leaves alone, and the hop query's scratch as well.  The context's frame error model plays no part:
 // kind, us_per_bit and air_us are the query's own parameters.
-#include "rm_host.hpp"
+#include "rm_query.hpp"
 #include "rm_math.hpp"
-
-#include <limits>
-#include <queue>
 
 using namespace rmh;
 
@@ -21,8 +18,7 @@ void routes_release(rm_context *c)
     c->rt.off_list.release();
     c->rt.stamp.release();
     c->rt.queue.release();
-    if (c->rt.h_words) (void)hipHostFree(c->rt.h_words);
-    c->rt.h_words = nullptr;
+    c->rt.h.release();
 }
 
 // the parameter rules of every form
@@ -57,8 +53,7 @@ static int routes_check(rm_context *c, const rm_routes_params *p, const int32_t 
     if (!c) return fail(RM_ERR_INVALID, "ctx is NULL");
     if (!out || !out->cost) return fail(RM_ERR_INVALID, "out or out->cost is NULL");
     RM_TRY(routes_params_check(p, true));
-    if (n_roots < 0) return fail(RM_ERR_INVALID, "negative root count");
-    if (n_roots > 0 && !roots) return fail(RM_ERR_INVALID, "roots is NULL");
+    RM_TRY(roots_check(roots, n_roots));
     if (c->params.kind != RM_MODEL_LOGDIST)
         return fail(RM_ERR_STATE, "the route query walks links that have an rssi: only the log-distance medium computes one per link");
     if (c->in_tick) return fail(RM_ERR_STATE, "rm_routes_query between rm_tick_begin and rm_tick_flush");
@@ -79,14 +74,8 @@ static int routes_run(rm_context *c, const rm_routes_params &p, const int32_t *r
         rm_context::Routes &rt = c->rt;
         const size_t n = size_t(c->n);
         constexpr size_t kWords = 5;
-        if (rt.words.n < kWords || rt.off_list.n < n || rt.stamp.n < n || rt.queue.n < 2 * n || !rt.h_words) {
-            RM_HIP(hipStreamSynchronize(c->stream)); // (an earlier query may still read the old blocks)
-            RM_HIP(rt.words.ensure(kWords));
-            RM_HIP(rt.off_list.ensure(n));
-            RM_HIP(rt.stamp.ensure(n));
-            RM_HIP(rt.queue.ensure(2 * n));
-            if (!rt.h_words) RM_HIP(hipHostMalloc(reinterpret_cast<void **>(&rt.h_words), 64, hipHostMallocMapped));
-        }
+        RM_TRY(grow(c, need(rt.words, kWords), need(rt.off_list, n), need(rt.stamp, n), need(rt.queue, 2 * n)));
+        RM_HIP(rt.h.ensure());
         RM_HIP(hipMemsetAsync(rt.words.p, 0, kWords * sizeof(unsigned long long), c->stream));
         const rm::ModelDev m = model_dev(c);
         rm::RouteDev r{};
@@ -108,15 +97,13 @@ static int routes_run(rm_context *c, const rm_routes_params &p, const int32_t *r
         r.air_us = p.air_us;
         r.noise_db = 10.0 * rm::det_log10(m.ld_noise_lin);
         r.max_cost = double(p.max_link_cost);
-        // the whole-table scan exactly where the neighbour query takes it (rm_api_neighbors.cpp)
-        const bool scan = !c->rx_sorted || c->f32_slack > 0.05 || !(c->params.ld_exponent > 0.0);
+        const bool scan = nb_needs_scan(c);
         const rm::NodesDev nd = nodes_dev(c);
         CallProbe probe(c); // (rm_profile_kernels names the path that ran)
-        // a queue's tail after the launches enqueued so far: one copy into the pinned word, one wait
+        // a queue's tail after the launches enqueued so far
         auto tail = [&](int which, int &count) -> int {
-            RM_HIP(hipMemcpyAsync(rt.h_words, r.tail + which, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            RM_HIP(hipStreamSynchronize(c->stream));
-            count = int(std::min<uint32_t>(*reinterpret_cast<const uint32_t *>(rt.h_words), uint32_t(c->n)));
+            RM_TRY(rt.h.read(c->stream, r.tail + which, sizeof(uint32_t)));
+            count = int(std::min<uint32_t>(rt.h.low(), uint32_t(c->n)));
             return RM_OK;
         };
         // both directions walk as a receiver somewhere: HEARD_BY in the relaxation (the frontier node receives), HEARS in the
@@ -137,10 +124,9 @@ static int routes_run(rm_context *c, const rm_routes_params &p, const int32_t *r
         if (t.roots > 0) {
             if (out.parent || out.rssi || out.link_cost || out.children) RM_HIP(rm::launch_route_parent(c->stream, nd, m, r, p.direction, scan));
             RM_HIP(rm::launch_route_totals(c->stream, r, c->n));
-            RM_HIP(hipMemcpyAsync(rt.h_words, r.sums, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-            RM_HIP(hipStreamSynchronize(c->stream));
-            t.reached = int32_t(std::min<unsigned long long>(rt.h_words[0], (unsigned long long)c->n));
-            t.max_cost = rt.h_words[1];
+            RM_TRY(rt.h.read(c->stream, r.sums, 2 * sizeof(unsigned long long)));
+            t.reached = int32_t(std::min<unsigned long long>(rt.h.p[0], (unsigned long long)c->n));
+            t.max_cost = rt.h.p[1];
         }
     }
     if (totals) *totals = t;
@@ -163,8 +149,7 @@ int rm_routes_query(rm_context *c, const rm_routes_params *params, const int32_t
                     rm_routes_totals *totals)
 {
     RM_TRY(routes_check(c, params, roots, n_roots, out));
-    for (int32_t k = 0; k < n_roots; ++k)
-        if (roots[k] < 0 || roots[k] >= c->n) return fail(RM_ERR_INVALID, "root index out of range");
+    RM_TRY(roots_in_table(roots, n_roots, c->n));
     if (c->n < 1) {
         if (totals) *totals = rm_routes_totals{0, 0, 0};
         return RM_OK;
@@ -172,33 +157,23 @@ int rm_routes_query(rm_context *c, const rm_routes_params *params, const int32_t
     RM_HIP(hipSetDevice(c->device));
     // the call's device block lives for this call only: cost, rssi, parent, link_cost, children, roots
     const size_t n = size_t(c->n);
-    const size_t o_rssi = pad64(n * 8), o_par = o_rssi + pad64(n * 8), o_lc = o_par + pad64(n * 4), o_chl = o_lc + pad64(n * 4),
-                 o_roots = o_chl + pad64(n * 4);
-    char *d = nullptr;
-    RM_HIP(hipMalloc(reinterpret_cast<void **>(&d), o_roots + pad64(size_t(std::max(n_roots, 1)) * 4)));
-    rm_routes_out dv{};
-    dv.cost = reinterpret_cast<uint64_t *>(d);
-    dv.rssi = out->rssi ? reinterpret_cast<double *>(d + o_rssi) : nullptr;
-    dv.parent = out->parent ? reinterpret_cast<int32_t *>(d + o_par) : nullptr;
-    dv.link_cost = out->link_cost ? reinterpret_cast<uint32_t *>(d + o_lc) : nullptr;
-    dv.children = out->children ? reinterpret_cast<int32_t *>(d + o_chl) : nullptr;
-    int32_t *d_roots = reinterpret_cast<int32_t *>(d + o_roots);
-    int rc = RM_OK;
-    hipError_t e = hipSuccess;
-    if (n_roots > 0) e = hipMemcpyAsync(d_roots, roots, size_t(n_roots) * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) rc = routes_run(c, *params, d_roots, n_roots, dv, totals);
-    if (rc == RM_OK && e == hipSuccess) {
-        e = hipMemcpyAsync(out->cost, dv.cost, n * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && dv.parent) e = hipMemcpyAsync(out->parent, dv.parent, n * 4, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && dv.rssi) e = hipMemcpyAsync(out->rssi, dv.rssi, n * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && dv.link_cost) e = hipMemcpyAsync(out->link_cost, dv.link_cost, n * 4, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && dv.children) e = hipMemcpyAsync(out->children, dv.children, n * 4, hipMemcpyDeviceToHost, c->stream);
+    CallBlock b(c);
+    const size_t o_cost = b.reserve(n * 8), o_rssi = b.reserve(n * 8), o_par = b.reserve(n * 4), o_lc = b.reserve(n * 4), o_chl = b.reserve(n * 4),
+                 o_roots = b.reserve(size_t(std::max(n_roots, 1)) * 4);
+    RM_TRY(b.alloc());
+    const rm_routes_out dv{b.at<uint64_t>(o_cost), b.at<int32_t>(o_par, out->parent), b.at<double>(o_rssi, out->rssi),
+                           b.at<uint32_t>(o_lc, out->link_cost), b.at<int32_t>(o_chl, out->children)};
+    int32_t *d_roots = b.at<int32_t>(o_roots);
+    b.in(d_roots, roots, size_t(n_roots) * 4);
+    const int rc = b.ok() ? routes_run(c, *params, d_roots, n_roots, dv, totals) : RM_OK;
+    if (rc == RM_OK) {
+        b.out(out->cost, dv.cost, n * 8);
+        b.out(out->parent, dv.parent, n * 4);
+        b.out(out->rssi, dv.rssi, n * 8);
+        b.out(out->link_cost, dv.link_cost, n * 4);
+        b.out(out->children, dv.children, n * 4);
     }
-    const hipError_t es = hipStreamSynchronize(c->stream); // (also on the way out of a failure: the block is freed below)
-    if (e == hipSuccess) e = es;
-    if (rc == RM_OK && e != hipSuccess) rc = fail(RM_ERR_HIP, std::string("rm_routes_query: ") + hipGetErrorString(e));
-    (void)hipFree(d);
-    return rc;
+    return b.finish(rc, "rm_routes_query");
 }
 
 int rm_routes_last_work(rm_context *c, int32_t *rounds, uint64_t *entries)
@@ -225,17 +200,13 @@ int rm_routes_from_links(int32_t n_nodes, int32_t n_links, const int32_t *node, 
     RM_TRY(routes_params_check(params, false));
     if (n_nodes < 0 || n_links < 0 || n_roots < 0) return fail(RM_ERR_INVALID, "negative count");
     if (n_links > 0 && (!node || !far || !rssi)) return fail(RM_ERR_INVALID, "node, far or rssi is NULL");
-    if (n_roots > 0 && !roots) return fail(RM_ERR_INVALID, "roots is NULL");
+    RM_TRY(roots_check(roots, n_roots));
     for (int32_t i = 0; i < n_links; ++i)
         if (node[i] < 0 || node[i] >= n_nodes || far[i] < 0 || far[i] >= n_nodes) return fail(RM_ERR_INVALID, "link index out of range");
-    for (int32_t k = 0; k < n_roots; ++k)
-        if (roots[k] < 0 || roots[k] >= n_nodes) return fail(RM_ERR_INVALID, "root index out of range");
+    RM_TRY(roots_in_table(roots, n_roots, n_nodes));
     const uint64_t unreached = std::numeric_limits<uint64_t>::max();
-    uint64_t nan_bits = 0x7FF8000000000000ull;
-    double nan;
-    std::memcpy(&nan, &nan_bits, sizeof(nan));
+    const double nan = quiet_nan();
     for (int32_t j = 0; j < n_nodes; ++j) {
-        out->cost[j] = unreached;
         if (out->parent) out->parent[j] = -1;
         if (out->rssi) out->rssi[j] = nan;
         if (out->link_cost) out->link_cost[j] = 0;
@@ -248,54 +219,16 @@ int rm_routes_from_links(int32_t n_nodes, int32_t n_links, const int32_t *node, 
         uint32_t c = 0;
         if (node[i] != far[i] && routes_cost(*params, noise_db, rssi[i], c)) lc[size_t(i)] = c;
     }
-    // the counting links by their far end (a counting sort): a settled node finds the nodes it may be the parent of
-    std::vector<int32_t> first(size_t(n_nodes) + 1, 0);
-    std::vector<int32_t> by_far(static_cast<size_t>(n_links), 0);
-    for (int32_t i = 0; i < n_links; ++i)
-        if (lc[size_t(i)]) ++first[size_t(far[i]) + 1];
-    for (int32_t p = 0; p < n_nodes; ++p) first[size_t(p) + 1] += first[size_t(p)];
-    {
-        std::vector<int32_t> at(first.begin(), first.end() - 1);
-        for (int32_t i = 0; i < n_links; ++i)
-            if (lc[size_t(i)]) by_far[size_t(at[size_t(far[i])]++)] = i;
-    }
-    // Dijkstra from all roots at once
-    rm_routes_totals t{0, 0, 0};
-    typedef std::pair<uint64_t, int32_t> Entry;
-    std::priority_queue<Entry, std::vector<Entry>, std::greater<Entry>> heap;
-    for (int32_t k = 0; k < n_roots; ++k)
-        if (out->cost[roots[k]] == unreached) {
-            out->cost[roots[k]] = 0;
-            heap.push(Entry(0, roots[k]));
-            ++t.roots;
-        }
-    while (!heap.empty()) {
-        const Entry top = heap.top();
-        heap.pop();
-        const int32_t p = top.second;
-        if (top.first != out->cost[p]) continue; // (an entry from before the node's cost fell)
-        ++t.reached;
-        t.max_cost = std::max(t.max_cost, top.first);
-        for (int32_t k = first[size_t(p)]; k < first[size_t(p) + 1]; ++k) {
-            const int32_t i = by_far[size_t(k)];
-            const uint64_t nc = top.first + lc[size_t(i)];
-            if (nc < out->cost[node[i]]) {
-                out->cost[node[i]] = nc;
-                heap.push(Entry(nc, node[i]));
-            }
-        }
-    }
+    // the counting links by their far end -- a settled node finds the nodes it may be the parent of -- and Dijkstra over them
+    const ByFar g = by_far(size_t(n_nodes), lc.size(), [&](size_t i) { return lc[i] != 0u; }, [&](size_t i) { return far[i]; });
+    const LeastCosts found = least_costs(n_nodes, g, roots, n_roots, [&](size_t i) { return node[i]; }, [&](size_t i) { return lc[i]; }, out->cost);
+    const rm_routes_totals t{found.reached, found.roots, found.max_cost};
     if (out->parent || out->rssi || out->link_cost || out->children) {
         // the best candidate on a least-cost path, by the rule's order: rssi descending, then the smaller node index
-        std::vector<int32_t> best(size_t(n_nodes), -1);
-        for (int32_t i = 0; i < n_links; ++i) {
-            if (!lc[size_t(i)]) continue;
-            const int32_t j = node[i];
-            if (out->cost[j] == 0 || out->cost[j] == unreached || out->cost[far[i]] == unreached) continue;
-            if (out->cost[far[i]] + lc[size_t(i)] != out->cost[j]) continue;
-            const int32_t b = best[size_t(j)];
-            if (b < 0 || rssi[i] > rssi[b] || (rssi[i] == rssi[b] && far[i] < far[b])) best[size_t(j)] = i;
-        }
+        const std::vector<int32_t> best = best_by_rssi(n_nodes, n_links, node, far, rssi, [&](int32_t i) {
+            const uint64_t cj = out->cost[node[i]], cf = out->cost[far[i]];
+            return lc[size_t(i)] && cj != 0 && cj != unreached && cf != unreached && cf + lc[size_t(i)] == cj;
+        });
         for (int32_t j = 0; j < n_nodes; ++j) {
             const int32_t b = best[size_t(j)];
             if (b < 0) continue;

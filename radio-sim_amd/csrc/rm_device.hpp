@@ -177,6 +177,46 @@ RM_D int uniform_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
 RM_D uint32_t uniform_u(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
 RM_D int wave_index() { return __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)); }
 
+// Called by whole waves: the `value` of every lane for which `won` holds is appended to `queue` behind *tail, in lane order, with
+// one atomicAdd per wave.  Nothing is stored at or beyond `cap` (the tail still counts such an entry).
+__device__ __forceinline__ void wave_append(const bool won, uint32_t *tail, int32_t *queue, const int32_t value, const uint32_t cap, const int lane)
+{
+    const uint64_t wm = ballot64(won);
+    if (!wm) return;
+    uint32_t base = 0u;
+    if (lane == 0) base = atomicAdd(tail, uint32_t(__popcll(wm)));
+    base = uniform_u(base);
+    const uint32_t at = base + lane_prefix(wm);
+    if (won && at < cap) queue[at] = value;
+}
+
+// What a query reports of its final path costs, as each wave of a grid-stride pass over cost[0 .. n) sees it: how many are not
+// `unreached`, the largest of those, and how many of them are 0 (the roots).  Every lane returns its wave's figures; the caller
+// adds them up with atomics of its own.
+struct CostTotals {
+    unsigned long long reached, max, zeros;
+};
+__device__ __forceinline__ CostTotals wave_cost_totals(const unsigned long long *cost, const int n, const unsigned long long unreached)
+{
+    CostTotals t{0ull, 0ull, 0ull};
+    for (int i = int(blockIdx.x * blockDim.x + threadIdx.x); i < n; i += int(gridDim.x * blockDim.x)) {
+        const unsigned long long c = cost[i];
+        if (c != unreached) {
+            ++t.reached;
+            t.zeros += c == 0ull;
+            t.max = c > t.max ? c : t.max;
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        t.reached += __shfl_xor(t.reached, d);
+        t.zeros += __shfl_xor(t.zeros, d);
+        const unsigned long long o = __shfl_xor(t.max, d);
+        t.max = o > t.max ? o : t.max;
+    }
+    return t;
+}
+
 // Consecutive lanes with equal `key` form a run (candidate entries of one frame are contiguous in
 // the list).  For the lanes with `pred`: how many such lanes precede me inside my run, how many
 // the run has, and which lane leads it -- so that one atomic per run replaces one per link.

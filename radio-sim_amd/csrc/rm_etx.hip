@@ -179,29 +179,14 @@ template <int K> __global__ void __launch_bounds__(kBlock) k_etx_parent(const Et
     }
 }
 
-// reached, max_cost and roots: a grid-stride pass over the final costs, one set of atomics per wave (k_route_totals' shape)
+// reached, max_cost and roots: a grid-stride pass over the final costs (wave_cost_totals), one set of atomics per wave
 __global__ void __launch_bounds__(kBlock) k_etx_totals(const EtxDev e)
 {
-    unsigned long long cnt = 0ull, mx = 0ull, roots = 0ull;
-    for (int i = int(blockIdx.x * blockDim.x + threadIdx.x); i < e.n; i += int(gridDim.x * blockDim.x)) {
-        const unsigned long long c = e.cost[i];
-        if (c != kEtxUnreached) {
-            ++cnt;
-            roots += c == 0ull;
-            mx = c > mx ? c : mx;
-        }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        cnt += __shfl_xor(cnt, d);
-        roots += __shfl_xor(roots, d);
-        const unsigned long long o = __shfl_xor(mx, d);
-        mx = o > mx ? o : mx;
-    }
-    if ((threadIdx.x & 63) == 0 && cnt) {
-        (void)atomicAdd(&e.words[2], cnt);
-        (void)atomicMax(&e.words[3], mx);
-        if (roots) (void)atomicAdd(&e.words[4], roots);
+    const CostTotals t = wave_cost_totals(e.cost, e.n, kEtxUnreached);
+    if ((threadIdx.x & 63) == 0 && t.reached) {
+        (void)atomicAdd(&e.words[2], t.reached);
+        (void)atomicMax(&e.words[3], t.max);
+        if (t.zeros) (void)atomicAdd(&e.words[4], t.zeros);
     }
 }
 

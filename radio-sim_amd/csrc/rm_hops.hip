@@ -21,29 +21,11 @@ __global__ void __launch_bounds__(kBlock) k_hop_init(const HopDev h, const int n
     if (h.children) h.children[i] = 0;
 }
 
-// the roots get hop 0; a root listed twice is claimed once (atomicCAS), an entry outside the table is skipped.  The claimed ones
-// are frontier 0: queue[0 .. *tail), *tail zeroed in front of the launch.
+// the roots get hop 0 (nb_seed; the claim is an atomicCAS).  The claimed ones are frontier 0: queue[0 .. *tail), *tail zeroed in
+// front of the launch.
 __global__ void __launch_bounds__(kBlock) k_hop_seed(const HopDev h, const int n, const int32_t *__restrict__ roots, const int n_roots)
 {
-    const int lane = threadIdx.x & 63;
-    const int stride = int(gridDim.x * blockDim.x);
-    const int rounds = (n_roots + stride - 1) / stride;
-    for (int r = 0; r < rounds; ++r) { // workgroup-uniform: whole waves reach the ballot
-        const int i = r * stride + int(blockIdx.x * blockDim.x + threadIdx.x);
-        bool won = false;
-        int node = -1;
-        if (i < n_roots) {
-            node = roots[i];
-            won = uint32_t(node) < uint32_t(n) && atomicCAS(&h.hop[node], -1, 0) == -1;
-        }
-        const uint64_t wm = ballot64(won);
-        if (wm) {
-            uint32_t base = 0u;
-            if (lane == 0) base = atomicAdd(h.tail, uint32_t(__popcll(wm)));
-            base = uniform_u(base);
-            if (won) h.queue[base + lane_prefix(wm)] = node;
-        }
-    }
+    nb_seed(roots, n_roots, n, h.tail, h.queue, [&](const int node) { return atomicCAS(&h.hop[node], -1, 0) == -1; });
 }
 
 // One level: a wave per frontier node p = queue[lo + e] (hop[p] == level) walks p's pairs in the REVERSE role -- DIR is the
@@ -66,19 +48,13 @@ __global__ void __launch_bounds__(kBlock) k_hop_expand(const NodesDev nd, const 
         nd, m, h.prep, h.off_list, p, cut, lane, [&](const int far) { return h.hop[far] == -1; },
         [&](const bool link, const double, const int far) {
             const bool won = link && atomicCAS(&h.hop[far], -1, level + 1) == -1;
-            const uint64_t wm = ballot64(won);
-            if (wm) {
-                uint32_t base = 0u;
-                if (lane == 0) base = atomicAdd(h.tail, uint32_t(__popcll(wm)));
-                base = uniform_u(base);
-                if (won) h.queue[base + lane_prefix(wm)] = far;
-            }
+            wave_append(won, h.tail, h.queue, far, uint32_t(nd.n), lane); // (one entry per node: always below n)
         });
 }
 
 // The parents: a wave per reached non-root node j = queue[lo + e] walks j's pairs in the forward direction; the candidates are
 // the links whose far end is one level closer.  Every lane keeps the best of its own pairs by the rule's order, the wave-wide
-// best is taken with nb_absorb's butterfly, lane 0 writes.  The hops are complete: the last level's launch has ended.
+// best follows (NbBest), lane 0 writes.  The hops are complete: the last level's launch has ended.
 template <int DIR, bool SCAN>
 __global__ void __launch_bounds__(kBlock) k_hop_parent(const NodesDev nd, const ModelDev m, const HopDev h, const int lo, const int hi)
 {
@@ -89,33 +65,17 @@ __global__ void __launch_bounds__(kBlock) k_hop_parent(const NodesDev nd, const 
     if (uint32_t(j) >= uint32_t(nd.n)) return;
     const int up = uniform_i(h.hop[j]) - 1;
     const double cut = fmax(m.ld_sens, h.min_rssi);
-    double br = 0.0;
-    int bn = -1;
-    bool bv = false;
+    NbBest best;
     nb_walk<DIR, SCAN>(
         nd, m, h.prep, h.off_list, j, cut, lane, [&](const int far) { return h.hop[far] == up; },
         [&](const bool link, const double rssi, const int far) {
-            if (link && (!bv || nb_precedes(rssi, far, br, bn))) {
-                br = rssi;
-                bn = far;
-                bv = true;
-            }
+            if (link) best.offer(rssi, far, 0u);
         });
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const double o_r = __shfl_xor(br, d);
-        const int o_n = __shfl_xor(bn, d);
-        const bool o_v = __shfl_xor(int(bv), d) != 0;
-        if (o_v && (!bv || nb_precedes(o_r, o_n, br, bn))) {
-            br = o_r;
-            bn = o_n;
-            bv = true;
-        }
-    }
-    if (lane == 0 && bv) {
-        if (h.parent) h.parent[j] = bn;
-        if (h.rssi) h.rssi[j] = f2u(br);
-        if (h.children) atomicAdd(&h.children[bn], 1);
+    best.wave<false>();
+    if (lane == 0 && best.valid) {
+        if (h.parent) h.parent[j] = best.node;
+        if (h.rssi) h.rssi[j] = f2u(best.rssi);
+        if (h.children) atomicAdd(&h.children[best.node], 1);
     }
 }
 
@@ -141,15 +101,7 @@ hipError_t launch_hop_expand(hipStream_t s, const NodesDev &nd, const ModelDev &
 {
     if (hi <= lo) return hipSuccess;
     const dim3 grid(cdiv(hi - lo, kNbWaves)), block(kBlock);
-    if (direction == RM_NB_HEARD_BY) {
-        if (scan) RM_KLAUNCH((k_hop_expand<RM_NB_HEARD_BY, true>), grid, block, 0, s, nd, m, h, lo, hi, level);
-        else RM_KLAUNCH((k_hop_expand<RM_NB_HEARD_BY, false>), grid, block, 0, s, nd, m, h, lo, hi, level);
-    } else if (direction == RM_NB_HEARS) {
-        if (scan) RM_KLAUNCH((k_hop_expand<RM_NB_HEARS, true>), grid, block, 0, s, nd, m, h, lo, hi, level);
-        else RM_KLAUNCH((k_hop_expand<RM_NB_HEARS, false>), grid, block, 0, s, nd, m, h, lo, hi, level);
-    } else {
-        return hipErrorInvalidValue;
-    }
+    RM_NB_BY_DIR_SCAN(k_hop_expand, grid, block, nd, m, h, lo, hi, level);
     return hipGetLastError();
 }
 
@@ -157,15 +109,7 @@ hipError_t launch_hop_parent(hipStream_t s, const NodesDev &nd, const ModelDev &
 {
     if (hi <= lo) return hipSuccess;
     const dim3 grid(cdiv(hi - lo, kNbWaves)), block(kBlock);
-    if (direction == RM_NB_HEARD_BY) {
-        if (scan) RM_KLAUNCH((k_hop_parent<RM_NB_HEARD_BY, true>), grid, block, 0, s, nd, m, h, lo, hi);
-        else RM_KLAUNCH((k_hop_parent<RM_NB_HEARD_BY, false>), grid, block, 0, s, nd, m, h, lo, hi);
-    } else if (direction == RM_NB_HEARS) {
-        if (scan) RM_KLAUNCH((k_hop_parent<RM_NB_HEARS, true>), grid, block, 0, s, nd, m, h, lo, hi);
-        else RM_KLAUNCH((k_hop_parent<RM_NB_HEARS, false>), grid, block, 0, s, nd, m, h, lo, hi);
-    } else {
-        return hipErrorInvalidValue;
-    }
+    RM_NB_BY_DIR_SCAN(k_hop_parent, grid, block, nd, m, h, lo, hi);
     return hipGetLastError();
 }
 

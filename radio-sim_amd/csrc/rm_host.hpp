@@ -105,6 +105,26 @@ struct PinnedBlock {
     }
 };
 
+// The 64 pinned, host-mapped bytes through which a query's host loop reads a few device words between its launches (a queue's tail,
+// a round's counter, the totals).
+struct PinnedWords {
+    unsigned long long *p = nullptr;
+    hipError_t ensure() { return p ? hipSuccess : hipHostMalloc(reinterpret_cast<void **>(&p), 64, hipHostMallocMapped); }
+    // bytes (<= 64) at dev_src as the launches enqueued on `s` so far leave them: one copy, one wait
+    int read(hipStream_t s, const void *dev_src, size_t bytes)
+    {
+        RM_HIP(hipMemcpyAsync(p, dev_src, bytes, hipMemcpyDeviceToHost, s));
+        RM_HIP(hipStreamSynchronize(s));
+        return RM_OK;
+    }
+    uint32_t low() const { return uint32_t(p[0]); } // (a 4-byte read: the low half of the first word)
+    void release()
+    {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+    }
+};
+
 // what a pool of heard lists (rm_ncpool.hpp) owns on its device: one entry per node, the three columns of the arena, the arena's
 // bump counter, and the event behind the last epoch's resets -- a context that joins makes its stream wait for it
 struct NcPoolMem {
@@ -241,35 +261,35 @@ struct rm_context : TickSlot {
     } nb;
     // the hop query (E17; rm_api_hops.cpp, rm_hops.hip): its own prep words and list of radios that are off (E16's are not
     // touched) -- words[0 .. 1] are k_nb_prep's, the low half of words[2] is the queue's tail; one 32-byte block, zeroed per
-    // query --, the queue of labelled nodes ([n_nodes]: every level's frontier is a range of it), and the pinned word the
-    // tail is copied to once per level.  Nothing is allocated before the first query.
+    // query --, the queue of labelled nodes ([n_nodes]: every level's frontier is a range of it), and the pinned words the
+    // tail is read through once per level.  Nothing is allocated before the first query.
     struct Hops {
         DevBuf<unsigned long long> words;
         DevBuf<int32_t> off_list;
         DevBuf<int32_t> queue;
-        uint32_t *h_tail = nullptr;
+        rmh::PinnedWords h;
     } hp;
     // the route query (E18; rm_api_routes.cpp, rm_routes.hip): scratch of its own (the hop query's is not touched) -- words[0 .. 1]
     // are k_nb_prep's, words[2] the two queues' tails, words[3 .. 4] the totals' sums; one block, zeroed per query --, the list of
     // radios that are off, the per-node round stamps, the two frontier queues ([n_nodes] each), and the pinned words the tail
-    // and the sums are copied to.  Nothing is allocated before the first query.
+    // and the sums are read through.  Nothing is allocated before the first query.
     struct Routes {
         DevBuf<unsigned long long> words;
         DevBuf<int32_t> off_list;
         DevBuf<uint32_t> stamp;
         DevBuf<int32_t> queue; // [2][n_nodes]
-        unsigned long long *h_words = nullptr;
+        rmh::PinnedWords h;
         int32_t last_rounds = 0;   // the last query's relaxation launches and the frontier entries they walked (rm_routes_last_work)
         uint64_t last_entries = 0;
     } rt;
     // the measured-route query (E21; rm_api_etx.cpp, rm_etx.hip): every entry's link cost ([n_nodes][K]), the per-node round
-    // stamps, the word block (rm::kEtxWords, zeroed per query) and the pinned words a round's counter and the totals are copied
-    // to.  Nothing is allocated before the first query.
+    // stamps, the word block (rm::kEtxWords, zeroed per query) and the pinned words a round's counter and the totals are read
+    // through.  Nothing is allocated before the first query.
     struct Etx {
         DevBuf<uint32_t> lc;
         DevBuf<uint32_t> stamp;
         DevBuf<unsigned long long> words;
-        unsigned long long *h_words = nullptr;
+        rmh::PinnedWords h;
         int32_t last_rounds = 0;    // the last query's relaxation launches and the nodes they examined (rm_etx_last_work)
         uint64_t last_examined = 0;
     } etx;

@@ -1,9 +1,13 @@
-// rm_nbwalk.hpp -- what the neighbour query (rm_neighbors.hip) and the hop query (rm_hops.hip; E17)
-// share: the rule's order, the txpower key of k_nb_prep, and nb_walk, the walk over one node's potential links as a device
-// template that takes the per-round visitor.  nb_walk is the pair tests and arithmetic, the box / group / receiver walk and the
-// whole-table scan of k_nb_query, statement for statement; k_nb_query keeps its own inlined copy, because taking the template
-// there moved its HEARS box variant from 45 to 47 VGPRs.  A change to one has to be made to the other: the hop
-// query's tests hold the two to each other (tests/test_gpu_hops.py, the 65 537-node case) and both to the oracle.
+// rm_nbwalk.hpp -- what the queries over the potential-link graph share: the neighbour query (rm_neighbors.hip; DESIGN.md section
+// 6, E16), the hop query (rm_hops.hip; E17) and the route query (rm_routes.hip; E18).  The rule's order and the txpower key of
+// k_nb_prep; nb_walk, the walk over one node's potential links as a device template that takes the per-round visitor; and what
+// the two tree queries have as one text -- nb_seed (the roots claimed into frontier 0), NbBest (a lane's and then a wave's best
+// link by the rule's order, the parent passes) -- and RM_NB_BY_DIR_SCAN, the launch of a kernel that is a template of the
+// direction and the scan.
+// nb_walk has the pair tests and arithmetic, the box / group / receiver walk and the whole-table scan of k_nb_query.  k_nb_query
+// keeps its own inlined copy of the walk, and nb_absorb its own butterfly, because taking the template there moved its HEARS box
+// variant from 45 to 47 VGPRs.  A change to the walk has to be made in both places: the hop query's tests hold
+// the two to each other (tests/test_gpu_hops.py, the 65 537-node case) and both to the oracle.
 // Device code only; gfx950, wave64.
 #pragma once
 
@@ -30,6 +34,69 @@ RM_D double nb_key_value(const unsigned long long key)
 
 // THE order of the rule: link a precedes link b
 RM_D bool nb_precedes(const double ra, const int na, const double rb, const int nb) { return ra > rb || (ra == rb && na < nb); }
+
+// The best link seen so far by the rule's order, with one 32-bit word that travels with it (a link cost; a kernel that has none
+// passes 0 and WORD = false to `wave`, and the word costs nothing).
+struct NbBest {
+    double rssi = 0.0;
+    int node = -1;
+    uint32_t word = 0u;
+    bool valid = false;
+    // a lane's own candidate
+    __device__ __forceinline__ void offer(const double r, const int n, const uint32_t w)
+    {
+        if (!valid || nb_precedes(r, n, rssi, node)) {
+            rssi = r;
+            node = n;
+            word = w;
+            valid = true;
+        }
+    }
+    // the wave-wide best in every lane: a butterfly of six exchanges, called by the whole wave
+    template <bool WORD> __device__ __forceinline__ void wave()
+    {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const double o_r = __shfl_xor(rssi, d);
+            const int o_n = __shfl_xor(node, d);
+            const uint32_t o_w = WORD ? uint32_t(__shfl_xor(int(word), d)) : 0u;
+            const bool o_v = __shfl_xor(int(valid), d) != 0;
+            if (o_v) offer(o_r, o_n, o_w);
+        }
+    }
+};
+
+// The roots of a tree query: an entry inside the table that claim(node) wins -- a root listed twice is claimed once -- goes into
+// queue[0 .. *tail), frontier 0; *tail is zero in front of the launch.  An entry outside the table is skipped.  The loop is
+// workgroup-uniform, so that whole waves reach the append.
+template <typename Claim>
+__device__ __forceinline__ void nb_seed(const int32_t *__restrict__ roots, const int n_roots, const int n, uint32_t *tail, int32_t *queue, Claim &&claim)
+{
+    const int lane = threadIdx.x & 63;
+    const int stride = int(gridDim.x * blockDim.x);
+    const int rounds = (n_roots + stride - 1) / stride;
+    for (int r = 0; r < rounds; ++r) {
+        const int i = r * stride + int(blockIdx.x * blockDim.x + threadIdx.x);
+        bool won = false;
+        int node = -1;
+        if (i < n_roots) {
+            node = roots[i];
+            won = uint32_t(node) < uint32_t(n) && claim(node);
+        }
+        wave_append(won, tail, queue, node, uint32_t(n), lane); // (at most one entry per node: below n)
+    }
+}
+
+// one launch of a kernel that is a template of <DIR, SCAN>, chosen by the `direction` and `scan` of the launch function, on its
+// stream `s`; an unknown direction ends the function
+#define RM_NB_BY_DIR_SCAN(kern, grid, block, ...)                                                                             \
+    do {                                                                                                                      \
+        if (direction == RM_NB_HEARD_BY && scan) RM_KLAUNCH((kern<RM_NB_HEARD_BY, true>), grid, block, 0, s, __VA_ARGS__);    \
+        else if (direction == RM_NB_HEARD_BY) RM_KLAUNCH((kern<RM_NB_HEARD_BY, false>), grid, block, 0, s, __VA_ARGS__);      \
+        else if (direction == RM_NB_HEARS && scan) RM_KLAUNCH((kern<RM_NB_HEARS, true>), grid, block, 0, s, __VA_ARGS__);     \
+        else if (direction == RM_NB_HEARS) RM_KLAUNCH((kern<RM_NB_HEARS, false>), grid, block, 0, s, __VA_ARGS__);            \
+        else return hipErrorInvalidValue;                                                                                     \
+    } while (0)
 
 // One wave walks the pairs of `node` (wave-uniform, inside the table) in rounds of up to 64, a lane each.
 // DIR = RM_NB_HEARD_BY: the node transmits, the pairs' far ends are receivers; RM_NB_HEARS: it receives, the far ends transmit

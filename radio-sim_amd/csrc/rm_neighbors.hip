@@ -271,14 +271,8 @@ hipError_t launch_nb_query(hipStream_t s, const NodesDev &nd, const ModelDev &m,
     if (direction == RM_NB_HEARS) {
         const hipError_t e = launch_nb_prep(s, nd, q.prep, q.off_list);
         if (e != hipSuccess) return e;
-        if (scan) RM_KLAUNCH((k_nb_query<RM_NB_HEARS, true>), grid, block, 0, s, nd, m, q);
-        else RM_KLAUNCH((k_nb_query<RM_NB_HEARS, false>), grid, block, 0, s, nd, m, q);
-    } else if (direction == RM_NB_HEARD_BY) {
-        if (scan) RM_KLAUNCH((k_nb_query<RM_NB_HEARD_BY, true>), grid, block, 0, s, nd, m, q);
-        else RM_KLAUNCH((k_nb_query<RM_NB_HEARD_BY, false>), grid, block, 0, s, nd, m, q);
-    } else {
-        return hipErrorInvalidValue;
     }
+    RM_NB_BY_DIR_SCAN(k_nb_query, grid, block, nd, m, q);
     return hipGetLastError();
 }
 

@@ -3,7 +3,8 @@
 // (part of libradiomedium_hip.so; gfx950 only, -ffp-contract=off, no fast-math; overview at the top of rm_engine.h)
 //
 // The hop query's structure (rm_hops.hip) with relaxation in place of claiming: a frontier of nodes whose cost fell, one launch per
-// round, and one parent-selection pass behind the last round.  Both walk a node's pairs with nb_walk (rm_nbwalk.hpp), E16's walk.
+// round, and one parent-selection pass behind the last round.  Both walk a node's pairs with nb_walk (rm_nbwalk.hpp), E16's walk;
+// the seeding and the parent's choice are the hop query's too (nb_seed, NbBest), the queue append everybody's (wave_append).
 // A node's cost only ever falls (a 64-bit atomicMin), and whoever lowers it queues it for the next round, at most once per round (a
 // per-node round stamp): a queue never holds more than n_nodes entries.  Link costs are positive integers, so the rounds end, and
 // the fixed point they end in does not depend on the order of the relaxations.
@@ -31,29 +32,10 @@ __global__ void __launch_bounds__(kBlock) k_route_init(const RouteDev r, const i
     if (r.children) r.children[i] = 0;
 }
 
-// the roots get cost 0; a root listed twice is claimed once (atomicCAS), an entry outside the table is skipped.  The claimed ones
-// are frontier 0: queue[0][0 .. tail[0]).
+// the roots get cost 0 (nb_seed; the claim is an atomicCAS).  The claimed ones are frontier 0: queue[0][0 .. tail[0]).
 __global__ void __launch_bounds__(kBlock) k_route_seed(const RouteDev r, const int n, const int32_t *__restrict__ roots, const int n_roots)
 {
-    const int lane = threadIdx.x & 63;
-    const int stride = int(gridDim.x * blockDim.x);
-    const int rounds = (n_roots + stride - 1) / stride;
-    for (int k = 0; k < rounds; ++k) { // workgroup-uniform: whole waves reach the ballot
-        const int i = k * stride + int(blockIdx.x * blockDim.x + threadIdx.x);
-        bool won = false;
-        int node = -1;
-        if (i < n_roots) {
-            node = roots[i];
-            won = uint32_t(node) < uint32_t(n) && atomicCAS(&r.cost[node], kRouteUnreached, 0ull) == kRouteUnreached;
-        }
-        const uint64_t wm = ballot64(won);
-        if (wm) {
-            uint32_t base = 0u;
-            if (lane == 0) base = atomicAdd(&r.tail[0], uint32_t(__popcll(wm)));
-            base = uniform_u(base);
-            if (won) r.queue[0][base + lane_prefix(wm)] = node; // (at most one entry per node: below n)
-        }
-    }
+    nb_seed(roots, n_roots, n, &r.tail[0], r.queue[0], [&](const int node) { return atomicCAS(&r.cost[node], kRouteUnreached, 0ull) == kRouteUnreached; });
 }
 
 // One round: a wave per frontier node p = queue[round & 1][e] walks p's pairs in the REVERSE role, as k_hop_expand does -- DIR is
@@ -89,20 +71,13 @@ __global__ void __launch_bounds__(kBlock) k_route_relax(const NodesDev nd, const
                 const unsigned long long nc = cp + c;
                 if (atomicMin(&r.cost[far], nc) > nc) won = atomicMax(&r.stamp[far], next) < next;
             }
-            const uint64_t wm = ballot64(won);
-            if (wm) {
-                uint32_t base = 0u;
-                if (lane == 0) base = atomicAdd(out_tail, uint32_t(__popcll(wm)));
-                base = uniform_u(base);
-                const uint32_t at = base + lane_prefix(wm);
-                if (won && at < uint32_t(nd.n)) out[at] = far; // (one entry per node and round: always below n)
-            }
+            wave_append(won, out_tail, out, far, uint32_t(nd.n), lane); // (one entry per node and round: always below n)
         });
 }
 
 // The parents: a wave per node j of the table; a reached node that is no root walks its pairs in the forward direction; the
 // candidates are the counting links with cost[far] + c == cost[j].  Every lane keeps the best of its own pairs by the rule's order,
-// the wave-wide best is taken with the butterfly of k_hop_parent, lane 0 writes.  The costs are final: the last round has ended.
+// the wave-wide best follows (NbBest, as in k_hop_parent), lane 0 writes.  The costs are final: the last round has ended.
 template <int DIR, bool SCAN>
 __global__ void __launch_bounds__(kBlock) k_route_parent(const NodesDev nd, const ModelDev m, const RouteDev r)
 {
@@ -112,62 +87,29 @@ __global__ void __launch_bounds__(kBlock) k_route_parent(const NodesDev nd, cons
     const unsigned long long cj = r.cost[j];
     if (cj == 0ull || cj == kRouteUnreached) return; // (wave-uniform: one address)
     const double cut = fmax(m.ld_sens, r.min_rssi);
-    double br = 0.0;
-    int bn = -1;
-    uint32_t bc = 0u;
-    bool bv = false;
+    NbBest best; // (its word: the link's cost)
     nb_walk<DIR, SCAN>(
         nd, m, r.prep, r.off_list, j, cut, lane, [&](const int far) { return r.cost[far] <= cj - 128ull; },
         [&](const bool link, const double rssi, const int far) {
             uint32_t c = 0u;
-            if (link && route_cost(r, rssi, c) && r.cost[far] + c == cj && (!bv || nb_precedes(rssi, far, br, bn))) {
-                br = rssi;
-                bn = far;
-                bc = c;
-                bv = true;
-            }
+            if (link && route_cost(r, rssi, c) && r.cost[far] + c == cj) best.offer(rssi, far, c);
         });
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const double o_r = __shfl_xor(br, d);
-        const int o_n = __shfl_xor(bn, d);
-        const uint32_t o_c = uint32_t(__shfl_xor(int(bc), d));
-        const bool o_v = __shfl_xor(int(bv), d) != 0;
-        if (o_v && (!bv || nb_precedes(o_r, o_n, br, bn))) {
-            br = o_r;
-            bn = o_n;
-            bc = o_c;
-            bv = true;
-        }
-    }
-    if (lane == 0 && bv) {
-        if (r.parent) r.parent[j] = bn;
-        if (r.rssi) r.rssi[j] = f2u(br);
-        if (r.link_cost) r.link_cost[j] = bc;
-        if (r.children) atomicAdd(&r.children[bn], 1);
+    best.wave<true>();
+    if (lane == 0 && best.valid) {
+        if (r.parent) r.parent[j] = best.node;
+        if (r.rssi) r.rssi[j] = f2u(best.rssi);
+        if (r.link_cost) r.link_cost[j] = best.word;
+        if (r.children) atomicAdd(&r.children[best.node], 1);
     }
 }
 
-// reached and max_cost: a grid-stride pass over the final costs, one pair of atomics per wave
+// reached and max_cost: a grid-stride pass over the final costs (wave_cost_totals), one pair of atomics per wave
 __global__ void __launch_bounds__(kBlock) k_route_totals(const RouteDev r, const int n)
 {
-    unsigned long long cnt = 0ull, mx = 0ull;
-    for (int i = int(blockIdx.x * blockDim.x + threadIdx.x); i < n; i += int(gridDim.x * blockDim.x)) {
-        const unsigned long long c = r.cost[i];
-        if (c != kRouteUnreached) {
-            ++cnt;
-            mx = c > mx ? c : mx;
-        }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        cnt += __shfl_xor(cnt, d);
-        const unsigned long long o = __shfl_xor(mx, d);
-        mx = o > mx ? o : mx;
-    }
-    if ((threadIdx.x & 63) == 0 && cnt) {
-        atomicAdd(&r.sums[0], cnt);
-        atomicMax(&r.sums[1], mx);
+    const CostTotals t = wave_cost_totals(r.cost, n, kRouteUnreached);
+    if ((threadIdx.x & 63) == 0 && t.reached) {
+        atomicAdd(&r.sums[0], t.reached);
+        atomicMax(&r.sums[1], t.max);
     }
 }
 
@@ -183,15 +125,7 @@ hipError_t launch_route_relax(hipStream_t s, const NodesDev &nd, const ModelDev 
 {
     if (count < 1) return hipSuccess;
     const dim3 grid(cdiv(count, kNbWaves)), block(kBlock);
-    if (direction == RM_NB_HEARD_BY) {
-        if (scan) RM_KLAUNCH((k_route_relax<RM_NB_HEARD_BY, true>), grid, block, 0, s, nd, m, r, count, round);
-        else RM_KLAUNCH((k_route_relax<RM_NB_HEARD_BY, false>), grid, block, 0, s, nd, m, r, count, round);
-    } else if (direction == RM_NB_HEARS) {
-        if (scan) RM_KLAUNCH((k_route_relax<RM_NB_HEARS, true>), grid, block, 0, s, nd, m, r, count, round);
-        else RM_KLAUNCH((k_route_relax<RM_NB_HEARS, false>), grid, block, 0, s, nd, m, r, count, round);
-    } else {
-        return hipErrorInvalidValue;
-    }
+    RM_NB_BY_DIR_SCAN(k_route_relax, grid, block, nd, m, r, count, round);
     return hipGetLastError();
 }
 
@@ -199,15 +133,7 @@ hipError_t launch_route_parent(hipStream_t s, const NodesDev &nd, const ModelDev
 {
     if (nd.n < 1) return hipSuccess;
     const dim3 grid(cdiv(nd.n, kNbWaves)), block(kBlock);
-    if (direction == RM_NB_HEARD_BY) {
-        if (scan) RM_KLAUNCH((k_route_parent<RM_NB_HEARD_BY, true>), grid, block, 0, s, nd, m, r);
-        else RM_KLAUNCH((k_route_parent<RM_NB_HEARD_BY, false>), grid, block, 0, s, nd, m, r);
-    } else if (direction == RM_NB_HEARS) {
-        if (scan) RM_KLAUNCH((k_route_parent<RM_NB_HEARS, true>), grid, block, 0, s, nd, m, r);
-        else RM_KLAUNCH((k_route_parent<RM_NB_HEARS, false>), grid, block, 0, s, nd, m, r);
-    } else {
-        return hipErrorInvalidValue;
-    }
+    RM_NB_BY_DIR_SCAN(k_route_parent, grid, block, nd, m, r);
     return hipGetLastError();
 }
 
