@@ -864,7 +864,7 @@ int rm_listen_at(const rm_listen_schedule *s, int64_t t_us);
  * written: results, the on-air window, java.util.Random, the traffic counters and the listening schedules' tables are as with the
  * feature off.  All sums are integers, minima or maxima: the tables after any sequence of calls do not depend on whether lone
  * ticks, a batch, a gated batch, a CSMA-CA batch or any split of a CSMA-CA run into carry batches evaluated the frames.
- * Peers are the caller's: nothing is inserted or evicted by what is heard.
+ * Peers are the caller's: this pass inserts and evicts nothing by what is heard (the neighbour tables below, rm_nbtable_*, do).
  * Accepted and refused where the traffic counters are: every evaluating call on a whole-table context (a dense tick ends with its
  * records and rm_result_dense keeps answering; rm_transmit on a reference medium takes the general tick path); refused with
  * RM_ERR_STATE before anything is launched, window, generator and tables untouched: contexts with a receiver partition, the
@@ -1379,6 +1379,98 @@ int rm_flood_read(rm_context *ctx, const int32_t *nodes, int32_t n, rm_flood_nod
 int rm_flood_device(rm_context *ctx, const rm_flood_node **dev_node, const rm_flood_totals **dev_totals);
 /* the measured tree: parent and hop by node index, int32[n_nodes] each, in device memory (dev_hop may be NULL); not waited for */
 int rm_flood_tree_device(rm_context *ctx, int32_t *dev_parent, int32_t *dev_hop);
+
+/* ---- neighbour tables: discover, evict and expire watched peers on the device ----------------------------------------------------
+ * (not reference behaviour.)  What a link estimator's neighbour table does -- learn peers
+ * from the frames heard, keep a small table, throw out the dead and the bad, protect the parent -- on the watched-link
+ * statistics' two tables (peer and rm_link_stats, [n_nodes][K]), by an order-independent rule: at most one admission per receiver
+ * per finished slot, the admitted sender chosen by a maximum, the slot to fill or evict chosen from the tables as they stood at the
+ * start of the call.  No evaluating call changes and the watched links' pass does not change: every call here reads a FINISHED
+ * result, as the unicast query does, or only the tables.  Off by default; then nothing is allocated or launched.  Memory when on:
+ * n_nodes * 40 bytes (a 32-byte row of counters, one 64-bit word of scratch that is 0 between calls) and the host forms' staging.
+ *
+ * Judgments, all on peer and stats as they stand on the stream at the start of the call, for a node d and its slot k:
+ *  EMPTY   peer[d][k] is outside 0 .. n_nodes-1 or equals d.
+ *  PINNED  a pin array was given, pin[d] is in 0 .. n_nodes-1 and peer[d][k] == pin[d].  The parent arrays of the hop, route and
+ *          measured-route queries and of rm_flood_tree_device go in as they lie in device memory.
+ *  STALE AT t  timeout_us > 0 and (last_start_us == INT64_MIN, or t >= timeout_us and last_start_us < t - timeout_us): a watched
+ *          entry that never heard anything is stale.
+ *  POOR    evict_cost > 0, heard >= max(min_heard, 1) and (delivered == 0 or c_in > evict_cost), with
+ *          c_in = max(128, (128 * heard + (delivered >> 1)) / delivered) in uint64: the measured-route query's entry cost.
+ *
+ * rm_nbtable_update*: slot and state rules as rm_flood_advance*.  A slot that overflowed its link capacity or was dropped: nothing
+ * changes but skipped_slots++.  Any other slot: updates++, then
+ *  (1) BIDS.  Link i of the slot, of packet p, s = recs[p].src, d = dst[i], bids iff s and d are node indices, s != d, no slot of
+ *      row d holds s, rssi[i] >= admit_rssi_dbm (NaN fails) and, with require_delivered, the link's final verdict is RM_DELIVERED.
+ *      Its key is (qc, -s), qc = rm_linkstats_q8(rssi[i]) clamped to -2^30 .. 2^30: the greatest qc wins, ties go to the least s.
+ *  (2) SETTLE.  A node d with a winning bid s takes the first that applies: (a) its lowest empty slot; (b) among the slots that are
+ *      not pinned and stale at time_us the least (last_start_us, k): evicted_stale[d]++; (c) among the slots that are not pinned
+ *      and poor those with delivered == 0 first (the least k of them), then the greatest c_in, then the least k:
+ *      evicted_poor[d]++; (d) refused[d]++ and nothing changes.  In (a) to (c) peer[d][k] = s, the entry is cleared and
+ *      admitted[d]++.
+ *  (3) COUNT.  Every link of the slot from an admitted s to its d -- duplicates, undelivered and weak copies included -- is added
+ *      to the fresh entry exactly as the watched links' pass adds a link.  ticks_counted / ticks_skipped are not touched.
+ * A row's valid entries stay distinct.  The answer is a pure function of (the tables at the start, the slot's result, the
+ * parameters, time_us, pin): nothing depends on launch geometry or on the order in which atomics land.
+ * The watched links' pass counts a whole batch before the first update of its slots can run: a peer admitted from slot b of a
+ * batch is not counted in slots b+1 .. of that batch, and is when the ticks run one by one with an update after each.  Both orders
+ * are deterministic and equal rm_nbtable_from_result applied in the same order.
+ *
+ * rm_nbtable_expire*: one walk over the table; every slot that is not empty, not pinned and stale at time_us becomes empty (peer
+ * -1, the entry cleared, expired[d]++).  Poor slots are left alone.  No result slot is read.
+ *
+ * Identities: the per-node sums are the totals; per node and in total admitted >= evicted_stale + evicted_poor.
+ * The device forms are enqueued on the context's stream and not waited for; the host forms upload the pin array first.
+ * RM_ERR_INVALID, nothing launched: bad parameters or a non-zero reserved field, NULL ctx or params, negative time_us, slot outside
+ * the last call's slots, a host pin entry >= n_nodes (negative host entries: no pin; device entries outside the table pin
+ * nothing).  RM_ERR_STATE, nothing launched: the feature off, the watched-link statistics off, for update what rm_unicast_query
+ * refuses (no evaluated result, a receiver partition, a gathered / rm_dist_* / rm_group_* form), rm_nbtable_enable on a context
+ * made under RM_GRAPH=1 or without nodes.  Arguments are checked before state.
+ * rm_linkstats_enable with the same K keeps everything; K = 0, another K or rm_nodes_upload with another node count switch this
+ * feature off with the statistics.  rm_linkstats_reset makes every entry stale.  rm_linkstats_watch* stays allowed.  Out of
+ * scope: replacing a healthy neighbour, several admissions per node and slot, smoothing, blacklists, K > 8, partitions. */
+typedef struct rm_nbtable_params {
+    double admit_rssi_dbm;     /* finite; a link below it never bids */
+    int64_t timeout_us;        /* 0 .. 2^62; 0: no slot is ever stale */
+    uint32_t min_heard;        /* 0 .. 2^31 */
+    uint32_t evict_cost;       /* 0, or 128 .. 2^32-1, in units of 1/128; 0: no slot is ever poor */
+    int32_t require_delivered; /* 0 or 1 */
+    int32_t reserved;          /* 0 */
+} rm_nbtable_params; /* 32 bytes */
+typedef struct rm_nbtable_node { /* 32 bytes: the table's row */
+    uint32_t admitted, evicted_stale, evicted_poor, refused, expired, reserved[3];
+} rm_nbtable_node;
+typedef struct rm_nbtable_totals {
+    uint64_t updates, skipped_slots, admitted, evicted_stale, evicted_poor, refused, expired, reserved;
+} rm_nbtable_totals; /* 64 bytes */
+void rm_nbtable_defaults(rm_nbtable_params *p); /* -95.0 dBm, 60 000 000 us, min_heard 4, evict_cost 1024, require_delivered 1 */
+/* pure host function, no device: RM_OK or RM_ERR_INVALID */
+int rm_nbtable_validate(const rm_nbtable_params *p);
+/* enable (again: new parameters, counters and totals zero; the statistics' tables are never touched here), release, state */
+int rm_nbtable_enable(rm_context *ctx, const rm_nbtable_params *p);
+int rm_nbtable_disable(rm_context *ctx);
+int rm_nbtable_enabled(const rm_context *ctx);
+int rm_nbtable_get_params(const rm_context *ctx, rm_nbtable_params *out);
+int rm_nbtable_reset(rm_context *ctx); /* counters and totals zero; the statistics' tables are left alone */
+int rm_nbtable_update_device(rm_context *ctx, int32_t slot, int64_t time_us, const int32_t *dev_pin /* [n_nodes] or NULL */);
+int rm_nbtable_update(rm_context *ctx, int32_t slot, int64_t time_us, const int32_t *pin /* [n_nodes] or NULL */); /* uploads pin */
+int rm_nbtable_expire_device(rm_context *ctx, int64_t time_us, const int32_t *dev_pin /* [n_nodes] or NULL */);
+int rm_nbtable_expire(rm_context *ctx, int64_t time_us, const int32_t *pin /* [n_nodes] or NULL */);
+/* n rows (nodes NULL: all, n = n_nodes) and the totals (may be NULL; out may be NULL with n = 0); synchronises.  The peers and the
+ * entries are read with rm_linkstats_peers_get and rm_linkstats_read. */
+int rm_nbtable_read(rm_context *ctx, const int32_t *nodes, int32_t n, rm_nbtable_node *out, rm_nbtable_totals *totals);
+/* the counters in device memory (valid until disable, another enable, or the statistics going off); either pointer may be NULL */
+int rm_nbtable_device(rm_context *ctx, const rm_nbtable_node **dev_node, const rm_nbtable_totals **dev_totals);
+/* pure host functions, no device: the update rule over one tick's host result (src[n_packets] and start_us[n_packets] are the
+ * packets' sources and starts; reads pkt_offset, dst, verdict, rssi or pkt_rssi, sinr) and the expire walk, on host tables peer
+ * and stats [n_nodes][K] in place; node [n_nodes] and totals are ADDED to (either may be NULL).  A host result has no lost flag:
+ * capacity problems are the caller's.  RM_ERR_INVALID: NULL arguments, bad parameters, K not 1, 2, 4 or 8, n_nodes < 0, negative
+ * time_us, a pin entry >= n_nodes. */
+int rm_nbtable_from_result(const rm_host_result *r, const int32_t *src, const int64_t *start_us, int32_t n_nodes, int32_t K, int32_t *peer,
+                           rm_link_stats *stats, const rm_nbtable_params *params, int64_t time_us, const int32_t *pin /* or NULL */,
+                           rm_nbtable_node *node, rm_nbtable_totals *totals);
+int rm_nbtable_expire_tables(int32_t n_nodes, int32_t K, int32_t *peer, rm_link_stats *stats, const rm_nbtable_params *params, int64_t time_us,
+                             const int32_t *pin /* or NULL */, rm_nbtable_node *node, rm_nbtable_totals *totals);
 
 /* ---- several devices behind one caller --------------------------------------------------------------
  * The reference host is ONE process (Main.java:65-73): a group drives n contexts from one host thread, one

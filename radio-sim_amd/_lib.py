@@ -163,6 +163,18 @@ FLOOD_TOTALS_DTYPE = np.dtype([(f, "<u8") for f in ("covered", "seeds", "sent", 
                                                     "max_hop", "last_first_us")])
 assert C.sizeof(FloodParams) == 32 and FLOOD_NODE_DTYPE.itemsize == 64 and FLOOD_TOTALS_DTYPE.itemsize == 80
 
+
+class NbTableParams(C.Structure):
+    """rm_nbtable_params: the neighbour tables' parameters (32 bytes)"""
+    _fields_ = [("admit_rssi_dbm", C.c_double), ("timeout_us", C.c_int64), ("min_heard", C.c_uint32), ("evict_cost", C.c_uint32),
+                ("require_delivered", C.c_int32), ("reserved", C.c_int32)]
+
+
+NBTABLE_NODE_DTYPE = np.dtype([(f, "<u4") for f in ("admitted", "evicted_stale", "evicted_poor", "refused", "expired")] + [("reserved", "<u4", (3,))])
+NBTABLE_TOTALS_DTYPE = np.dtype([(f, "<u8") for f in ("updates", "skipped_slots", "admitted", "evicted_stale", "evicted_poor", "refused", "expired",
+                                                      "reserved")])
+assert C.sizeof(NbTableParams) == 32 and NBTABLE_NODE_DTYPE.itemsize == 32 and NBTABLE_TOTALS_DTYPE.itemsize == 64
+
 NODE_STATS_DTYPE = np.dtype([(name, "<u8") for name, _ in NodeStats._fields_])
 assert NODE_STATS_DTYPE.itemsize == C.sizeof(NodeStats) == 64
 
@@ -531,6 +543,23 @@ SIGNATURES = {
     "rm_flood_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "rm_flood_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "rm_flood_tree_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_nbtable_defaults": (None, [C.POINTER(NbTableParams)]),
+    "rm_nbtable_validate": (C.c_int, [C.POINTER(NbTableParams)]),
+    "rm_nbtable_enable": (C.c_int, [C.c_void_p, C.POINTER(NbTableParams)]),
+    "rm_nbtable_disable": (C.c_int, [C.c_void_p]),
+    "rm_nbtable_enabled": (C.c_int, [C.c_void_p]),
+    "rm_nbtable_get_params": (C.c_int, [C.c_void_p, C.POINTER(NbTableParams)]),
+    "rm_nbtable_reset": (C.c_int, [C.c_void_p]),
+    "rm_nbtable_update_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
+    "rm_nbtable_update": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
+    "rm_nbtable_expire_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "rm_nbtable_expire": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "rm_nbtable_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rm_nbtable_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "rm_nbtable_from_result": (C.c_int, [C.POINTER(HostResult), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                         C.POINTER(NbTableParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_nbtable_expire_tables": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(NbTableParams), C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
     "rm_det_math": (C.c_double, [C.c_int32, C.c_double]),
     "rm_link_hash": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
     "rm_evq_init": (None, [C.c_void_p]),

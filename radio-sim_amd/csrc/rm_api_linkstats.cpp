@@ -50,6 +50,7 @@ static int linkstats_off(rm_context *c)
 {
     rm_context::LinkStats &lk = c->lk;
     if (lk.n >= 0) RM_HIP(hipStreamSynchronize(c->stream)); // (a pass in flight still reads and adds to the tables)
+    nbtable_release(c); // (the neighbour tables, E22, write these tables: they go off with them)
     lk.K = 0;
     lk.n = -1;
     lk.host.clear();

@@ -132,6 +132,7 @@ void passes_release(rm_context *c)
     etx_release(c);
     fwd_release(c);
     flood_release(c);
+    nbtable_release(c);
 }
 
 } // namespace rmh

@@ -947,6 +947,24 @@ RM_D u64 *relay_w(uint64_t *p) { return reinterpret_cast<u64 *>(p); }
 template <typename Dev> RM_D bool relay_in(const Dev &f, int j) { return j >= 0 && j < f.n_nodes; }
 RM_D bool relay_slot_lost(const UcSlot &s) { return s.out_count && uc_lost(s); }
 
+// the slot's links: stored ones only, and none behind the last packet's segment
+RM_D uint32_t relay_links(const UcSlot &s)
+{
+    if (!s.out_count || !s.pkt_offset || !s.dst || !s.verdict || !s.recs || s.n_new <= 0) return 0u;
+    return min(min(s.out_count[0], s.out_count[2]), s.pkt_offset[s.n_new]);
+}
+// the packet of link i < pkt_offset[n_new]: the last p with pkt_offset[p] <= i (empty packets share their offset with the next one)
+RM_D int relay_pkt(const UcSlot &s, const uint32_t i)
+{
+    int lo = 0, hi = s.n_new;
+    while (hi - lo > 1) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (s.pkt_offset[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // the wave's share of a total -- one address for everybody -- added once
 RM_D void relay_total(uint64_t *word, u64 v)
 {

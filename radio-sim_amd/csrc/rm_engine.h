@@ -1156,6 +1156,24 @@ hipError_t launch_flood_sources(hipStream_t s, const FloodDev &f, int64_t time_u
 hipError_t launch_flood_advance(hipStream_t s, const FloodDev &f, const UcSlot &slot, const int32_t *cand, int P);
 hipError_t launch_flood_tree(hipStream_t s, const FloodDev &f, int32_t *parent, int32_t *hop);
 
+// (rm_nbtable.hip) the neighbour tables.  peer / table are the watched-link statistics'
+// tables, which the update and the expire walk WRITE; node / totals are the feature's counters; bid ([n_nodes], 0 at rest) is
+// per-node scratch that every call leaves as it found it.  The rule is the nbt_* text of rm_math.hpp.
+struct NbTableDev {
+    int32_t *peer;        // [n_nodes][K]
+    rm_link_stats *table; // [n_nodes][K]
+    rm_nbtable_node *node;
+    rm_nbtable_totals *totals;
+    uint64_t *bid;
+    int n_nodes, K;
+    rm_nbtable_params p;
+};
+// the counters and the totals zero, the scratch at rest
+hipError_t launch_nbtable_init(hipStream_t s, const NbTableDev &f);
+// four launches: bids over the slot's links, one lane per node settles, the admitted peers' links counted, the scratch back to rest
+hipError_t launch_nbtable_update(hipStream_t s, const NbTableDev &f, const UcSlot &slot, int64_t time_us, const int32_t *pin);
+hipError_t launch_nbtable_expire(hipStream_t s, const NbTableDev &f, int64_t time_us, const int32_t *pin);
+
 // reception stage (rm_events.hip)
 hipError_t launch_ev_append(hipStream_t s, const EvDev &e, const EvLinkSrc &ls, const rm_tx_record *tx, int n_new, int64_t now,
                             int immediate, const uint32_t *dropped_flag);

@@ -151,24 +151,9 @@ __global__ void __launch_bounds__(64) k_flood_src_write(const FloodDev f, const 
 
 // ---- advance
 
-// the slot's links: stored ones only, and none behind the last packet's segment
-RM_D uint32_t flood_links(const UcSlot &s)
-{
-    if (!s.out_count || !s.pkt_offset || !s.dst || !s.verdict || !s.recs || s.n_new <= 0) return 0u;
-    return min(min(s.out_count[0], s.out_count[2]), s.pkt_offset[s.n_new]);
-}
-
-// the packet of link i < pkt_offset[n_new]: the last p with pkt_offset[p] <= i (empty packets share their offset with the next one)
-RM_D int flood_pkt(const UcSlot &s, const uint32_t i)
-{
-    int lo = 0, hi = s.n_new;
-    while (hi - lo > 1) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (s.pkt_offset[mid] <= i) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
+// (the slot's links and a link's packet: relay_links and relay_pkt of rm_device.hpp, shared with the neighbour tables)
+RM_D uint32_t flood_links(const UcSlot &s) { return relay_links(s); }
+RM_D int flood_pkt(const UcSlot &s, const uint32_t i) { return relay_pkt(s, i); }
 
 // d, which has the data, transmits in this call: it owns a packet number at which it is due and that the gate let through
 RM_D bool flood_sends(const FloodDev &f, const UcSlot &s, const int d)

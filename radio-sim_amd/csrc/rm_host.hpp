@@ -349,6 +349,15 @@ struct rm_context : TickSlot {
         DevBuf<int32_t> pmin, act;
         DevBuf<int64_t> tmin;
     } fl;
+    // neighbour tables (E22; rm_api_nbtable.cpp, rm_nbtable.hip): the parameters, the counters by node index and their totals, one
+    // word of scratch per node.  The peers and entries it writes are the watched-link statistics' (lk); of the base it uses the
+    // staging of a host pin array and the block of a list read, never the claim words or the unit counts
+    struct NbTable : Relay {
+        rm_nbtable_params p{};
+        DevBuf<rm_nbtable_node> node;
+        DevBuf<rm_nbtable_totals> totals;
+        DevBuf<uint64_t> bid;
+    } nt;
     double base_rssi = -100.0; // AbstractRadioMedium.java:38
 
     // host mirror of the node table (Simulator.getNodes() snapshot)
@@ -1029,6 +1038,10 @@ void fwd_release(rm_context *c);
 int flood_nodes_changed(rm_context *c);
 // rm_destroy
 void flood_release(rm_context *c);
+
+// ---- rm_api_nbtable.cpp: neighbour tables (E22)
+// the watched-link statistics go off (K = 0, another K, another node count; the stream has been waited for) and rm_destroy
+void nbtable_release(rm_context *c);
 
 // ---- rm_api_comm.cpp
 int comm_all_gather(rm_context *c, const void *mine, void *all, size_t bytes);

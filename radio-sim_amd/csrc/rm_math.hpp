@@ -176,12 +176,17 @@ RM_HD bool route_link_cost(int kind, double us_per_bit, int64_t air_us, double n
 // the measured-route query's entry cost: the rounded 128 * heard / delivered of one watched-link entry
 // -- the text the kernels (rm_etx.hip) and rm_etx_link_cost / rm_etx_from_tables are both built from.  false: the entry is not
 // usable or its cost is above the cap.  128 * H <= 2^47 and D >> 1 < 2^63: the sum cannot wrap.
+// (etx_ratio: the quotient alone, for delivered >= 1 -- also what the neighbour tables judge a poor slot by, E22)
+RM_HD uint64_t etx_ratio(uint64_t heard, uint64_t delivered)
+{
+    const uint64_t q = (128ull * heard + (delivered >> 1)) / delivered;
+    return q < 128ull ? 128ull : q; // (a caller's table with delivered > heard)
+}
 RM_HD bool etx_entry_cost(uint32_t min_heard, uint32_t max_link_cost, uint64_t heard, uint64_t delivered, uint32_t &cost)
 {
     const uint64_t least = min_heard > 1u ? uint64_t(min_heard) : 1ull;
     if (heard < least || heard > (1ull << 40) || delivered < 1ull) return false;
-    uint64_t q = (128ull * heard + (delivered >> 1)) / delivered;
-    if (q < 128ull) q = 128ull; // (a caller's table with delivered > heard)
+    const uint64_t q = etx_ratio(heard, delivered);
     if (q > uint64_t(max_link_cost)) return false;
     cost = uint32_t(q);
     return true;
@@ -288,6 +293,78 @@ RM_HD void flood_fire(const int64_t imin_us, const int32_t doublings, const int3
     h = mix64(h ^ uint64_t(m));
     start_us = first_us + before;
     fire_us = start_us + int64_t(half) + int64_t(uint64_t((static_cast<unsigned __int128>(h) * half) >> 64)); // (one text for host and device)
+}
+
+// the neighbour tables' rule: what the parameters may hold, the judgments of a slot, a bid's key and the
+// choice of the slot a winning bid takes -- the text the kernels (rm_nbtable.hip), rm_nbtable_from_result, rm_nbtable_expire_tables
+// and rm_nbtable_validate are built from.  Integers and one comparison of doubles only.
+RM_HD bool nbt_valid(const rm_nbtable_params &p)
+{
+    if (!(fabs(p.admit_rssi_dbm) < INFINITY)) return false; // (NaN and the infinities)
+    if (p.timeout_us < 0 || p.timeout_us > (int64_t(1) << 62) || p.min_heard > (1u << 31)) return false;
+    if (p.evict_cost != 0u && p.evict_cost < 128u) return false;
+    return (p.require_delivered == 0 || p.require_delivered == 1) && p.reserved == 0;
+}
+RM_HD bool nbt_in(int32_t n_nodes, int32_t j) { return j >= 0 && j < n_nodes; }
+RM_HD bool nbt_empty(int32_t n_nodes, int32_t d, int32_t peer) { return !nbt_in(n_nodes, peer) || peer == d; }
+RM_HD bool nbt_stale(int64_t timeout_us, int64_t t, int64_t last_start_us)
+{
+    if (timeout_us <= 0) return false;
+    return last_start_us == INT64_MIN || (t >= timeout_us && last_start_us < t - timeout_us);
+}
+// c_in: UINT64_MAX with delivered == 0 (above every quotient)
+RM_HD bool nbt_poor(const rm_nbtable_params &p, uint64_t heard, uint64_t delivered, uint64_t &c_in)
+{
+    if (p.evict_cost == 0u || heard < (p.min_heard > 1u ? uint64_t(p.min_heard) : 1ull)) return false;
+    c_in = delivered == 0ull ? UINT64_MAX : etx_ratio(heard, delivered);
+    return c_in > uint64_t(p.evict_cost);
+}
+// a bid's key: (qc, -s) in one word whose rest value 0 is below every bid
+RM_HD uint64_t nbt_key(double rssi, int32_t s)
+{
+    int64_t qc = linkstats_q8(rssi);
+    qc = qc < -(int64_t(1) << 30) ? -(int64_t(1) << 30) : (qc > (int64_t(1) << 30) ? (int64_t(1) << 30) : qc);
+    return (uint64_t(qc + (int64_t(1) << 30) + 1) << 32) | uint64_t(0x7FFFFFFF - s);
+}
+RM_HD int32_t nbt_key_src(uint64_t key) { return int32_t(0x7FFFFFFF - int64_t(key & 0xFFFFFFFFull)); }
+RM_HD bool nbt_bids(const rm_nbtable_params &p, double rssi, bool delivered)
+{
+    return rssi >= p.admit_rssi_dbm && (p.require_delivered == 0 || delivered);
+}
+// the slot of row d (peer[K], st[K], as at the start of the call) a winning bid takes: kind 0 an empty slot, 1 a stale one, 2 a
+// poor one; -1: refused
+RM_HD int nbt_settle(const rm_nbtable_params &p, int32_t n_nodes, int K, int32_t d, const int32_t *peer, const rm_link_stats *st, int64_t t,
+                     int32_t pin, int &kind)
+{
+    kind = 0;
+    for (int k = 0; k < K; ++k)
+        if (nbt_empty(n_nodes, d, peer[k])) return k;
+    const bool pinned = nbt_in(n_nodes, pin);
+    int best = -1;
+    kind = 1;
+    for (int k = 0; k < K; ++k) {
+        if ((pinned && peer[k] == pin) || !nbt_stale(p.timeout_us, t, st[k].last_start_us)) continue;
+        if (best < 0 || st[k].last_start_us < st[best].last_start_us) best = k;
+    }
+    if (best >= 0) return best;
+    uint64_t best_c = 0;
+    kind = 2;
+    for (int k = 0; k < K; ++k) {
+        uint64_t c = 0;
+        if ((pinned && peer[k] == pin) || !nbt_poor(p, st[k].heard, st[k].delivered, c)) continue;
+        if (best < 0 || c > best_c) {
+            best = k;
+            best_c = c;
+        }
+    }
+    return best;
+}
+RM_HD void nbt_clear(rm_link_stats &e)
+{
+    e.heard = e.delivered = 0;
+    e.rssi_q8_sum = e.sinr_q8_sum = 0;
+    e.first_start_us = INT64_MAX;
+    e.last_start_us = INT64_MIN;
 }
 
 // the traffic schedule: what a record may hold, a packet's due time, and the number of a node's packets

@@ -233,27 +233,33 @@ class Engine:
         check(self._L.rm_unicast_query_at_device(self._h, n, dev_slot_ptr, dev_pkt_ptr, dev_want_ptr, C.byref(out)))
 
     @staticmethod
+    def _host_result(result, keep):
+        """a _lib.HostResult as it is, or one over anything with pkt_offset, dst, verdict and rssi or pkt_rssi (sinr optional), e.g.
+        what tick_flush_view returns; the arrays it points into are appended to `keep`"""
+        if isinstance(result, HostResult):
+            return result
+
+        def col(name, dt):
+            a = getattr(result, name, None)
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dt)
+            keep.append(a)
+            return a.ctypes.data
+        off = np.ascontiguousarray(result.pkt_offset, dtype=np.uint32)
+        keep.append(off)
+        rssi = col("rssi", np.float64)
+        return HostResult(count=int(result.count), n_packets=len(off) - 1, pkt_offset=off.ctypes.data, dst=col("dst", np.int32),
+                          verdict=col("verdict", np.uint8), rssi=rssi, sinr=col("sinr", np.float64),
+                          pkt_rssi=None if rssi is not None else col("pkt_rssi", np.float64))
+
+    @staticmethod
     def unicast_from_result(result, src, n_nodes, want, fields=None):
         """rm_unicast_from_result (pure host function): the same answer from one tick's host result -- a _lib.HostResult, or
         anything with pkt_offset, dst, verdict and rssi or pkt_rssi (sinr optional), e.g. what tick_flush_view returns;
         src: the packets' sources (None: every packet sent)"""
         keep = []
-        if isinstance(result, HostResult):
-            r = result
-        else:
-            def col(name, dt):
-                a = getattr(result, name, None)
-                if a is None:
-                    return None
-                a = np.ascontiguousarray(a, dtype=dt)
-                keep.append(a)
-                return a.ctypes.data
-            off = np.ascontiguousarray(result.pkt_offset, dtype=np.uint32)
-            keep.append(off)
-            rssi = col("rssi", np.float64)
-            r = HostResult(count=int(result.count), n_packets=len(off) - 1, pkt_offset=off.ctypes.data, dst=col("dst", np.int32),
-                           verdict=col("verdict", np.uint8), rssi=rssi, sinr=col("sinr", np.float64),
-                           pkt_rssi=None if rssi is not None else col("pkt_rssi", np.float64))
+        r = Engine._host_result(result, keep)
         want = np.ascontiguousarray(want, dtype=np.int32).reshape(-1)
         assert len(want) == r.n_packets
         if src is not None:
@@ -970,6 +976,128 @@ class Engine:
     def flood_tree_device(self, dev_parent_ptr, dev_hop_ptr=None):
         """rm_flood_tree_device: parent (and hop) by node index into int32[n_nodes] arrays in device memory; not waited for"""
         check(self._L.rm_flood_tree_device(self._h, dev_parent_ptr, dev_hop_ptr))
+
+    # -- neighbour tables: discover, evict and expire watched peers on the device (DESIGN.md section 6, E22)
+    @staticmethod
+    def nbtable_params(**kw):
+        """rm_nbtable_defaults with the given fields replaced: admit_rssi_dbm, timeout_us, min_heard, evict_cost, require_delivered"""
+        p = _lib.NbTableParams()
+        _lib.lib().rm_nbtable_defaults(C.byref(p))
+        for k, v in kw.items():
+            if k not in dict(_lib.NbTableParams._fields_):
+                raise TypeError("rm_nbtable_params has no field " + k)
+            setattr(p, k, v)
+        return p
+
+    @staticmethod
+    def nbtable_validate(params):
+        """rm_nbtable_validate (pure host): the return code of the validation rm_nbtable_enable runs (0: accepted)"""
+        return int(_lib.lib().rm_nbtable_validate(C.byref(params)))
+
+    def nbtable_enable(self, params=None, **kw):
+        """rm_nbtable_enable: the counters made (again: cleared) with `params` or nbtable_params(**kw); needs linkstats_enable first"""
+        p = params if params is not None else self.nbtable_params(**kw)
+        check(self._L.rm_nbtable_enable(self._h, C.byref(p)))
+
+    def nbtable_get_params(self):
+        p = _lib.NbTableParams()
+        check(self._L.rm_nbtable_get_params(self._h, C.byref(p)))
+        return p
+
+    def nbtable_disable(self):
+        check(self._L.rm_nbtable_disable(self._h))
+
+    def nbtable_enabled(self):
+        return bool(self._L.rm_nbtable_enabled(self._h))
+
+    def nbtable_reset(self):
+        """rm_nbtable_reset: counters and totals zero; the watched-link statistics' tables are left alone"""
+        check(self._L.rm_nbtable_reset(self._h))
+
+    @staticmethod
+    def _nbtable_pin(pin):
+        return None if pin is None else np.ascontiguousarray(pin, dtype=np.int32).reshape(-1)
+
+    def nbtable_update(self, slot, time_us, pin=None):
+        """rm_nbtable_update: result slot `slot` of the last evaluating call admits at most one new peer per node; pin: int32
+        [n_nodes] of protected peers (negative: none), e.g. the parents of a route query, or None"""
+        p = self._nbtable_pin(pin)
+        if p is not None and p.shape[0] != int(self._L.rm_node_count(self._h)):
+            raise ValueError("one pin entry per node")
+        check(self._L.rm_nbtable_update(self._h, int(slot), int(time_us), _ptr(p)))
+
+    def nbtable_update_device(self, slot, time_us, dev_pin_ptr=None):
+        """The raw form: pin as int32[n_nodes] in device memory (or None); enqueued on the context's stream, not waited for"""
+        check(self._L.rm_nbtable_update_device(self._h, int(slot), int(time_us), dev_pin_ptr))
+
+    def nbtable_expire(self, time_us, pin=None):
+        """rm_nbtable_expire: every slot that is not empty, not pinned and stale at time_us becomes empty"""
+        p = self._nbtable_pin(pin)
+        if p is not None and p.shape[0] != int(self._L.rm_node_count(self._h)):
+            raise ValueError("one pin entry per node")
+        check(self._L.rm_nbtable_expire(self._h, int(time_us), _ptr(p)))
+
+    def nbtable_expire_device(self, time_us, dev_pin_ptr=None):
+        check(self._L.rm_nbtable_expire_device(self._h, int(time_us), dev_pin_ptr))
+
+    def nbtable_read(self, nodes=None):
+        """rm_nbtable_read: (structured array of NBTABLE_NODE_DTYPE -- the listed nodes in list order, or all --, the totals as a
+        dict); the peers and entries themselves are linkstats_peers and linkstats_read"""
+        ptr, n, _idx = self._node_list(nodes)
+        out = np.zeros(n, dtype=_lib.NBTABLE_NODE_DTYPE)
+        tot = np.zeros(1, dtype=_lib.NBTABLE_TOTALS_DTYPE)
+        check(self._L.rm_nbtable_read(self._h, ptr, n, out.ctypes.data if n else None, tot.ctypes.data))
+        return out, {k: int(tot[k][0]) for k in tot.dtype.names}
+
+    def nbtable_device(self):
+        """rm_nbtable_device: device pointers (rows [n_nodes] of 32 bytes, totals)"""
+        a, t = C.c_void_p(), C.c_void_p()
+        check(self._L.rm_nbtable_device(self._h, C.byref(a), C.byref(t)))
+        return a.value, t.value
+
+    @staticmethod
+    def _nbtable_host_tables(peer, stats, node, totals):
+        if peer.dtype != np.int32 or peer.ndim != 2 or not peer.flags.c_contiguous:
+            raise ValueError("peer is a C-contiguous int32 [n_nodes][K] array, updated in place")
+        if stats.dtype != _lib.LINK_STATS_DTYPE or stats.shape != peer.shape or not stats.flags.c_contiguous:
+            raise ValueError("stats is a C-contiguous LINK_STATS_DTYPE [n_nodes][K] array, updated in place")
+        n = peer.shape[0]
+        if node is None:
+            node = np.zeros(n, dtype=_lib.NBTABLE_NODE_DTYPE)
+        if totals is None:
+            totals = np.zeros(1, dtype=_lib.NBTABLE_TOTALS_DTYPE)
+        if node.dtype != _lib.NBTABLE_NODE_DTYPE or node.shape != (n,) or totals.dtype != _lib.NBTABLE_TOTALS_DTYPE or totals.shape != (1,):
+            raise ValueError("node is NBTABLE_NODE_DTYPE [n_nodes] and totals NBTABLE_TOTALS_DTYPE [1], both added to")
+        return n, peer.shape[1], node, totals
+
+    @staticmethod
+    def nbtable_from_result(result, src, start_us, peer, stats, params, time_us, pin=None, node=None, totals=None):
+        """rm_nbtable_from_result (pure host function): the update rule over one tick's host result (as unicast_from_result takes
+        it) with the packets' src and start_us; peer (int32 [n][K]) and stats (LINK_STATS_DTYPE [n][K]) change in place, node and
+        totals (made when None) are added to -> (node, totals)"""
+        keep = []
+        r = Engine._host_result(result, keep)
+        n, K, node, totals = Engine._nbtable_host_tables(peer, stats, node, totals)
+        src = np.ascontiguousarray(src, dtype=np.int32).reshape(-1)
+        start = np.ascontiguousarray(start_us, dtype=np.int64).reshape(-1)
+        assert len(src) == len(start) == r.n_packets
+        p = Engine._nbtable_pin(pin)
+        if p is not None and p.shape[0] != n:
+            raise ValueError("one pin entry per node")
+        check(_lib.lib().rm_nbtable_from_result(C.byref(r), _ptr(src), _ptr(start), n, K, peer.ctypes.data, stats.ctypes.data, C.byref(params),
+                                                int(time_us), _ptr(p), node.ctypes.data, totals.ctypes.data))
+        return node, totals
+
+    @staticmethod
+    def nbtable_expire_tables(peer, stats, params, time_us, pin=None, node=None, totals=None):
+        """rm_nbtable_expire_tables (pure host function): the expire walk over host tables, in place -> (node, totals)"""
+        n, K, node, totals = Engine._nbtable_host_tables(peer, stats, node, totals)
+        p = Engine._nbtable_pin(pin)
+        if p is not None and p.shape[0] != n:
+            raise ValueError("one pin entry per node")
+        check(_lib.lib().rm_nbtable_expire_tables(n, K, peer.ctypes.data, stats.ctypes.data, C.byref(params), int(time_us), _ptr(p),
+                                                  node.ctypes.data, totals.ctypes.data))
+        return node, totals
 
     # -- java.util.Random
     def seed(self, seed):

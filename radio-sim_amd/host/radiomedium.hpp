@@ -1001,6 +1001,75 @@ public:
         }
         return true;
     }
+    // Neighbour tables (extension E22): the watched links' peer rows learnt from the frames heard.  setLinkWatch(K) comes first;
+    // setNeighbourTable(&params) switches the rule on (nullptr: off; the watch tables stay); updateNeighbours reads the LAST
+    // evaluated tick -- the tick mode's flush -- and admits at most one new peer per node, into an empty slot or in place of a
+    // stale or poor one that is not pinned; expireNeighbours empties the stale slots that are not pinned.  pinned: empty, or one
+    // entry per node of Simulator.getNodes() (nullptr: no pin), e.g. the parents of measuredRoutes.  The rows are the device's:
+    // watchLinks still sets them, and what it set before is not restored over what was learnt.  false and lastError on a refusal.
+    static rm_nbtable_params neighbourTableDefaults()
+    {
+        rm_nbtable_params p;
+        rm_nbtable_defaults(&p);
+        return p;
+    }
+    bool setNeighbourTable(const rm_nbtable_params *params)
+    {
+        lastError.clear();
+        if (params && (!syncNodes() || !restoreLinkWatch())) return false;
+        if ((params ? rm_nbtable_enable(ctx_, params) : rm_nbtable_disable(ctx_)) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        return true;
+    }
+    bool getNeighbourTable() const { return rm_nbtable_enabled(ctx_) != 0; }
+    bool updateNeighbours(int64_t time, const std::vector<const Node *> &pinned = {})
+    {
+        lastError.clear();
+        std::vector<int32_t> pin;
+        if (!neighbourPins(pinned, pin)) return false;
+        if (rm_nbtable_update(ctx_, 0, time, pinned.empty() ? nullptr : pin.data()) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        return true;
+    }
+    bool expireNeighbours(int64_t time, const std::vector<const Node *> &pinned = {})
+    {
+        lastError.clear();
+        std::vector<int32_t> pin;
+        if (!neighbourPins(pinned, pin)) return false;
+        if (rm_nbtable_expire(ctx_, time, pinned.empty() ? nullptr : pin.data()) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        return true;
+    }
+    // the node's counters; totals (may be nullptr); peers (may be nullptr): the node's K slots, nullptr for an empty one
+    bool getNeighbourTableStatistics(const Node &node, rm_nbtable_node *out, rm_nbtable_totals *totals = nullptr, std::vector<Node *> *peers = nullptr)
+    {
+        lastError.clear();
+        const int32_t i = node.index;
+        if (!out || !simulator || !syncNodes()) return false;
+        if (rm_nbtable_read(ctx_, &i, 1, out, totals) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        if (peers) {
+            const int K = rm_linkstats_enabled(ctx_);
+            std::vector<int32_t> row(size_t(K > 0 ? K : 0) + 1);
+            if (K <= 0 || rm_linkstats_peers_get(ctx_, &i, 1, row.data()) != RM_OK) {
+                lastError = K <= 0 ? "no watched-link statistics: setLinkWatch(K) comes first" : rm_last_error();
+                return false;
+            }
+            const std::vector<Node *> &nodes = simulator->getNodes();
+            peers->assign(size_t(K), nullptr);
+            for (int k = 0; k < K; ++k)
+                if (row[size_t(k)] >= 0 && size_t(row[size_t(k)]) < nodes.size() && row[size_t(k)] != i) (*peers)[size_t(k)] = nodes[size_t(row[size_t(k)])];
+        }
+        return true;
+    }
     // Did a frame reach the node it was addressed to (extension E12)?  One entry per packet of the LAST evaluated tick -- the tick
     // mode's flush, or transmitIfClear() -- in packet order: destinations[k] is packet k's intended receiver (nullptr: not asked).
     // status is RM_UC_*; link the index of the heard link in the tick's result (-1 without one); rssi and sinr as the result has
@@ -1090,6 +1159,17 @@ protected:
             lastError = rm_last_error();
             return false;
         }
+        return true;
+    }
+    // the pin array of updateNeighbours / expireNeighbours: empty, or one entry per node (nullptr: -1)
+    bool neighbourPins(const std::vector<const Node *> &pinned, std::vector<int32_t> &pin)
+    {
+        if (!simulator || !syncNodes()) return false;
+        if (!pinned.empty() && pinned.size() != simulator->getNodes().size()) {
+            lastError = "neighbour tables: one pinned peer (or nullptr) per node, or none at all";
+            return false;
+        }
+        for (const Node *nd : pinned) pin.push_back(nd ? nd->index : -1);
         return true;
     }
     // the schedules the medium set, set again where the engine has dropped them (a node table of another size clears its tables), as
