@@ -1472,6 +1472,107 @@ int rm_nbtable_from_result(const rm_host_result *r, const int32_t *src, const in
 int rm_nbtable_expire_tables(int32_t n_nodes, int32_t K, int32_t *peer, rm_link_stats *stats, const rm_nbtable_params *params, int64_t time_us,
                              const int32_t *pin /* or NULL */, rm_nbtable_node *node, rm_nbtable_totals *totals);
 
+/* ---- link estimator: EWMA ETX over counter windows and forwarding acks ----------------------------------------------------------
+ * (not reference behaviour.)  What CTP's 4-bit estimator or Contiki's link-stats keep per
+ * neighbour: a smoothed ETX in the measured-route query's units of 1/128, fed by windows of the watched links' counters (beacon
+ * samples) and by windows of the forwarding queues' acked / failed attempts toward the current next hop (data samples).  The
+ * estimator READS a watch table (peer and rm_link_stats, [n_nodes][K]) and optionally a forwarding table (rm_fwd_node [n_nodes])
+ * -- the context's own or the caller's -- and never writes them: rm_linkstats_reset is not needed to start a window, so the
+ * neighbour tables' stale and poor judgments stay as they are.  It keeps tables of its own: an rm_linkest_entry per (node, slot),
+ * an rm_linkest_node per node, the totals, and the PUBLISHED table -- a valid rm_etx_tables (rm_linkest_tables) whose entry with an
+ * estimate is {heard = etx, delivered = 128, 0, 0, INT64_MAX, INT64_MIN} and whose entry without one is the cleared entry, with
+ * pub_peer == entry.peer.  The measured-route query's c_in of such an entry is exactly etx (128 .. 65535), so rm_etx_query_device
+ * over rm_linkest_tables with min_heard <= 128 routes over the smoothed costs.  Off by default; then nothing is allocated or
+ * launched.  Memory when on: n_nodes * (K * 84 + 32) bytes.  No evaluating call changes.
+ *
+ * rm_linkest_fold*: one launch.  inputs == NULL: the context's E14 tables, and E19's rows while E19 is on (else no data step).
+ * All judgments are on the inputs as they stand on the stream at the start of the call; the result is a pure function of (the
+ * state at the start, the inputs, the parameters) and does not depend on launch geometry or on the order of atomics.  folds++.
+ *  ewma(a, old, s) = s when old == 0, else (a * old + (256 - a) * s + 128) >> 8 in 64-bit arithmetic: between min(old, s) and
+ *  max(old, s), so within 128 .. max_etx.  The rounding leaves a dead band: under a constant sample s the estimate stops moving
+ *  once (256 - a) * (old - s) <= 128 from above, or (256 - a) * (s - old) < 128 from below (up to 4 units at a = 230; none at a = 0).
+ *  sample(dn, dd) = max_etx when dd == 0, else min(max_etx, max(128, (128 * dn + (dd >> 1)) / dd)) in uint64 arithmetic modulo
+ *  2^64 (exact for dn < 2^57).
+ *  BEACON STEP, entry (j, k), p = peer[j][k], H = heard, D = delivered:
+ *  (1) p empty (outside 0 .. n_nodes-1, or j): the entry becomes {0, 0, 0, 0, 0, -1}; cleared++ if entry.peer was not -1.
+ *  (2) else if p != entry.peer or H < base_heard or D < base_delivered: the entry becomes {0, 0, 0, 0, 0, p}; restarted++ per node
+ *      and in total (an admission, an eviction, rm_linkstats_watch, rm_linkstats_reset).
+ *  (3) then, kept or restarted: dH = H - base_heard, dD = D - base_delivered; if beacon_window > 0 and dH >= beacon_window:
+ *      etx = ewma(beacon_alpha_q8, etx, sample(dH, dD)), windows++, beacon_samples++, base_heard = H, base_delivered = D.
+ *  DATA STEP, node j, only with a forwarding table and data_window > 0, after the row's beacon step; w = fwd[j].next,
+ *  A = acked, T = acked + failed (deferred attempts were not on the air):
+ *  (1) w != base_next or T < base_tx or A < base_ack: base_next = w, base_tx = T, base_ack = A, no sample.
+ *  (2) else if w is a node index other than j and T - base_tx >= data_window: dT = T - base_tx, dA = A - base_ack, base_tx = T,
+ *      base_ack = A; with k the lowest slot of row j whose entry.peer == w: none: data_unmatched++ per node and in total; else
+ *      etx[j][k] = ewma(data_alpha_q8, etx, sample(dT, dA)), data_windows++ of the entry, data_samples++ per node and in total.
+ *  estimates is the number of entries with etx != 0.  The published entry is rewritten whenever etx or peer changes.
+ * Identities: the per-node restarted / data_samples / data_unmatched sum to the totals; beacon_samples is the sum of windows and
+ * data_samples the sum of data_windows over entries that were not cleared or restarted since.
+ * The device form is enqueued on the context's stream and not waited for; the host form uploads the inputs first.
+ * RM_ERR_INVALID, nothing launched: NULL ctx or params, what rm_linkest_validate refuses, K outside {1, 2, 4, 8}, explicit inputs
+ * with another K than the enabled one, a non-zero reserved field, a NULL peer or stats, or (device form) peer not aligned to 4 K
+ * bytes, stats or fwd not to 8.  RM_ERR_STATE, nothing launched: the feature off; inputs == NULL while E14 is off or has another
+ * K; a context with a receiver partition; between rm_tick_begin and rm_tick_flush; rm_linkest_enable on a context made under
+ * RM_GRAPH=1 or without nodes.  Arguments are checked before state.  rm_nodes_upload with another node count switches the feature
+ * off; rm_linkstats_enable with another K leaves it on, and own-table folds are RM_ERR_STATE until rm_linkest_enable with that K;
+ * rm_node_update, rm_nodes_move, rm_set_model and rm_seed keep everything.  Out of scope: samples over the sender's sent count
+ * (E11), the neighbour tables judging by the estimate, estimate-aware hysteresis, K > 8, partitions and the multi-rank forms. */
+typedef struct rm_linkest_params {
+    uint32_t beacon_window;   /* 0 .. 2^31 heard frames per beacon sample; 0: no beacon samples */
+    uint32_t data_window;     /* 0 .. 2^31 acked + failed attempts per data sample; 0: no data samples */
+    uint32_t beacon_alpha_q8; /* 0 .. 255: the weight of the OLD estimate out of 256 */
+    uint32_t data_alpha_q8;   /* 0 .. 255 */
+    uint32_t max_etx;         /* 128 .. 65535, in units of 1/128: a sample's cap, and a window without a delivery */
+    uint32_t reserved;        /* 0 */
+} rm_linkest_params; /* 24 bytes */
+typedef struct rm_linkest_entry {
+    uint64_t base_heard, base_delivered; /* the counters at the last sample or restart */
+    uint32_t etx;                        /* 0: no estimate yet; else 128 .. max_etx */
+    uint32_t windows, data_windows;      /* samples folded into etx since the last restart */
+    int32_t peer;                        /* -1: empty */
+} rm_linkest_entry; /* 32 bytes */
+typedef struct rm_linkest_node {
+    uint64_t base_tx, base_ack;
+    int32_t base_next; /* -1 after enable */
+    uint32_t data_samples, data_unmatched, restarted;
+} rm_linkest_node; /* 32 bytes */
+typedef struct rm_linkest_totals {
+    uint64_t folds, beacon_samples, data_samples, data_unmatched, restarted, cleared, estimates, reserved;
+} rm_linkest_totals; /* 64 bytes */
+typedef struct rm_linkest_inputs {
+    const int32_t *peer;        /* [n_nodes][K] */
+    const rm_link_stats *stats; /* [n_nodes][K] */
+    const rm_fwd_node *fwd;     /* [n_nodes], or NULL: no data step */
+    int32_t K;                  /* the enabled K */
+    int32_t reserved;           /* 0 */
+} rm_linkest_inputs;
+void rm_linkest_defaults(rm_linkest_params *p); /* windows 3 and 5, both alphas 230, max_etx 6400: CTP's windows, 0.9, an ETX of 50 */
+/* pure host function, no device: RM_OK or RM_ERR_INVALID */
+int rm_linkest_validate(const rm_linkest_params *p);
+/* enable (again: new K and parameters, everything in its after-enable state; the old tables are released first, so an enable that
+ * fails with RM_ERR_HIP leaves the feature OFF, not as it was), release, state (K, or 0 while off) */
+int rm_linkest_enable(rm_context *ctx, int32_t K, const rm_linkest_params *p);
+int rm_linkest_disable(rm_context *ctx);
+int rm_linkest_enabled(const rm_context *ctx);
+int rm_linkest_get_params(const rm_context *ctx, rm_linkest_params *out);
+int rm_linkest_reset(rm_context *ctx); /* every table back to its after-enable state; K and the parameters stay */
+/* inputs: a host struct (or NULL) whose arrays are device memory; enqueued, not waited for */
+int rm_linkest_fold_device(rm_context *ctx, const rm_linkest_inputs *dev_inputs);
+/* the same with host arrays of any alignment, uploaded first */
+int rm_linkest_fold(rm_context *ctx, const rm_linkest_inputs *inputs);
+/* n rows of K entries (entry_out [n][K]) and of node state (node_out [n]), nodes NULL: all, n = n_nodes; any output may be NULL;
+ * synchronises */
+int rm_linkest_read(rm_context *ctx, const int32_t *nodes, int32_t n, rm_linkest_entry *entry_out, rm_linkest_node *node_out,
+                    rm_linkest_totals *totals);
+/* the tables in device memory (valid until disable, another enable or another node count); any pointer may be NULL */
+int rm_linkest_device(rm_context *ctx, const rm_linkest_entry **dev_entry, const rm_linkest_node **dev_node, const rm_linkest_totals **dev_totals);
+/* the published table as the measured-route query's explicit tables (device pointers; the same lifetime) */
+int rm_linkest_tables(rm_context *ctx, rm_etx_tables *out);
+/* the fold over host arrays in place, a pure host function without a device: entry, pub_peer and pub_stats are [n_nodes][K], node
+ * [n_nodes]; totals (may be NULL) is ADDED to.  RM_ERR_INVALID: NULL arguments, bad parameters or inputs, n_nodes < 0. */
+int rm_linkest_fold_tables(int32_t n_nodes, const rm_linkest_inputs *inputs, const rm_linkest_params *params, rm_linkest_entry *entry,
+                           rm_linkest_node *node, int32_t *pub_peer, rm_link_stats *pub_stats, rm_linkest_totals *totals);
+
 /* ---- several devices behind one caller --------------------------------------------------------------
  * The reference host is ONE process (Main.java:65-73): a group drives n contexts from one host thread, one
  * per device (an ordinal may repeat: several partitions on one GPU).  Receivers are partitioned over the

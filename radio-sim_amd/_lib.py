@@ -175,6 +175,27 @@ NBTABLE_TOTALS_DTYPE = np.dtype([(f, "<u8") for f in ("updates", "skipped_slots"
                                                       "reserved")])
 assert C.sizeof(NbTableParams) == 32 and NBTABLE_NODE_DTYPE.itemsize == 32 and NBTABLE_TOTALS_DTYPE.itemsize == 64
 
+
+class LinkEstParams(C.Structure):
+    """rm_linkest_params: the link estimator's parameters (24 bytes)"""
+    _fields_ = [("beacon_window", C.c_uint32), ("data_window", C.c_uint32), ("beacon_alpha_q8", C.c_uint32), ("data_alpha_q8", C.c_uint32),
+                ("max_etx", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class LinkEstInputs(C.Structure):
+    """rm_linkest_inputs: the tables a fold reads -- peer and stats [n_nodes][K], fwd [n_nodes] or NULL"""
+    _fields_ = [("peer", C.c_void_p), ("stats", C.c_void_p), ("fwd", C.c_void_p), ("K", C.c_int32), ("reserved", C.c_int32)]
+
+
+LINKEST_ENTRY_DTYPE = np.dtype([("base_heard", "<u8"), ("base_delivered", "<u8"), ("etx", "<u4"), ("windows", "<u4"), ("data_windows", "<u4"),
+                                ("peer", "<i4")])
+LINKEST_NODE_DTYPE = np.dtype([("base_tx", "<u8"), ("base_ack", "<u8"), ("base_next", "<i4"), ("data_samples", "<u4"), ("data_unmatched", "<u4"),
+                               ("restarted", "<u4")])
+LINKEST_TOTALS_DTYPE = np.dtype([(f, "<u8") for f in ("folds", "beacon_samples", "data_samples", "data_unmatched", "restarted", "cleared", "estimates",
+                                                      "reserved")])
+assert C.sizeof(LinkEstParams) == 24 and LINKEST_ENTRY_DTYPE.itemsize == 32 and LINKEST_NODE_DTYPE.itemsize == 32
+assert LINKEST_TOTALS_DTYPE.itemsize == 64
+
 NODE_STATS_DTYPE = np.dtype([(name, "<u8") for name, _ in NodeStats._fields_])
 assert NODE_STATS_DTYPE.itemsize == C.sizeof(NodeStats) == 64
 
@@ -560,6 +581,20 @@ SIGNATURES = {
                                          C.POINTER(NbTableParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rm_nbtable_expire_tables": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(NbTableParams), C.c_int64, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
+    "rm_linkest_defaults": (None, [C.POINTER(LinkEstParams)]),
+    "rm_linkest_validate": (C.c_int, [C.POINTER(LinkEstParams)]),
+    "rm_linkest_enable": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(LinkEstParams)]),
+    "rm_linkest_disable": (C.c_int, [C.c_void_p]),
+    "rm_linkest_enabled": (C.c_int, [C.c_void_p]),
+    "rm_linkest_get_params": (C.c_int, [C.c_void_p, C.POINTER(LinkEstParams)]),
+    "rm_linkest_reset": (C.c_int, [C.c_void_p]),
+    "rm_linkest_fold_device": (C.c_int, [C.c_void_p, C.POINTER(LinkEstInputs)]),
+    "rm_linkest_fold": (C.c_int, [C.c_void_p, C.POINTER(LinkEstInputs)]),
+    "rm_linkest_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rm_linkest_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "rm_linkest_tables": (C.c_int, [C.c_void_p, C.POINTER(EtxTables)]),
+    "rm_linkest_fold_tables": (C.c_int, [C.c_int32, C.POINTER(LinkEstInputs), C.POINTER(LinkEstParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
     "rm_det_math": (C.c_double, [C.c_int32, C.c_double]),
     "rm_link_hash": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
     "rm_evq_init": (None, [C.c_void_p]),

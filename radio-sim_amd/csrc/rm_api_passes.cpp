@@ -117,6 +117,7 @@ int passes_nodes_changed(rm_context *c)
     RM_TRY(traffic_nodes_changed(c));
     RM_TRY(fwd_nodes_changed(c));
     RM_TRY(flood_nodes_changed(c));
+    RM_TRY(linkest_nodes_changed(c));
     return linkstats_nodes_changed(c);
 }
 
@@ -133,6 +134,7 @@ void passes_release(rm_context *c)
     fwd_release(c);
     flood_release(c);
     nbtable_release(c);
+    linkest_release(c);
 }
 
 } // namespace rmh

@@ -1174,6 +1174,26 @@ hipError_t launch_nbtable_init(hipStream_t s, const NbTableDev &f);
 hipError_t launch_nbtable_update(hipStream_t s, const NbTableDev &f, const UcSlot &slot, int64_t time_us, const int32_t *pin);
 hipError_t launch_nbtable_expire(hipStream_t s, const NbTableDev &f, int64_t time_us, const int32_t *pin);
 
+// (rm_linkest.hip) the link estimator.  in_peer / in_stats / in_fwd are READ only -- the
+// watched-link statistics' and the forwarding queues' tables, or a caller's; everything else is the feature's own.  The rule is the
+// lest_* text of rm_math.hpp.
+struct LinkEstDev {
+    const int32_t *in_peer;        // [n_nodes][K]
+    const rm_link_stats *in_stats; // [n_nodes][K]
+    const rm_fwd_node *in_fwd;     // [n_nodes] or nullptr: no data step
+    rm_linkest_entry *entry;       // [n_nodes][K]
+    rm_linkest_node *node;         // [n_nodes]
+    int32_t *pub_peer;             // [n_nodes][K]
+    rm_link_stats *pub_stats;      // [n_nodes][K]
+    rm_linkest_totals *totals;
+    int n_nodes, K;
+    rm_linkest_params p;
+};
+// every table in its after-enable state
+hipError_t launch_linkest_init(hipStream_t s, const LinkEstDev &f);
+// one launch: a lane per entry, a row inside one wave
+hipError_t launch_linkest_fold(hipStream_t s, const LinkEstDev &f);
+
 // reception stage (rm_events.hip)
 hipError_t launch_ev_append(hipStream_t s, const EvDev &e, const EvLinkSrc &ls, const rm_tx_record *tx, int n_new, int64_t now,
                             int immediate, const uint32_t *dropped_flag);

@@ -358,6 +358,21 @@ struct rm_context : TickSlot {
         DevBuf<rm_nbtable_totals> totals;
         DevBuf<uint64_t> bid;
     } nt;
+    // link estimator (E23; rm_api_linkest.cpp, rm_linkest.hip): K, the parameters, the entries and the published table
+    // ([n_nodes][K] each), the node state, the totals, and the device copies of a host fold's inputs.  The tables it reads are the
+    // watched-link statistics' (lk) and the forwarding queues' (fw), or the caller's; of the base it uses the block of a list read
+    struct LinkEst : Relay {
+        int32_t K = 0;
+        rm_linkest_params p{};
+        DevBuf<rm_linkest_entry> entry;
+        DevBuf<rm_linkest_node> node;
+        DevBuf<int32_t> pub_peer;
+        DevBuf<rm_link_stats> pub_stats;
+        DevBuf<rm_linkest_totals> totals;
+        DevBuf<int32_t> in_peer;
+        DevBuf<rm_link_stats> in_stats;
+        DevBuf<rm_fwd_node> in_fwd;
+    } le;
     double base_rssi = -100.0; // AbstractRadioMedium.java:38
 
     // host mirror of the node table (Simulator.getNodes() snapshot)
@@ -1042,6 +1057,12 @@ void flood_release(rm_context *c);
 // ---- rm_api_nbtable.cpp: neighbour tables (E22)
 // the watched-link statistics go off (K = 0, another K, another node count; the stream has been waited for) and rm_destroy
 void nbtable_release(rm_context *c);
+
+// ---- rm_api_linkest.cpp: link estimator (E23)
+// rm_nodes_upload: another node count switches the feature off
+int linkest_nodes_changed(rm_context *c);
+// rm_destroy
+void linkest_release(rm_context *c);
 
 // ---- rm_api_comm.cpp
 int comm_all_gather(rm_context *c, const void *mine, void *all, size_t bytes);

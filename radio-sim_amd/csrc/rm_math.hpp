@@ -367,6 +367,91 @@ RM_HD void nbt_clear(rm_link_stats &e)
     e.last_start_us = INT64_MIN;
 }
 
+// the link estimator's rule: what the parameters may hold, the smoothing, a window's sample, the beacon
+// step of one entry, the data step's judgment of one node and the published entry -- the text the kernel (rm_linkest.hip),
+// rm_linkest_fold_tables and rm_linkest_validate are built from.  Unsigned integers only.
+RM_HD bool lest_valid(const rm_linkest_params &p)
+{
+    if (p.beacon_window > (1u << 31) || p.data_window > (1u << 31)) return false;
+    if (p.beacon_alpha_q8 > 255u || p.data_alpha_q8 > 255u) return false;
+    return p.max_etx >= 128u && p.max_etx <= 65535u && p.reserved == 0u;
+}
+// alpha is the weight of the OLD estimate out of 256; 0: no estimate yet.  Between min(old, s) and max(old, s)
+RM_HD uint32_t lest_ewma(uint32_t a, uint32_t old, uint32_t s)
+{
+    if (old == 0u) return s;
+    return uint32_t((uint64_t(a) * old + uint64_t(256u - a) * s + 128ull) >> 8);
+}
+// a window of dn tries of which dd got through: 128 .. max_etx
+RM_HD uint32_t lest_sample(uint32_t max_etx, uint64_t dn, uint64_t dd)
+{
+    if (dd == 0ull) return max_etx;
+    const uint64_t q = etx_ratio(dn, dd);
+    return q > uint64_t(max_etx) ? max_etx : uint32_t(q);
+}
+RM_HD void lest_restart(rm_linkest_entry &e, int32_t peer)
+{
+    e.base_heard = e.base_delivered = 0ull;
+    e.etx = e.windows = e.data_windows = 0u;
+    e.peer = peer;
+}
+enum { LEST_CLEARED = 1, LEST_RESTARTED = 2, LEST_SAMPLED = 4 };
+// the beacon step of entry (j, k) whose input slot holds peer p with counters H, D: what happened, as LEST_* bits
+RM_HD unsigned lest_beacon(const rm_linkest_params &p, int32_t n_nodes, int32_t j, int32_t peer, uint64_t H, uint64_t D, rm_linkest_entry &e)
+{
+    if (nbt_empty(n_nodes, j, peer)) {
+        const unsigned did = e.peer != -1 ? unsigned(LEST_CLEARED) : 0u;
+        lest_restart(e, -1);
+        return did;
+    }
+    unsigned did = 0u;
+    if (peer != e.peer || H < e.base_heard || D < e.base_delivered) {
+        lest_restart(e, peer);
+        did = LEST_RESTARTED;
+    }
+    const uint64_t dH = H - e.base_heard, dD = D - e.base_delivered;
+    if (p.beacon_window > 0u && dH >= uint64_t(p.beacon_window)) {
+        e.etx = lest_ewma(p.beacon_alpha_q8, e.etx, lest_sample(p.max_etx, dH, dD));
+        e.windows += 1u;
+        e.base_heard = H;
+        e.base_delivered = D;
+        did |= LEST_SAMPLED;
+    }
+    return did;
+}
+// the data step's judgment of node j whose forwarding row says next hop w, T = acked + failed, A = acked: true when a sample of
+// (dT, dA) toward w is due (the bases are moved either way)
+RM_HD bool lest_data(const rm_linkest_params &p, int32_t n_nodes, int32_t j, int32_t w, uint64_t T, uint64_t A, rm_linkest_node &nd, uint64_t &dT,
+                     uint64_t &dA)
+{
+    if (w != nd.base_next || T < nd.base_tx || A < nd.base_ack) {
+        nd.base_next = w;
+        nd.base_tx = T;
+        nd.base_ack = A;
+        return false;
+    }
+    if (!nbt_in(n_nodes, w) || w == j || T - nd.base_tx < uint64_t(p.data_window)) return false;
+    dT = T - nd.base_tx;
+    dA = A - nd.base_ack;
+    nd.base_tx = T;
+    nd.base_ack = A;
+    return true;
+}
+RM_HD void lest_data_sample(const rm_linkest_params &p, uint64_t dT, uint64_t dA, rm_linkest_entry &e)
+{
+    e.etx = lest_ewma(p.data_alpha_q8, e.etx, lest_sample(p.max_etx, dT, dA));
+    e.data_windows += 1u;
+}
+// the published entry: c_in of the measured-route query is exactly etx
+RM_HD void lest_publish(uint32_t etx, rm_link_stats &s)
+{
+    nbt_clear(s);
+    if (etx != 0u) {
+        s.heard = uint64_t(etx);
+        s.delivered = 128ull;
+    }
+}
+
 // the traffic schedule: what a record may hold, a packet's due time, and the number of a node's packets
 // due before a time -- the text the generator (rm_traffic.hip), rm_traffic_due and rm_traffic_validate are all built from.
 // 64-bit integers only.

@@ -1099,6 +1099,123 @@ class Engine:
                                                   node.ctypes.data, totals.ctypes.data))
         return node, totals
 
+    # -- link estimator: EWMA ETX over counter windows and forwarding acks
+    @staticmethod
+    def linkest_params(**kw):
+        """rm_linkest_defaults with the given fields replaced: beacon_window, data_window, beacon_alpha_q8, data_alpha_q8, max_etx"""
+        p = _lib.LinkEstParams()
+        _lib.lib().rm_linkest_defaults(C.byref(p))
+        for k, v in kw.items():
+            if k not in dict(_lib.LinkEstParams._fields_):
+                raise TypeError("rm_linkest_params has no field " + k)
+            setattr(p, k, int(v))
+        return p
+
+    @staticmethod
+    def linkest_validate(params):
+        """rm_linkest_validate (pure host): the return code of the validation rm_linkest_enable runs (0: accepted)"""
+        return int(_lib.lib().rm_linkest_validate(C.byref(params)))
+
+    def linkest_enable(self, K, params=None, **kw):
+        """rm_linkest_enable: the tables made (again: in their after-enable state) for K slots per node with `params` or
+        linkest_params(**kw)"""
+        p = params if params is not None else self.linkest_params(**kw)
+        check(self._L.rm_linkest_enable(self._h, int(K), C.byref(p)))
+
+    def linkest_get_params(self):
+        p = _lib.LinkEstParams()
+        check(self._L.rm_linkest_get_params(self._h, C.byref(p)))
+        return p
+
+    def linkest_disable(self):
+        check(self._L.rm_linkest_disable(self._h))
+
+    def linkest_enabled(self):
+        """K, or 0 while the feature is off"""
+        return int(self._L.rm_linkest_enabled(self._h))
+
+    def linkest_reset(self):
+        """rm_linkest_reset: every table back to its after-enable state"""
+        check(self._L.rm_linkest_reset(self._h))
+
+    @staticmethod
+    def _linkest_inputs(peer, stats, fwd, keep):
+        """host arrays (peer int32 [n][K], stats LINK_STATS_DTYPE [n][K], fwd FWD_NODE_DTYPE [n] or None) -> rm_linkest_inputs"""
+        peer = np.ascontiguousarray(peer, dtype=np.int32)
+        stats = np.ascontiguousarray(stats, dtype=_lib.LINK_STATS_DTYPE)
+        if peer.ndim != 2 or stats.shape != peer.shape:
+            raise ValueError("peer and stats are [n_nodes][K]")
+        keep += [peer, stats]
+        f = None
+        if fwd is not None:
+            f = np.ascontiguousarray(fwd, dtype=_lib.FWD_NODE_DTYPE).reshape(-1)
+            if f.shape[0] != peer.shape[0]:
+                raise ValueError("one forwarding row per node")
+            keep.append(f)
+        return _lib.LinkEstInputs(peer=peer.ctypes.data, stats=stats.ctypes.data, fwd=_ptr(f), K=peer.shape[1], reserved=0)
+
+    def linkest_fold(self, peer=None, stats=None, fwd=None):
+        """rm_linkest_fold: one fold over the context's own tables (no arguments: E14's, and E19's while it is on) or over host
+        arrays peer / stats [n_nodes][K] and fwd [n_nodes] (or None: no data step), uploaded first"""
+        if peer is None and stats is None and fwd is None:
+            check(self._L.rm_linkest_fold(self._h, None))
+            return
+        keep = []
+        inp = self._linkest_inputs(peer, stats, fwd, keep)
+        if keep[0].shape[0] != int(self._L.rm_node_count(self._h)):
+            raise ValueError("one row of the inputs per node")
+        check(self._L.rm_linkest_fold(self._h, C.byref(inp)))
+
+    def linkest_fold_device(self, dev_inputs=None):
+        """The raw form: None (the context's own tables) or (peer pointer, stats pointer, fwd pointer or None, K) in device memory;
+        enqueued on the context's stream, not waited for"""
+        if dev_inputs is None:
+            check(self._L.rm_linkest_fold_device(self._h, None))
+            return
+        inp = _lib.LinkEstInputs(peer=dev_inputs[0], stats=dev_inputs[1], fwd=dev_inputs[2], K=int(dev_inputs[3]), reserved=0)
+        check(self._L.rm_linkest_fold_device(self._h, C.byref(inp)))
+
+    def linkest_read(self, nodes=None):
+        """rm_linkest_read: (entries [n][K] of LINKEST_ENTRY_DTYPE, node state [n] of LINKEST_NODE_DTYPE -- the listed nodes in list
+        order, or all --, the totals as a dict)"""
+        ptr, n, _idx = self._node_list(nodes)
+        K = max(self.linkest_enabled(), 1)
+        ent = np.zeros((n, K), dtype=_lib.LINKEST_ENTRY_DTYPE)
+        nod = np.zeros(n, dtype=_lib.LINKEST_NODE_DTYPE)
+        tot = np.zeros(1, dtype=_lib.LINKEST_TOTALS_DTYPE)
+        check(self._L.rm_linkest_read(self._h, ptr, n, ent.ctypes.data if n else None, nod.ctypes.data if n else None, tot.ctypes.data))
+        return ent, nod, {k: int(tot[k][0]) for k in tot.dtype.names}
+
+    def linkest_device(self):
+        """rm_linkest_device: device pointers (entries [n_nodes][K] of 32 bytes, node state [n_nodes] of 32 bytes, totals)"""
+        e, a, t = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(self._L.rm_linkest_device(self._h, C.byref(e), C.byref(a), C.byref(t)))
+        return e.value, a.value, t.value
+
+    def linkest_tables(self):
+        """rm_linkest_tables: the published table as etx_routes_device's dev_tables -- (peer pointer, stats pointer, K)"""
+        t = _lib.EtxTables()
+        check(self._L.rm_linkest_tables(self._h, C.byref(t)))
+        return t.peer, t.stats, int(t.K)
+
+    @staticmethod
+    def linkest_fold_tables(peer, stats, fwd, params, entry, node, pub_peer, pub_stats, totals=None):
+        """rm_linkest_fold_tables (pure host function): one fold over host arrays; entry (LINKEST_ENTRY_DTYPE [n][K]), node
+        (LINKEST_NODE_DTYPE [n]), pub_peer (int32 [n][K]) and pub_stats (LINK_STATS_DTYPE [n][K]) change in place, totals
+        (LINKEST_TOTALS_DTYPE [1], made when None) is added to -> totals"""
+        keep = []
+        inp = Engine._linkest_inputs(peer, stats, fwd, keep)
+        n, K = keep[0].shape
+        for a, dt, shape, what in ((entry, _lib.LINKEST_ENTRY_DTYPE, (n, K), "entry"), (node, _lib.LINKEST_NODE_DTYPE, (n,), "node"),
+                                   (pub_peer, np.dtype(np.int32), (n, K), "pub_peer"), (pub_stats, _lib.LINK_STATS_DTYPE, (n, K), "pub_stats")):
+            if a.dtype != dt or a.shape != shape or not a.flags.c_contiguous:
+                raise ValueError(what + " is a C-contiguous array of its record type, one row per node, updated in place")
+        if totals is None:
+            totals = np.zeros(1, dtype=_lib.LINKEST_TOTALS_DTYPE)
+        check(_lib.lib().rm_linkest_fold_tables(n, C.byref(inp), C.byref(params), entry.ctypes.data, node.ctypes.data, pub_peer.ctypes.data,
+                                                pub_stats.ctypes.data, totals.ctypes.data))
+        return totals
+
     # -- java.util.Random
     def seed(self, seed):
         check(self._L.rm_seed(self._h, seed))

@@ -1070,6 +1070,86 @@ public:
         }
         return true;
     }
+    // Link estimator (extension E23): a smoothed ETX per watched neighbour, folded from windows of the watched links' counters and,
+    // while the forwarding queues are on, of their acked / failed attempts toward the next hop.  setLinkWatch(K) comes first;
+    // setLinkEstimator(&params) makes the tables for that K (nullptr: off; the watch tables stay); foldLinkEstimator() is one
+    // fold over the medium's own tables as they stand; getLinkEstimates reads a node's K entries in slot order, and optionally its
+    // data-step state, the totals and the peers the entries name (nullptr: an empty entry).  The estimate is also a watch table
+    // of its own (linkEstimateTables, device pointers) for rm_etx_query_device.  false and lastError on a refusal.
+    static rm_linkest_params linkEstimatorDefaults()
+    {
+        rm_linkest_params p;
+        rm_linkest_defaults(&p);
+        return p;
+    }
+    bool setLinkEstimator(const rm_linkest_params *params)
+    {
+        lastError.clear();
+        if (!params) {
+            if (rm_linkest_disable(ctx_) != RM_OK) {
+                lastError = rm_last_error();
+                return false;
+            }
+            return true;
+        }
+        if (!syncNodes() || !restoreLinkWatch()) return false;
+        const int K = rm_linkstats_enabled(ctx_);
+        if (K <= 0) {
+            lastError = "setLinkEstimator: setLinkWatch(K) comes first";
+            return false;
+        }
+        if (rm_linkest_enable(ctx_, int32_t(K), params) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        return true;
+    }
+    int getLinkEstimator() const { return rm_linkest_enabled(ctx_); } // K, or 0 while off
+    bool foldLinkEstimator()
+    {
+        lastError.clear();
+        if (!syncNodes()) return false;
+        if (rm_linkest_fold(ctx_, nullptr) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        return true;
+    }
+    bool getLinkEstimates(const Node &node, std::vector<rm_linkest_entry> *entries, rm_linkest_node *state = nullptr, rm_linkest_totals *totals = nullptr,
+                          std::vector<Node *> *peers = nullptr)
+    {
+        lastError.clear();
+        if (!entries || !simulator || !syncNodes()) return false;
+        const int K = rm_linkest_enabled(ctx_);
+        entries->assign(size_t(K > 0 ? K : 0) + 1, rm_linkest_entry{}); // (one spare: never a NULL pointer)
+        const int32_t i = node.index;
+        rm_linkest_node st{};
+        if (rm_linkest_read(ctx_, &i, 1, entries->data(), &st, totals) != RM_OK) {
+            lastError = rm_last_error();
+            entries->clear();
+            return false;
+        }
+        entries->resize(size_t(K));
+        if (state) *state = st;
+        if (peers) {
+            const std::vector<Node *> &nodes = simulator->getNodes();
+            peers->assign(size_t(K), nullptr);
+            for (int k = 0; k < K; ++k) {
+                const int32_t q = (*entries)[size_t(k)].peer;
+                if (q >= 0 && size_t(q) < nodes.size()) (*peers)[size_t(k)] = nodes[size_t(q)];
+            }
+        }
+        return true;
+    }
+    bool linkEstimateTables(rm_etx_tables *out)
+    {
+        lastError.clear();
+        if (rm_linkest_tables(ctx_, out) != RM_OK) {
+            lastError = rm_last_error();
+            return false;
+        }
+        return true;
+    }
     // Did a frame reach the node it was addressed to (extension E12)?  One entry per packet of the LAST evaluated tick -- the tick
     // mode's flush, or transmitIfClear() -- in packet order: destinations[k] is packet k's intended receiver (nullptr: not asked).
     // status is RM_UC_*; link the index of the heard link in the tick's result (-1 without one); rssi and sinr as the result has
